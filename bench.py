@@ -8,12 +8,19 @@ image's 64-row bands are dealt round-robin to the ranks, each rank renders its
 bands with the HIP kernel, and the bands are gathered to rank 0 over RCCL --
 strong scaling: the job is one image whatever N is.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  value = rays traced by all ranks / wall time (the reference's count: every
 World::intersect evaluation, including the area-light shadow rays the light-cone cull answers without an object test;
-`tested_rays_per_s` is the rate of the rays that were tested).  `roofline` names the roof that binds this kernel --
+`tested_rays_per_s` is the rate of the rays that were tested).  `ms_per_step` = wall time of the K timed steps / K.
+
+A plain run sets up, warms up, times the K steps, writes the last step's frame if --dump-outputs is given and prints
+the line.  Everything else is measured or checked only with --full: the parity rows against the CPU oracle
+(`parity_check`), the live roofline counters (child runs under rocprofv3), `one_shot`, `cpu_baseline`, and for N > 1
+the even-split timing and the other wire format.  Without --full, `roofline` quotes committed counters only.
+
+`roofline` names the roof that binds this kernel --
 FP32 VALU issue: VALU wave-instructions x 64 lanes per launch (PMC-measured, taken from the profiles/*_pmc.json whose
 kernel id and workload match the kernel that just ran, else null) / the launch's mean HIP-event duration, against
 256 CU x 4 SIMD x 32 lanes x 2.4 GHz = 78.6 Tlane-op/s; `traffic` = PMC HBM bytes per launch from the same summary.
@@ -34,6 +41,9 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 VALU_PEAK_TOPS = 256 * 4 * 32 * 2.4e9 / 1e12  # 78.6: one non-FMA f32 lane-op per SIMD lane per cycle at the 2.4 GHz peak clock
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_SAMPLE_PIXELS = 1 << 21  # a frame above the limit: this many pixels (24 MB of f32 RGB + 16 MB of f64 indices)
+DUMP_SEED = 0x5EED
 
 
 # BASELINE.json's configurations by name (C1 .. C5) -> (scene function, width, height)
@@ -74,9 +84,16 @@ def parse(argv=None):
                     "the other format is timed beside it")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="N>1 started without a launcher: seconds the "
                     "parent waits for its ranks before ending them")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: parity rows against "
+                    "the CPU oracle, live roofline counters, one_shot, cpu_baseline and (N>1) the even-split and other-wire "
+                    "timings; --cpu-seconds / --no-verify / --no-one-shot / --no-live-pmc act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame the last timed step delivered to "
+                    "DIR/*.npy (float32; a fixed, seeded pixel sample when the frame exceeds %d MB)" % (DUMP_LIMIT_BYTES >> 20))
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     # the workload: a named BASELINE configuration, overridden field by field by --scene / --size / --height
     scene, width, height = WORKLOADS[args.workload or "C3"]
     if args.scene is not None and args.workload is None and args.scene != scene:
@@ -178,6 +195,27 @@ def cpu_baseline(world, camera, depth, budget_s):
                   "reference)" % (sampled, block, camera.width, h, total_rays, total_t),
         "single_thread_value": round(single, 3),
     }
+
+
+def dump_outputs(image, out_dir):
+    """--dump-outputs: the frame a caller of the timed path receives, as float32 .npy files in `out_dir`.  A frame of at
+    most DUMP_LIMIT_BYTES is written whole (image.npy, H x W x 3); a larger one as a fixed, seeded sample of pixels
+    (image_sample.npy, n x 3) with their row-major pixel indices (image_sample_pixels.npy, float64: exact below 2^53).
+    The sample depends on the frame's size only, so two builds' dumps of one workload compare entry by entry."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    h, w, c = image.shape
+    frame = image.to(torch.float32)  # (--wire u8: the bytes Canvas::to_ppm prints, as floats)
+    if h * w * c * 4 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), frame.cpu().numpy())
+        return ["image.npy"]
+    n = min(DUMP_SAMPLE_PIXELS, h * w)
+    pix = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=n, replace=False))
+    rows = frame.reshape(h * w, c).index_select(0, torch.from_numpy(pix).to(frame.device))
+    np.save(os.path.join(out_dir, "image_sample.npy"), rows.cpu().numpy())
+    np.save(os.path.join(out_dir, "image_sample_pixels.npy"), pix.astype(np.float64))
+    return ["image_sample.npy", "image_sample_pixels.npy"]
 
 
 def main(argv=None):
@@ -318,17 +356,18 @@ def main(argv=None):
             extra_parts = 0  # (--force-dist: one rank has nobody to take parts from)
         calib = {"render_ms_even_share": round(k_ms, 4), "gather_ms_even_share_unoverlapped": round(g_ms, 4)}
         if extra_parts > 0:
-            # the even split, timed the same way as the split `value` is measured with: so that the first run on real xGMI
-            # links can be read (is the (N + E)-way split what the calibration promised?)
-            fence()
-            drain()
-            t_even = time.perf_counter()
-            run(args.steps)
-            fence()
-            e_even = torch.tensor([time.perf_counter() - t_even], dtype=torch.float64, device=device)
-            dist.all_reduce(e_even, op=dist.ReduceOp.MAX)
-            calib["even_split_ms_per_step"] = round(float(e_even.item()) / args.steps * 1e3, 4)
-            drain()
+            if args.full:
+                # the even split, timed the same way as the split `value` is measured with: so that the first run on real xGMI
+                # links can be read (is the (N + E)-way split what the calibration promised?)
+                fence()
+                drain()
+                t_even = time.perf_counter()
+                run(args.steps)
+                fence()
+                e_even = torch.tensor([time.perf_counter() - t_even], dtype=torch.float64, device=device)
+                dist.all_reduce(e_even, op=dist.ReduceOp.MAX)
+                calib["even_split_ms_per_step"] = round(float(e_even.item()) / args.steps * 1e3, 4)
+                drain()
             gather = BandGather(camera.height, camera.width, 3, wire_dtype, device, rank, world_size, extra_parts=extra_parts, force_collective=args.force_dist)
             run = make_runner(gather, quantise=wire_u8)
             run(max(2, min(args.warmup, 3)))
@@ -339,6 +378,8 @@ def main(argv=None):
     image = run(args.steps)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and image is not None:  # (rank 0: the gathered frame)
+        dump_outputs(image, args.dump_outputs)
 
     st = drain()  # counters of the last frame's launches + kernel time per frame on this rank
     st["kernel_ms"] = st["kernel_ms"] if st["kernel_ms"] > 0 else 0.0
@@ -358,7 +399,7 @@ def main(argv=None):
     # of the xGMI traffic of the f32 Canvas rows that `value` is measured with.  Never fatal: a failure is reported
     # in the field instead.
     wire = None
-    if dist_on and args.steps > 0:
+    if dist_on and args.full:
         try:
             other = torch.float32 if wire_u8 else torch.uint8  # the format the measured steps did NOT use
             gather8 = BandGather(camera.height, camera.width, 3, other, device, rank, world_size, force_collective=args.force_dist)
@@ -393,14 +434,14 @@ def main(argv=None):
         algo_bytes = st["rays"] * n_obj * 64 + st["shaded_hits"] * 48 + st["pixels"] * 12
         achieved = algo_bytes / (st["kernel_ms"] * 1e-3) / 1e9 if st["kernel_ms"] > 0 else 0.0
         pmc = None
-        if world_size == 1 and not args.no_live_pmc and not args.force_dist:
+        if args.full and world_size == 1 and not args.no_live_pmc and not args.force_dist:
             lp = live_pmc(args, renderer.kernel_id)
             if lp is not None:
                 pmc = ("live", lp)
         if pmc is None and world_size == 1:
             pmc = matching_pmc_summary(renderer.kernel_id, args.scene, camera.width, camera.height)
         verify = None
-        if not args.no_verify and image is not None and image.dtype == torch.float32:
+        if args.full and not args.no_verify and image is not None and image.dtype == torch.float32:
             verify = verify_rows(image, world, camera, depth)  # (the GATHERED frame when the collectives ran)
         line = {
             "metric": "Mrays/s", "value": round(rays / (elapsed / args.steps) / 1e6, 2), "unit": "Mrays/s",
@@ -451,12 +492,12 @@ def main(argv=None):
                                  "render_kernel_ms_max_over_ranks": round(float(kern.item()), 4),
                                  "gathered_bytes_per_step": int(camera.height * camera.width * (3 if wire_u8 else 12) * (world_size - 1) // n_parts),
                                  "wire_format_gather": wire}
-        if world_size == 1 and not args.no_one_shot:
+        if args.full and world_size == 1 and not args.no_one_shot:
             try:
                 line["one_shot"] = one_shot(world, camera, depth)
             except Exception as exc:  # noqa: BLE001 -- informational: never costs the headline line
                 line["one_shot"] = {"error": repr(exc)[:300]}
-        if args.cpu_seconds > 0 and world_size == 1:
+        if args.full and args.cpu_seconds > 0 and world_size == 1:
             line["cpu_baseline"] = cpu_baseline(world, camera, depth, args.cpu_seconds)
         elif world_size > 1:
             line["cpu_baseline"] = None  # measured on rank 0 at N=1 only

@@ -151,3 +151,46 @@ def test_kernel_ids_of_the_committed_summaries_name_the_code_object():
     for p in glob.glob(os.path.join(ROOT, "profiles", "r04_*_pmc.json")):
         kid = json.load(open(p))["kernel_id"]
         assert re.fullmatch(r"spec_[0-9a-f]{16}\.[0-9a-f]{8}", kid), (p, kid)
+
+
+# ---- a plain run, --full and --dump-outputs ------------------------------------------------------------------------
+def test_full_and_dump_outputs_are_off_by_default_and_steps_are_counted():
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None and a.steps == 50
+    a = bench.parse(["--full", "--dump-outputs", "out", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "out" and a.steps == 7
+    import pytest
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])  # ms_per_step needs at least one timed step
+
+
+def test_dump_outputs_writes_a_small_frame_whole(tmp_path):
+    import numpy as np
+    import torch
+    frame = torch.arange(5 * 7 * 3, dtype=torch.float32).reshape(5, 7, 3)
+    assert bench.dump_outputs(frame, str(tmp_path / "d")) == ["image.npy"]
+    got = np.load(tmp_path / "d" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame.numpy())
+    q = torch.full((2, 3, 3), 255, dtype=torch.uint8)  # --wire u8: the bytes, as floats
+    bench.dump_outputs(q, str(tmp_path / "q"))
+    assert np.load(tmp_path / "q" / "image.npy").dtype == np.float32
+
+
+def test_dump_outputs_samples_a_large_frame_the_same_way_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    assert bench.DUMP_SAMPLE_PIXELS * (3 * 4 + 8) <= bench.DUMP_LIMIT_BYTES  # the sample and its indices fit the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 100)
+    h, w = 40, 30
+    frame = torch.rand((h, w, 3), generator=torch.Generator().manual_seed(1))
+    names = bench.dump_outputs(frame, str(tmp_path / "a"))
+    bench.dump_outputs(frame.clone(), str(tmp_path / "b"))
+    assert sorted(names) == sorted(os.listdir(tmp_path / "a")) == ["image_sample.npy", "image_sample_pixels.npy"]
+    rows, pix = np.load(tmp_path / "a" / "image_sample.npy"), np.load(tmp_path / "a" / "image_sample_pixels.npy")
+    assert rows.dtype == np.float32 and rows.shape == (100, 3) and pix.dtype == np.float64 and pix.shape == (100,)
+    assert len(set(pix.tolist())) == 100 and 0 <= pix.min() and pix.max() < h * w
+    assert np.array_equal(rows, frame.numpy().reshape(-1, 3)[pix.astype(np.int64)])
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 4096

@@ -23,10 +23,10 @@ def _bench(args, timeout=900):
 
 
 def test_one_gpu_line_and_self_launched_two_rank_line_agree():
-    one = _bench(["--size", "512", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-one-shot", "--no-live-pmc"])
+    one = _bench(["--full", "--size", "512", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-one-shot", "--no-live-pmc"])
     assert one["n_gpus"] == 1 and one["unit"] == "Mrays/s" and one["scaling"] == "strong" and one["dtype"] == "f32"
     assert one["parity_check"]["rows_checked_bit_exact_vs_oracle"]
-    two = _bench(["--gpus", "2", "--backend", "gloo", "--size", "512", "--steps", "3", "--warmup", "1"])
+    two = _bench(["--full", "--gpus", "2", "--backend", "gloo", "--size", "512", "--steps", "3", "--warmup", "1"])
     assert two["n_gpus"] == 2 and two["steps"] == 3 and two["value"] > 0 and two["ms_per_step"] > 0
     # the job is one image whatever N is: same rays, same shaded hits, same pixels
     for key in ("rays_per_frame", "shaded_hits_per_frame", "pixels_per_frame"):
@@ -42,8 +42,28 @@ def test_one_gpu_line_and_self_launched_two_rank_line_agree():
     assert two["cpu_baseline"] is None and "one_shot" not in two
 
 
+def test_a_plain_line_is_lean_and_dumps_the_timed_frame(tmp_path):
+    """Without --full the line carries the headline figures only -- no oracle rows, no live counters, no one_shot, no CPU
+    baseline -- and --dump-outputs writes the frame the last timed step delivered: the oracle's, bit for bit."""
+    import numpy as np
+
+    from ray_tracer_challenge_amd import scenes
+    from tests import helpers as H
+    line = _bench(["--size", "128", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["parity_check"] is None and "one_shot" not in line and "cpu_baseline" not in line
+    assert not (line["roofline"]["pmc_source"] or "").startswith("live")
+    assert sorted(os.listdir(tmp_path)) == ["image.npy"]
+    img = np.load(tmp_path / "image.npy")
+    world, camera, depth = scenes.soft_shadows(128, 128)
+    exp, rays = H.oracle_camera(camera).render(H.oracle_world(world), depth, threads=4)
+    assert img.dtype == np.float32
+    H.assert_images_equal(img, exp, "bench --dump-outputs")
+    assert line["config"]["rays_per_frame"] == rays
+
+
 def test_workload_selector_runs_c5_by_name():
-    line = _bench(["--workload", "C5", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-one-shot", "--no-live-pmc"])
+    line = _bench(["--full", "--workload", "C5", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-one-shot", "--no-live-pmc"])
     assert line["config"]["workload"].startswith("C5: sphere_grid 8192x8192") and line["config"]["pixels_per_frame"] == 8191 * 8191
     assert line["parity_check"]["rows_checked_bit_exact_vs_oracle"]
 
@@ -58,7 +78,7 @@ def test_the_drivers_launcher_form_still_works():
     s.close()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size", "384",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--size", "384",
                         "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -72,7 +92,7 @@ def test_the_rccl_branch_runs_with_one_rank():
     created --, the band gather through dist.gather on the communication stream, work.wait()'s stream hand-off, the
     calibration and the other wire format, all with ONE rank on the one GPU this box has.  The gathered frame's rows are
     compared with the oracle like any other line's."""
-    line = _bench(["--force-dist", "--size", "512", "--steps", "3", "--warmup", "2", "--cpu-seconds", "0", "--no-one-shot", "--no-live-pmc"])
+    line = _bench(["--full", "--force-dist", "--size", "512", "--steps", "3", "--warmup", "2", "--cpu-seconds", "0", "--no-one-shot", "--no-live-pmc"])
     assert line["n_gpus"] == 1 and line["value"] > 0
     mg = line["multi_gpu"]
     assert mg["backend"] == "nccl (RCCL)" and mg["ranks"] == 1 and mg["forced_with_one_rank"] is True and mg["wire"] == "f32"
@@ -81,19 +101,19 @@ def test_the_rccl_branch_runs_with_one_rank():
     assert line["render_only"]["value"] >= line["value"] * 0.5
     assert line["parity_check"]["rows_checked_bit_exact_vs_oracle"]  # rows of the frame dist.gather delivered
     # ... and with the bytes Canvas::to_ppm prints as the measured wire format
-    u8 = _bench(["--force-dist", "--wire", "u8", "--size", "512", "--steps", "3", "--warmup", "2", "--cpu-seconds", "0", "--no-one-shot", "--no-live-pmc"])
+    u8 = _bench(["--full", "--force-dist", "--wire", "u8", "--size", "512", "--steps", "3", "--warmup", "2", "--cpu-seconds", "0", "--no-one-shot", "--no-live-pmc"])
     assert u8["multi_gpu"]["wire"] == "u8" and u8["multi_gpu"]["wire_format_gather"]["equals_quantised_f32_frame"] is True
     assert u8["parity_check"]["rows_checked_bit_exact_vs_oracle"]
     assert u8["config"]["rays_per_frame"] == line["config"]["rays_per_frame"]
 
 
 def test_the_roofline_counters_are_collected_live():
-    """Without --no-live-pmc the one-GPU line measures its own counters (child runs under rocprofv3 --pmc, one group each): the
+    """With --full and without --no-live-pmc the one-GPU line measures its own counters (child runs under rocprofv3 --pmc, one group each): the
     VALU instruction count and the HBM-side bytes belong to the kernel that was timed, whatever profiles/ holds."""
     import shutil
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("no rocprofv3 on this box")
-    line = _bench(["--size", "1024", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-one-shot"])
+    line = _bench(["--full", "--size", "1024", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-one-shot"])
     roof = line["roofline"]
     assert roof["pmc_source"].startswith("live"), roof
     pixels = 1023 * 1023

@@ -2,6 +2,7 @@
 # a round's final evidence set (bash tools/final_evidence.sh r04): profiles (kernel trace + PMC) of eight scenes, timelines, configuration table, whole-frame verification, bench line
 TAG=${1:-r04}
 mkdir -p gpurun_out/$TAG
+DEST=$_  # (the folder just made: the bench line is written there too)
 bash profiles/run_all.sh $TAG > gpurun_out/$TAG/run_all.log 2>&1
 for s in c3 c4 c5 hexagons mesh dragons reflect_refract first_textures; do python profiles/summarize.py ${TAG}_$s > gpurun_out/$TAG/summary_$s.json 2> gpurun_out/$TAG/summary_$s.err || echo "summarize $s failed"; done
 cp profiles/${TAG}_* gpurun_out/$TAG/   # (summarize.py writes beside itself; only gpurun_out/ travels back)
@@ -21,7 +22,7 @@ for s in "reflect_refract 4096 2048" "first_textures 4096 2048" "mesh 2048 2048"
 echo timelines done
 python tools/time_configs.py 2>&1 | grep -v amdgpu > gpurun_out/$TAG/time_configs.txt
 echo table done
-python bench.py > gpurun_out/$TAG/bench_line.json 2> gpurun_out/$TAG/bench.err
-tail -c 300 gpurun_out/$TAG/bench_line.json
+python bench.py --full > "$DEST/bench_line.json" 2> "$DEST/bench.err"
+tail -c 300 "$DEST/bench_line.json"
 python tools/verify_configs.py 2>&1 | grep -v amdgpu > gpurun_out/$TAG/verify_configs.txt
 tail -3 gpurun_out/$TAG/verify_configs.txt
