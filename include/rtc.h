@@ -389,6 +389,48 @@ rtc_status rtc_ctx_to_ppm(rtc_ctx* ctx, const void* d_rgb, uint32_t width, uint3
  * n*4 f32, out n*3 f32. */
 rtc_status rtc_color_at(const rtc_scene* scene, const float* origins, const float* directions, uint32_t n,
                         int32_t depth, int32_t device, float* out_rgb);
+/* ------------------------------------------------------------------------
+ * First-hit buffers: what the path knows about a ray's first hit before it becomes a colour.
+ * "First hit" is, in this order: xs = World::intersect(ray) (world.rs:52-60); hit = Intersection::hit(xs)
+ * (intersection.rs:30-35: the first minimum among distance >= 0, -0.0 counts, ties by list order);
+ * comps = precompute_values(ray, hit, xs) (world.rs:212-283) for EVERY hit, opaque or not; and
+ * light = world.light.intensity_at(comps.over_point, world), the number shade_hit hands to phong_lighting for that hit
+ * (world.rs:75), drawn with the jitter key (pixel index, path 1) -- the key a render gives a pixel's primary hit.
+ *
+ * One plane per field of PrecomputedValues (world.rs:165-182) plus the light fraction; NULL = not wanted.  A miss stores
+ * object = -1 and zeros in every other requested plane; every requested plane is written in full; a plane that is not
+ * requested is not touched.  Vector planes are 4 f32 per element with w as the reference's Tuple has it (1 for points, 0 for
+ * vectors).  `light` with an RTC_JITTER_SEQUENCE light is refused (the cycle is state, see the enum); without the light
+ * plane such a scene is accepted -- no draw is made.
+ * ---------------------------------------------------------------------- */
+typedef struct rtc_hit_planes {
+    int32_t* object;      /* index into rtc_scene.objects; -1: no hit                       */
+    float*   distance;    /* Intersection.distance                                           */
+    float*   point;       /* 4 f32 each                                                      */
+    float*   eye;
+    float*   normal;      /* after the inside flip (world.rs:223-226)                        */
+    float*   reflectv;    /* from the normal BEFORE the flip (world.rs:220)                  */
+    float*   over_point;
+    float*   under_point;
+    int32_t* inside;      /* 0 / 1                                                           */
+    float*   n1n2;        /* 2 f32: n1, n2 (world.rs:234-263)                                */
+    float*   light;       /* intensity_at(over_point), 0..1                                  */
+} rtc_hit_planes;
+
+/* Batched first hits for caller-supplied rays, like rtc_color_at: host buffers, origins / directions n*4 f32 (origin.w
+ * 1, direction.w 0), every plane of `out` n elements; ray i uses pixel index i as its jitter key.  No plane requested, or
+ * a null ray pointer with n > 0: RTC_ERR_INVALID_ARG (decided before any device call). */
+rtc_status rtc_hit_at(const rtc_scene* scene, const float* origins, const float* directions, uint32_t n,
+                      int32_t device, const rtc_hit_planes* out);
+/* The first hits of the camera's pixels from a persistent context: the planes are DEVICE pointers, the launch is
+ * asynchronous on `stream`, the partition rules and the compact row layout are rtc_ctx_render's -- plane element (yl, x)
+ * at index yl*width + x, rtc_partition_rows() rows.  The last row and the last column of a frame (never traced,
+ * camera.rs:80-81) are stored as misses.  Rendered by ahead-of-time kernels of the families rtc_ctx_render's ahead-of-time
+ * branch chooses from.  Leaves rtc_ctx_stats, the frame schedule's measurements and the scene's compiled render kernel
+ * alone: a render after it is scheduled and reported exactly as if this call had not happened.
+ * A null context, no plane requested: RTC_ERR_INVALID_ARG (decided before any device call). */
+rtc_status rtc_ctx_render_hits(rtc_ctx* ctx, const rtc_partition* part, const rtc_hit_planes* d_out, void* stream);
+
 /* Batched Light::intensity_at (light.rs:10) for n world points (n*4 f32). */
 rtc_status rtc_intensity_at(const rtc_scene* scene, const float* points, uint32_t n, int32_t device,
                             float* out);

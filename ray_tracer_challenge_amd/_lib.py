@@ -91,6 +91,18 @@ class rtc_opts(C.Structure):
                 ("quantize", C.c_int32), ("out_on_device", C.c_int32)]
 
 
+class rtc_hit_planes(C.Structure):
+    """One plane per field of PrecomputedValues plus the light fraction (rtc.h); a null pointer: not wanted."""
+    _fields_ = [("object", C.c_void_p), ("distance", C.c_void_p), ("point", C.c_void_p), ("eye", C.c_void_p),
+                ("normal", C.c_void_p), ("reflectv", C.c_void_p), ("over_point", C.c_void_p), ("under_point", C.c_void_p),
+                ("inside", C.c_void_p), ("n1n2", C.c_void_p), ("light", C.c_void_p)]
+
+
+# plane -> (is int32, values per element), in the struct's order
+HIT_PLANES = {"object": (True, 1), "distance": (False, 1), "point": (False, 4), "eye": (False, 4), "normal": (False, 4),
+              "reflectv": (False, 4), "over_point": (False, 4), "under_point": (False, 4), "inside": (True, 1),
+              "n1n2": (False, 2), "light": (False, 1)}
+
 # name -> (restype, argtypes); every symbol declared in include/rtc.h
 SIGNATURES = {
     "rtc_translation": (None, [C.c_float] * 3 + [FP]),
@@ -154,6 +166,8 @@ SIGNATURES = {
     "rtc_ctx_to_ppm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                  C.POINTER(C.c_uint64), C.c_void_p]),
     "rtc_color_at": (C.c_int, [C.POINTER(rtc_scene), FP, FP, C.c_uint32, C.c_int32, C.c_int32, FP]),
+    "rtc_hit_at": (C.c_int, [C.POINTER(rtc_scene), FP, FP, C.c_uint32, C.c_int32, C.POINTER(rtc_hit_planes)]),
+    "rtc_ctx_render_hits": (C.c_int, [C.c_void_p, C.POINTER(rtc_partition), C.POINTER(rtc_hit_planes), C.c_void_p]),
     "rtc_intensity_at": (C.c_int, [C.POINTER(rtc_scene), FP, C.c_uint32, C.c_int32, FP]),
     "rtc_is_shadowed": (C.c_int, [C.POINTER(rtc_scene), FP, FP, C.c_uint32, C.c_int32, C.POINTER(C.c_int32)]),
     "rtc_point_on_light": (C.c_int, [C.POINTER(rtc_light), C.POINTER(C.c_int32), C.c_uint32, C.c_int32, FP]),

@@ -796,6 +796,18 @@ class _CScene:
         self.scene.groups = C.cast(self.groups, C.POINTER(L.rtc_group))
 
 
+class HitRecord:
+    """What World.hit_at returns: one numpy array per plane of rtc_hit_planes, None for a plane that was not asked for."""
+    __slots__ = tuple(L.HIT_PLANES)
+
+    def __init__(self, **arrays):
+        for k in self.__slots__:
+            setattr(self, k, arrays.get(k))
+
+    def planes(self):
+        return {k: getattr(self, k) for k in self.__slots__ if getattr(self, k) is not None}
+
+
 class World:
     """World { objects, light } -- world.rs:18-21"""
 
@@ -819,6 +831,26 @@ class World:
         cs = self._c()
         L.check(L.lib().rtc_color_at(C.byref(cs.scene), _p(o), _p(d), o.shape[0], int(depth), device, _p(out)))
         return out
+
+    def hit_at(self, origins, directions, light=True, device=0, planes=None):
+        """The first hit of each ray of a batch (rtc_hit_at): World::intersect, Intersection::hit, precompute_values and --
+        with `light` -- intensity_at(over_point), ray i drawing with pixel index i.  (n,4),(n,4) -> a HitRecord of numpy
+        arrays named as rtc_hit_planes' fields (a miss: object -1, zeros elsewhere).  `planes`: only these (default: all;
+        `light` is left out where light=False)."""
+        o = np.ascontiguousarray(np.asarray(origins, dtype=f32).reshape(-1, 4))
+        d = np.ascontiguousarray(np.asarray(directions, dtype=f32).reshape(-1, 4))
+        names = list(L.HIT_PLANES) if planes is None else list(planes)
+        if not light:
+            names = [k for k in names if k != "light"]
+        n = o.shape[0]
+        arrays, hp = {}, L.rtc_hit_planes()
+        for k in names:
+            is_int, per = L.HIT_PLANES[k]  # (KeyError: not a plane)
+            arrays[k] = np.zeros((n, per) if per > 1 else n, dtype=np.int32 if is_int else f32)
+            setattr(hp, k, arrays[k].ctypes.data)
+        cs = self._c()
+        L.check(L.lib().rtc_hit_at(C.byref(cs.scene), _p(o), _p(d), n, device, C.byref(hp)))
+        return HitRecord(**arrays)
 
     def intensity_at(self, points, device=0):
         """Light::intensity_at for a batch of points (light/light.rs:10)."""

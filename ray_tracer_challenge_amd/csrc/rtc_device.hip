@@ -32,6 +32,7 @@
 
 #include "rtc_internal.h"
 #include "rtc_kernel_core.h"
+#include "rtc_hits.h"
 #include "rtc_wavefront.h"
 
 namespace rtc {
@@ -283,6 +284,7 @@ struct Policy {
     int tree_waves = 0, reg_levels = 0, blocks_y = 0, block_s = -1, block_s_top = -1;  // (0 / -1: the library's own choice)
     uint32_t fill_wgs = 0u, tile_fill_wgs = 0u, cluster_min_run = 0u, cluster_leaf = 0u, area_share_waves = 0u, feedback_pct = 85u, feedback_down_pct = 40u, feedback_passes = 2u, feedback_max_s = 4u;
     double cluster_gmax = -1.0;
+    int hits_tile = 0;  // RTC_AMD_HITS_TILE = 3 / 5 / 6: a wave's tile in rtc_ctx_render_hits is 8 x 8 / 32 x 2 / 64 x 1 pixels (0: the library's own choice)
 
     static Policy from_env() {
         Policy p;
@@ -330,6 +332,7 @@ struct Policy {
         if (const char* e = RTC_DEV_ENV("RTC_AMD_CLUSTER_MIN_RUN")) p.cluster_min_run = std::max(3u, (uint32_t)std::atoi(e));
         if (const char* e = RTC_DEV_ENV("RTC_AMD_CLUSTER_LEAF")) p.cluster_leaf = std::min(64u, std::max(2u, (uint32_t)std::atoi(e)));
         if (const char* e = RTC_DEV_ENV("RTC_AMD_CLUSTER_GMAX")) p.cluster_gmax = std::atof(e);
+        p.hits_tile = digit(RTC_DEV_ENV("RTC_AMD_HITS_TILE"), 3, 6, 0);
         return p;
     }
     // The share of the frame below which a scene's rectangle is launched instead of the whole grid (rtc_ctx_render).
@@ -1684,6 +1687,14 @@ std::string aot_kernel_id() {
 }
 
 }  // namespace
+
+// rtc_hit_planes as the kernels take it; false: no plane requested
+static bool hit_planes_view(const rtc_hit_planes* p, HitPlanes* v) {
+    v->object = p->object, v->distance = p->distance, v->inside = p->inside, v->light = p->light;
+    v->point = (float4*)p->point, v->eye = (float4*)p->eye, v->normal = (float4*)p->normal, v->reflectv = (float4*)p->reflectv;
+    v->over_point = (float4*)p->over_point, v->under_point = (float4*)p->under_point, v->n1n2 = (float2*)p->n1n2;
+    return p->object || p->distance || p->point || p->eye || p->normal || p->reflectv || p->over_point || p->under_point || p->inside || p->n1n2 || p->light;
+}
 
 static SceneSoA soa_view(const float4* base, const SceneHdr& hdr, const float* d_texels) {
     uint32_t m = rtc::padded_count(hdr.n_objects);
@@ -3133,6 +3144,57 @@ rtc_status rtc_ctx_render(rtc_ctx* c, int32_t depth, const rtc_partition* part, 
     return rtc::ctx_render_slot(c, depth, part, d_out_rgb, stream, 0u);
 }
 
+// The context's scene and camera, none of its render state: no counters, no events, no block or tile lists, no compiled
+// kernel -- a render after this call finds the context as the render before it left it.
+rtc_status rtc_ctx_render_hits(rtc_ctx* c, const rtc_partition* part, const rtc_hit_planes* d_out, void* stream_) {
+    if (!c || !d_out) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: null argument");
+    HitPlanes planes;
+    if (!hit_planes_view(d_out, &planes)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: no plane requested");
+    if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: no scene/camera set");
+    const Partition q = resolve(part);
+    if (q.part >= q.n_parts) return fail(RTC_ERR_INVALID_ARG, "partition %u of %u", q.part, q.n_parts);
+    // (rtc_ctx_set_scene refuses RTC_JITTER_SEQUENCE lights: no resident scene has one)
+    const uint32_t rows = partition_rows(c->hdr.height, part);
+    if (rows == 0) return RTC_OK;  // a partition that owns no band has nothing to write
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    HitsArgs a;
+    a.hdr = c->hdr;
+    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.planes = planes;
+    a.rows = rows;
+    a.band_rows = q.band_rows, a.n_parts = q.n_parts, a.part = q.part;
+    const bool light = planes.light != nullptr;
+    // A wave's tile (HitsArgs::tile_w_log2), geometry only (profiles/hits_times.txt, planes = object, distance, normal; 8 x 8 / 32 x 2 /
+    // 64 x 1): C3 4096^2 233 / 232 / 232 us -- neither the walk nor the stores: a quarter of a million waves of a few hundred
+    // instructions each; mesh 2048^2 167 / 197 / 266 us -- the walk, which wants a wave's rays close together; C5 8192^2 516 / 450 /
+    // 450 us -- 95 % of its pixels miss the scene's box and store zeros, 24 B each: there the stores bind, and a wave that writes
+    // 128 contiguous bytes of a dword plane per row beats one that writes eight pieces of 32.  So: the compact tile, but the
+    // 32 x 2 one where most of the frame is sky (the share below which the render puts several blocks into a workgroup).
+    // With the light plane always the compact tile: intensity_at's wave votes (block cones, culls) decide more when a wave's
+    // pixels are close together.  RTC_AMD_HITS_TILE (development) pins one.
+    a.tile_w_log2 = (!light && c->scene_box_coverage < 0.25f) ? 5u : 3u;
+    if (c->policy.hits_tile == 3 || c->policy.hits_tile == 5 || c->policy.hits_tile == 6) a.tile_w_log2 = (uint32_t)c->policy.hits_tile;
+    const uint32_t bw = a.tile_w_log2 == 3u ? 16u : 1u << a.tile_w_log2, bh = 256u / bw;
+    const dim3 grid((c->hdr.width + bw - 1) / bw, (rows + bh - 1) / bh), block(256);
+    // the families rtc_ctx_render's ahead-of-time branch chooses from, by the same conditions (SIMPLE is a property of
+    // intensity_at alone: the geometry-only kernels exist once per object-loop family)
+#define RTC_LAUNCH_HITS(NOBJ, SIMPLE)                                                                       \
+    do {                                                                                                    \
+        if (light) hipLaunchKernelGGL((hits_kernel<NOBJ, SIMPLE, true>), grid, block, 0, stream, a);         \
+        else hipLaunchKernelGGL((hits_kernel<NOBJ, false, false>), grid, block, 0, stream, a);               \
+    } while (0)
+    if (c->hdr.n_trav) RTC_LAUNCH_HITS(-1, false);
+    else if (c->n_objects <= 4 && c->simple) RTC_LAUNCH_HITS(4, true);
+    else if (c->n_objects <= 4) RTC_LAUNCH_HITS(4, false);
+    else if (c->n_objects <= 8 && c->simple) RTC_LAUNCH_HITS(8, true);
+    else if (c->n_objects <= 8) RTC_LAUNCH_HITS(8, false);
+    else RTC_LAUNCH_HITS(0, false);
+#undef RTC_LAUNCH_HITS
+    HIP_TRY(hipGetLastError());
+    return RTC_OK;
+}
+
 rtc_status rtc_ctx_stats(rtc_ctx* c, rtc_stats* out) {
     if (!c || !out) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_stats: null argument");
     std::memset(out, 0, sizeof(*out));
@@ -3275,6 +3337,52 @@ rtc_status rtc_color_at(const rtc_scene* scene, const float* origins, const floa
                        depth, (float*)d_out.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out_rgb, d_out.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+    return RTC_OK;
+}
+
+rtc_status rtc_hit_at(const rtc_scene* scene, const float* origins, const float* directions, uint32_t n, int32_t device,
+                      const rtc_hit_planes* out) {
+    if (!scene || !out) return fail(RTC_ERR_INVALID_ARG, "rtc_hit_at: null argument");
+    HitPlanes host;
+    if (!hit_planes_view(out, &host)) return fail(RTC_ERR_INVALID_ARG, "rtc_hit_at: no plane requested");
+    if (n > 0 && (!origins || !directions)) return fail(RTC_ERR_INVALID_ARG, "rtc_hit_at: null ray buffer");
+    if (n == 0) return RTC_OK;
+    for (uint32_t i = 0; i < n; i++) {
+        if (origins[i * 4 + 3] != 1.0f || directions[i * 4 + 3] != 0.0f)
+            return fail(RTC_ERR_INVALID_ARG, "ray %u: origin.w must be 1 and direction.w 0", i);
+    }
+    SceneHdr hdr;
+    DevBuf soa, tex, d_o, d_d, d_planes[11];
+    // (a sequence-jitter light is refused by the flattening where the light plane would draw from it)
+    rtc_status st = begin_batch(scene, device, &hdr, &soa, &tex, /*allow_sequence=*/host.light == nullptr);
+    if (st != RTC_OK) return st;
+    HIP_TRY(d_o.alloc((size_t)n * 16));
+    HIP_TRY(d_d.alloc((size_t)n * 16));
+    HIP_TRY(hipMemcpy(d_o.p, origins, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d.p, directions, (size_t)n * 16, hipMemcpyHostToDevice));
+    // the planes in rtc_hit_planes' order: host pointer, bytes per element, where the device view keeps its pointer
+    HitPlanes dev;
+    std::memset(&dev, 0, sizeof(dev));
+    struct PlaneCopy {
+        void* host;
+        size_t bytes;
+        void** dev;
+    } planes[11] = {{host.object, 4, (void**)&dev.object},      {host.distance, 4, (void**)&dev.distance},
+                    {host.point, 16, (void**)&dev.point},       {host.eye, 16, (void**)&dev.eye},
+                    {host.normal, 16, (void**)&dev.normal},     {host.reflectv, 16, (void**)&dev.reflectv},
+                    {host.over_point, 16, (void**)&dev.over_point}, {host.under_point, 16, (void**)&dev.under_point},
+                    {host.inside, 4, (void**)&dev.inside},      {host.n1n2, 8, (void**)&dev.n1n2},
+                    {host.light, 4, (void**)&dev.light}};
+    for (int k = 0; k < 11; k++) {
+        if (!planes[k].host) continue;
+        HIP_TRY(d_planes[k].alloc((size_t)n * planes[k].bytes));
+        *planes[k].dev = d_planes[k].p;
+    }
+    hipLaunchKernelGGL(hit_at_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr, soa_view((const float4*)soa.p, hdr, (const float*)tex.p),
+                       (const float4*)d_o.p, (const float4*)d_d.p, n, dev);
+    HIP_TRY(hipGetLastError());
+    for (int k = 0; k < 11; k++)
+        if (planes[k].host) HIP_TRY(hipMemcpy(planes[k].host, d_planes[k].p, (size_t)n * planes[k].bytes, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 

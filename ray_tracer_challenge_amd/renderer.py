@@ -71,6 +71,33 @@ class Renderer:
                                        C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
         return out
 
+    def render_hits(self, planes=("object", "distance", "normal", "light"), out=None, part=None, stream=None):
+        """The first hit of every pixel's ray (rtc_ctx_render_hits) on `stream` (default: torch's current stream);
+        asynchronous.  -> {plane: tensor}: int32 (rows, w) for object / inside, float32 (rows, w) for distance / light,
+        float32 (rows, w, 4) for the vector planes, (rows, w, 2) for n1n2.  `out`: tensors to write into, by plane."""
+        rows, planes = self.rows(part), tuple(planes)
+        if not planes:
+            raise ValueError("no plane requested")
+        res, hp = {}, L.rtc_hit_planes()
+        for k in planes:
+            if k not in L.HIT_PLANES:
+                raise ValueError("%r is not a plane (%s)" % (k, ", ".join(L.HIT_PLANES)))
+            is_int, per = L.HIT_PLANES[k]
+            dtype = torch.int32 if is_int else torch.float32
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty((rows, self.width, per) if per > 1 else (rows, self.width), dtype=dtype, device=self.device)
+            # (checked, not asserted: the raw pointer goes to a kernel that writes rows x width elements through it, 16 bytes at a time)
+            if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == rows * self.width * per and t.data_ptr() % 16 == 0):
+                raise ValueError("out[%r] must be a contiguous, 16-byte aligned %s CUDA tensor of %d x %d%s"
+                                 % (k, "int32" if is_int else "float32", rows, self.width, " x %d" % per if per > 1 else ""))
+            res[k] = t
+            setattr(hp, k, t.data_ptr())
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        L.check(self._lib.rtc_ctx_render_hits(self._ctx, C.byref(part) if part is not None else None, C.byref(hp),
+                                              C.c_void_p(s.cuda_stream)), self._lib)
+        return res
+
     @property
     def kernel_name(self):
         return self._lib.rtc_ctx_kernel_name(self._ctx).decode()
