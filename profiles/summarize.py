@@ -38,7 +38,7 @@ for r in csv.DictReader(open(stats)):
     if "render_kernel" in r["Name"]:
         out["kernel_trace"] = {"calls": int(r["Calls"]), "avg_ns": float(r["AverageNs"]), "min_ns": float(r["MinNs"]),
                                "max_ns": float(r["MaxNs"])}
-# The one-workgroup warm-up launch (rtc_device.hip ctx_render_slot: a kernel's first launch on a queue, a few microseconds over zero
+# The one-workgroup warm-up launch (rtc_device.hip warm_up: a kernel's first launch on a queue, a few microseconds over zero
 # rows) is a render_kernel dispatch too: the per-dispatch trace says which rows are frames.
 traces = glob.glob(os.path.join(src, "trace", "*", "*_kernel_trace.csv"))
 if traces:

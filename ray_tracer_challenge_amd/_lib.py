@@ -199,7 +199,13 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
          # the block-list feedback's two host functions as rtc_ctx_render uses them (tests/test_block_lists.py)
          "rtc_diag_refine_block_list": (C.c_uint32, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
                                                      C.c_double, C.c_double, C.POINTER(C.c_uint32), C.c_uint32]),
-         "rtc_diag_simulate_dispatch": (C.c_double, [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32])}
+         "rtc_diag_simulate_dispatch": (C.c_double, [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]),
+         # rtc_launch_plan.h's arithmetic: the band walk, the scene-tile list, the scene-rectangle launch (tests/test_launch_plan.py)
+         "rtc_diag_band_walk": (C.c_uint32, [C.c_uint32, C.c_uint32, C.POINTER(rtc_partition), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64)]),
+         "rtc_diag_scene_tiles": (C.c_uint64, [C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(rtc_partition),
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
+         "rtc_diag_rect_launch": (C.c_uint64, [C.c_uint32, C.c_uint32, C.POINTER(rtc_partition), C.POINTER(C.c_uint32), C.c_uint32, C.c_int32,
+                                               C.c_uint32, C.POINTER(C.c_uint32)])}
 
 _lib = None
 _loaded = {}  # path -> CDLL

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "rtc_internal.h"
+#include "rtc_launch_plan.h"
 #include "rtc_kernel_core.h"
 #include "rtc_hits.h"
 #include "rtc_wavefront.h"
@@ -70,6 +71,11 @@ static const uint32_t h_inv_pio4[24] = RTC_INV_PIO4_INIT;
         if (e_ != hipSuccess)                                                                        \
             return fail(RTC_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+#define RTC_TRY(expr)                \
+    do {                             \
+        rtc_status s_ = (expr);      \
+        if (s_ != RTC_OK) return s_; \
+    } while (0)
 
 static int usable_devices() {
     int n = 0;
@@ -93,13 +99,22 @@ static rtc_status check_tuple(const float v[4], float w, const char* what) {
 }
 
 // The four geometry records of one object (see SceneSoA).
-static void pack_geometry(const rtc_object& o, float4 g[4]) {
+static uint32_t shape_bits(const rtc_object& o) {  // an object's kind / flags word (geo[i].w)
     uint32_t bits = (uint32_t)o.kind | (o.casts_shadow ? SHAPE_CASTS : 0u) | (o.closed ? SHAPE_CLOSED : 0u);
     if (o.inv[1] == 0.0f && o.inv[2] == 0.0f && o.inv[4] == 0.0f && o.inv[6] == 0.0f && o.inv[8] == 0.0f &&
         o.inv[9] == 0.0f) {
         bits |= SHAPE_DIAG;
         if (o.inv[0] == o.inv[5] && o.inv[5] == o.inv[10]) bits |= SHAPE_UNIFORM;  // a uniform scale (shadow_fast)
     }
+    return bits;
+}
+// what the SIMPLE kernels take: scale+translate-only, no cylinder / cone / triangle
+static bool simple_shape(uint32_t bits) {
+    const uint32_t kind = bits & SHAPE_KIND_MASK;
+    return (bits & SHAPE_DIAG) && kind != RTC_CYLINDER && kind != RTC_CONE && kind != RTC_TRIANGLE;
+}
+static void pack_geometry(const rtc_object& o, float4 g[4]) {
+    const uint32_t bits = shape_bits(o);
     float bits_f;
     std::memcpy(&bits_f, &bits, 4);
     g[0] = make_float4(o.inv[0], o.inv[5], o.inv[10], bits_f);
@@ -1299,16 +1314,12 @@ static rtc_status flatten(const Policy& P, const rtc_scene* scene, const rtc_cam
 
 using namespace rtc;
 
-struct rtc_ctx_tiles {
-    const uint8_t* bits;
-    uint32_t w, h;
-};
 struct BlockList {  // RenderArgs::tiles of one partition (build_block_list), resident on the device
     uint32_t* d = nullptr;
     size_t n = 0, n_listed = 0;  // (n_listed: a grid's list leaves the padding out)
     // feedback (refine_block_list): the list as built, where its first launch leaves its waves' running times, and how far it is
     std::vector<uint32_t> host;
-    size_t d_cap = 0, ticks_cap = 0;  // bytes behind d / d_ticks: grown, never shrunk (hipMalloc / hipFree cost the animation's frames milliseconds)
+    size_t d_cap = 0, ticks_cap = 0;  // dwords behind d / d_ticks: grown, never shrunk (hipMalloc / hipFree cost the animation's frames milliseconds)
     uint32_t* d_ticks = nullptr;  // [4 n] wave times -- or, for kernels that do not time their waves, [4 n] uint4 work counts (a copy of block_counts)
     bool counts = false, swizzled = false, listed = false;  // (listed: a grid whose frames run from `d`, its blocks in order)
     // IDLE (regular grids): a scene's first frame -- nothing is measured before a second frame of the SAME scene shows that frames repeat
@@ -1717,6 +1728,49 @@ static SceneSoA soa_view(const float4* base, const SceneHdr& hdr, const float* d
     return s;
 }
 
+// a grow-only device buffer of at least `n` elements, *cap counting elements (nothing may be in flight that reads the old
+// one).  headroom: half as much again, for buffers that grow by steps.  The pointer is null and the capacity zero while
+// the allocation is attempted: a failed hipMalloc cannot leave a stale capacity beside a freed pointer.
+template <class T>
+static hipError_t grow(T** p, size_t* cap, size_t n, bool headroom = false) {
+    if (*p != nullptr && *cap >= n) return hipSuccess;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr, *cap = 0;
+    const size_t want = headroom ? std::max<size_t>(256 / sizeof(T), n + n / 2) : n;
+    hipError_t e = hipMalloc((void**)p, want * sizeof(T));
+    if (e == hipSuccess) *cap = want;
+    return e;
+}
+
+// The ahead-of-time kernels: render_kernel<NOBJ, SIMPLE> / hits_kernel<NOBJ, SIMPLE, LIGHT>.  <= 4 / <= 8 objects get fully unrolled
+// object loops (SIMPLE: all of them scale+translate-only, no cylinder), anything larger takes the generic loop (0), a
+// traversal stream the packet walk (-1).
+struct KernelFamily {
+    int nobj;  // -1, 4, 8, 0
+    bool simple;
+    const void* key() const { return (const void*)(uintptr_t)(0x1000 + 2 * (nobj + 1) + (simple ? 1 : 0)); }  // (no code object's address)
+    std::string name(const char* tree_how = "tree") const {
+        if (nobj < 0) return std::string("render_kernel<") + tree_how + ">";
+        return "render_kernel<" + std::to_string(nobj) + (simple ? ",simple>" : ",general>");
+    }
+};
+static KernelFamily aot_family(const rtc_ctx* c) {
+    if (c->hdr.n_trav) return {-1, false};
+    if (c->n_objects <= 4) return {4, c->simple};
+    if (c->n_objects <= 8) return {8, c->simple};
+    return {0, false};
+}
+// f(NOBJ, SIMPLE) with the family as compile-time constants
+template <class F>
+static void dispatch_family(KernelFamily k, F&& f) {
+    if (k.nobj < 0) f(std::integral_constant<int, -1>(), std::false_type());
+    else if (k.nobj == 4 && k.simple) f(std::integral_constant<int, 4>(), std::true_type());
+    else if (k.nobj == 4) f(std::integral_constant<int, 4>(), std::false_type());
+    else if (k.nobj == 8 && k.simple) f(std::integral_constant<int, 8>(), std::true_type());
+    else if (k.nobj == 8) f(std::integral_constant<int, 8>(), std::false_type());
+    else f(std::integral_constant<int, 0>(), std::false_type());
+}
+
 extern "C" {
 
 int32_t rtc_device_count(void) { return usable_devices(); }
@@ -1866,150 +1920,31 @@ static void mark_plane_side(const std::array<double, 4>& row, const rtc_camera* 
         for (long tx = tx0; tx <= tx1; tx++) (*tiles)[(size_t)ty * tw + tx] = 1;
 }
 
-// RenderArgs::tiles' words: lanes per pixel 2^s (s = 0 .. 4), pixel origin (multiples of 4; local rows below 2^17)
-static inline uint32_t tile_word(uint32_t s, uint32_t x0, uint32_t y0) { return (s & 3u) << 30 | (x0 / 4u) << 16 | (s >> 2) << 15 | (y0 / 4u); }
-static inline uint32_t tile_s(uint32_t t) { return (t >> 30) | ((t >> 13) & 4u); }
-static inline uint32_t tile_x0(uint32_t t) { return ((t >> 16) & 0x3fffu) << 2; }
-static inline uint32_t tile_y0(uint32_t t) { return (t & 0x7fffu) << 2; }
-// The block list of one partition (RenderArgs::tiles): the 16 x 16 tiles of the partition's compact rows, those a mesh
-// projects to first and cut into blocks of 2^mesh_share_log2 lanes per pixel (8 x 8 or 8 x 4 pixels), the others after
-// them, whole, one lane per pixel.
-static void build_block_list(const Policy& P, const rtc_ctx_tiles& T, uint32_t width, uint32_t mesh_share_log2, uint32_t rows, const Partition& q, std::vector<uint32_t>* out) {
-    out->clear();
-    std::vector<uint32_t> light;
-    uint32_t hs = mesh_share_log2;  // lanes per pixel (log2) in the mesh tiles; RTC_AMD_BLOCK_S=0..3: development
-    // the dearest tiles first (rank 3: glass that also reflects), or the frame ends waiting for a few waves that started
-    // late (RTC_AMD_BLOCK_ORDER=0: image order; RTC_AMD_BLOCK_S_TOP=0..3: lanes per pixel of rank 3 alone -- development)
-    const bool ordered = P.block_order;
-    uint32_t hs_top = hs;
-    // large frames at two lanes: only the glass keeps them, the other meshes' tiles take one (first frames of here_be_dragons
-    // 4000 x 1600 2.87 -> 2.68 ms, mesh 2048^2 3.47 -> 3.24; at 1024^2 and below the other way round: 2.38 -> 2.70,
-    // profiles/r03_ab_first_frame_lanes.txt)
-    if (hs == 1u && ((uint64_t)width * rows + 63u) / 64u > 60000u) hs = 0u;
-    if (P.block_s >= 0) hs = hs_top = (uint32_t)P.block_s;
-    if (P.block_s_top >= 0) hs_top = (uint32_t)P.block_s_top;
-    for (uint32_t rank = 3u; rank >= 1u; rank--) {
-        const uint32_t s = rank == 3u ? hs_top : hs;
-        const uint32_t hbw = 16u >> (s >> 1), hbh = 16u >> ((s + 1u) >> 1);
-        for (uint32_t yl0 = 0; yl0 < rows; yl0 += 16u) {
-            const uint32_t band = yl0 / q.band_rows;
-            const uint32_t y = (band * q.n_parts + q.part) * q.band_rows + (yl0 - band * q.band_rows);  // global row of the tile's first row
-            for (uint32_t x0 = 0; x0 < width; x0 += 16u) {
-                const uint32_t ty = std::min(y / 16u, T.h - 1u), tx = std::min(x0 / 16u, T.w - 1u);
-                const uint32_t r = T.bits[(size_t)ty * T.w + tx];
-                if (r != 0u && (ordered ? r == rank : rank == 1u)) {
-                    for (uint32_t dy = 0; dy < 16u && yl0 + dy < rows; dy += hbh)
-                        for (uint32_t dx = 0; dx < 16u && x0 + dx < width; dx += hbw)
-                            out->push_back(tile_word(s, x0 + dx, yl0 + dy));
-                } else if (rank == 1u && r == 0u) {
-                    light.push_back(tile_word(0u, x0, yl0));
-                }
-            }
-        }
+// ... and what the pairs in use measured, added up
+static hipError_t sum_event_ms(const rtc_ctx* c, double* sum_ms) {
+    for (size_t i = 0; i < c->events_used; i++) {
+        float ms = 0.0f;
+        const hipError_t e = hipEventElapsedTime(&ms, c->events[i].first, c->events[i].second);
+        if (e != hipSuccess) return e;
+        *sum_ms += ms;
     }
-    out->insert(out->end(), light.begin(), light.end());
+    return hipSuccess;
 }
-
-// Feedback for block lists.  The list a scene starts with knows three kinds of tile (build_block_list) and nothing of what a tile
-// costs; the frame it schedules ends with a tail -- here_be_dragons 4000 x 1600: waves of 2.3 ms that started at 0.8 ms of a 3.1 ms
-// frame; mesh 2048^2: the machine runs out of waves at 2.2 ms, the longest (two lanes per pixel, the centre of the glass mesh)
-// run to 3.4.  The first launch of a list therefore times its waves (RenderArgs::wave_ticks), and the list of every later frame
-// of this scene and partition is made from those times: a 16 x 16 tile whose longest wave ran more than half of the frame's
-// throughput time (the sum of all waves' times over the wave slots of the device) gets more lanes per pixel, each doubling
-// taken to shorten its waves to 0.7 (measured: tools/ab_env.py over RTC_AMD_BLOCK_S), and the tiles start in the order of their predicted
-// longest wave.  Which lanes trace a pixel and when changes nothing about its value (tests/test_gpu_fullsize.py compares first
-// and later frames with the oracle).
-static void refine_block_list(const std::vector<uint32_t>& list, const uint32_t* ticks /* [4 list.size()] */, uint32_t width, uint32_t rows, double wave_slots,
-                              double threshold, double down, std::vector<uint32_t>* out, uint32_t max_s = 4u, double* throughput_ticks = nullptr) {
-    struct Tile {
-        uint32_t x0, y0, s;
-        uint64_t longest = 0;
-        double predicted = 0.0;
-    };
-    const uint32_t tw = (width + 15u) / 16u;
-    std::vector<Tile> tiles;
-    std::vector<int32_t> index((size_t)tw * ((rows + 15u) / 16u), -1);
-    uint64_t total = 0u;  // (an integer: a chain of double additions, four per block, was most of this loop's time)
-    for (size_t b = 0; b < list.size(); b++) {
-        const uint32_t t = list[b], x0 = tile_x0(t), y0 = tile_y0(t);
-        if (x0 >= width || y0 >= rows) continue;  // (a padded grid's blocks outside the image)
-        int32_t& slot = index[(size_t)(y0 / 16u) * tw + x0 / 16u];
-        if (slot < 0) {
-            slot = (int32_t)tiles.size();
-            Tile n;
-            n.x0 = x0 & ~15u, n.y0 = y0 & ~15u, n.s = tile_s(t);
-            tiles.push_back(n);
-        }
-        Tile& tile = tiles[(size_t)slot];
-        const uint32_t* d = ticks + 4u * b;  // (the block's four waves)
-        tile.longest = std::max<uint64_t>(tile.longest, std::max(std::max(d[0], d[1]), std::max(d[2], d[3])));
-        total += (uint64_t)d[0] + d[1] + d[2] + d[3];
-    }
-    const double throughput = (double)total / std::max(1.0, wave_slots);  // ticks the frame takes if the work were spread evenly
-    if (throughput_ticks) *throughput_ticks = throughput;
-    for (Tile& t : tiles) {
-        t.predicted = (double)t.longest;
-        while (t.s < max_s && t.predicted > threshold * throughput) t.s++, t.predicted *= 0.7;  // (up to sixteen lanes per pixel)
-        while (t.s > 0u && t.predicted / 0.7 < down * throughput) t.s--, t.predicted /= 0.7;
-    }
-    // the tiles by predicted longest wave, longest first, equal ones in list order: a radix sort of the (non-negative) doubles' bit
-    // patterns, 16 bits a pass, passes whose digit is the same everywhere skipped -- a comparison sort of 16 384 tiles cost the host
-    // 2 ms in front of the frame that waits for the list, this a tenth of that
-    std::vector<uint32_t> order(tiles.size()), other(tiles.size());
-    {
-        std::vector<uint64_t> key(tiles.size());
-        uint64_t all_or = 0u, all_and = ~(uint64_t)0u;
-        for (uint32_t i = 0; i < order.size(); i++) {
-            const double pr = tiles[i].predicted > 0.0 ? tiles[i].predicted : 0.0;
-            uint64_t k;
-            std::memcpy(&k, &pr, sizeof(k));
-            key[i] = ~k;  // (ascending in ~k = descending in the prediction)
-            all_or |= key[i], all_and &= key[i];
-            order[i] = i;
-        }
-        std::vector<uint32_t> count(65537u);
-        for (uint32_t shift = 0u; shift < 64u; shift += 16u) {
-            if ((((all_or ^ all_and) >> shift) & 0xffffu) == 0u) continue;
-            std::fill(count.begin(), count.end(), 0u);
-            for (uint32_t i : order) count[((key[i] >> shift) & 0xffffu) + 1u]++;
-            for (uint32_t d = 0u; d < 65536u; d++) count[d + 1u] += count[d];
-            for (uint32_t i : order) other[count[(key[i] >> shift) & 0xffffu]++] = i;
-            order.swap(other);
+// the next HIP-event pair of the launches since the last rtc_ctx_stats
+static hipError_t next_event_pair(rtc_ctx* c, std::pair<hipEvent_t, hipEvent_t>** out) {
+    if (c->events_used == c->events.size()) {
+        if (c->events.size() >= 4096) {
+            c->events_used = 0;  // nobody is reading the timings: recycle
+        } else {
+            std::pair<hipEvent_t, hipEvent_t> e;
+            hipError_t err = hipEventCreate(&e.first);
+            if (err == hipSuccess) err = hipEventCreate(&e.second);
+            if (err != hipSuccess) return err;
+            c->events.push_back(e);
         }
     }
-    out->clear();
-    for (uint32_t i : order) {
-        const Tile& t = tiles[i];
-        const uint32_t hbw = 16u >> (t.s >> 1), hbh = 16u >> ((t.s + 1u) >> 1);
-        for (uint32_t dy = 0; dy < 16u && t.y0 + dy < rows; dy += hbh)
-            for (uint32_t dx = 0; dx < 16u && t.x0 + dx < width; dx += hbw) out->push_back(tile_word(t.s, t.x0 + dx, t.y0 + dy));
-    }
-}
-
-// How long a frame takes whose blocks start in the given order: every block goes to the workgroup slot that is free first and
-// keeps it for as long as its longest wave ran (what the dispatcher does, with costs in whatever unit `cost` is in).
-static double simulate_dispatch(const std::vector<uint32_t>& cost, size_t slots) {
-    std::priority_queue<double, std::vector<double>, std::greater<double>> free_at;
-    for (size_t i = 0; i < std::max<size_t>(1, slots); i++) free_at.push(0.0);
-    double end = 0.0;
-    for (uint32_t c : cost) {
-        const double t = free_at.top() + (double)c;
-        free_at.pop();
-        free_at.push(t);
-        end = std::max(end, t);
-    }
-    return end;
-}
-
-// a device buffer of at least `bytes` (nothing may be in flight that reads the old one)
-static hipError_t grow(uint32_t** p, size_t* cap, size_t bytes) {
-    if (*p != nullptr && *cap >= bytes) return hipSuccess;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr, *cap = 0;
-    const size_t want = std::max<size_t>(256, bytes + bytes / 2);
-    hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
+    *out = &c->events[c->events_used++];
+    return hipSuccess;
 }
 static hipError_t feedback_staging(rtc_ctx* c, size_t bytes, void** p) {  // (the caller has synchronised the device: nothing is using the old one)
     if (c->h_feedback == nullptr || c->h_feedback_cap < bytes) {
@@ -2054,7 +1989,7 @@ static rtc_status recut_block_list(rtc_ctx* c, BlockList& bl, uint32_t rows) {
                      by_s[0][3] * 32 / 1000, by_s[0][4] * 16 / 1000, by_s[1][0] * 256 / 1000, by_s[1][1] * 128 / 1000, by_s[1][2] * 64 / 1000, by_s[1][3] * 32 / 1000,
                      by_s[1][4] * 16 / 1000);
     }
-    HIP_TRY(grow(&bl.d, &bl.d_cap, refined.size() * sizeof(uint32_t)));  // (nothing is in flight: the synchronisation above)
+    HIP_TRY(grow(&bl.d, &bl.d_cap, refined.size(), true));  // (nothing is in flight: the synchronisation above)
     HIP_TRY(feedback_staging(c, refined.size() * sizeof(uint32_t), &staging));  // (the times have been used)
     std::memcpy(staging, refined.data(), refined.size() * sizeof(uint32_t));
     HIP_TRY(hipMemcpy(bl.d, staging, refined.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -2122,12 +2057,24 @@ static rtc_status order_grid(rtc_ctx* c, BlockList& bl, uint32_t gx, uint32_t gy
     }
     refine_block_list(launched, ticks, c->hdr.width, rows, wave_slots, INFINITY, 0.0, &ordered);
     if (ordered.empty() || ordered.size() > bl.n) return RTC_OK;
-    HIP_TRY(grow(&bl.d, &bl.d_cap, ordered.size() * sizeof(uint32_t)));  // (nothing is in flight: the synchronisation above)
+    HIP_TRY(grow(&bl.d, &bl.d_cap, ordered.size(), true));  // (nothing is in flight: the synchronisation above)
     std::memcpy(staging, ordered.data(), ordered.size() * sizeof(uint32_t));  // (the times have been used; ordered.size() <= nt)
     HIP_TRY(hipMemcpy(bl.d, staging, ordered.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     bl.n_listed = ordered.size();
     bl.listed = true;
     return RTC_OK;
+}
+
+// One launch of the scene's render kernel: the scene-compiled one, or the context's ahead-of-time family.
+static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hipStream_t stream, RenderArgs& a) {
+    if (spec_fn) {
+        void* params[] = {&a};
+        return hipModuleLaunchKernel(spec_fn, grid.x, grid.y, 1, 256, 1, 1, 0, stream, params, nullptr);
+    }
+    dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+        hipLaunchKernelGGL((render_kernel<decltype(nobj)::value, decltype(simple)::value>), grid, dim3(256), 0, stream, a);
+    });
+    return hipGetLastError();
 }
 
 // The policy wanted a scene-compiled kernel and hiprtc did not deliver one.  RTC_AMD_SPECIALIZE=1: an error.  Default
@@ -2203,21 +2150,11 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camer
     if (!same_records) {
         c->soa_host.clear();
         c->texels_host.clear();
-        if (texels.size() > c->texel_cap) {
-            if (c->d_texels) (void)hipFree(c->d_texels);
-            c->d_texels = nullptr;
-            c->texel_cap = 0;
-            HIP_TRY(hipMalloc(&c->d_texels, texels.size() * sizeof(float)));
-            c->texel_cap = texels.size();
+        if (!texels.empty()) {
+            HIP_TRY(grow(&c->d_texels, &c->texel_cap, texels.size()));
+            HIP_TRY(hipMemcpy(c->d_texels, texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
         }
-        if (!texels.empty()) HIP_TRY(hipMemcpy(c->d_texels, texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
-        if (soa.size() > c->soa_cap) {
-            if (c->d_soa) (void)hipFree(c->d_soa);
-            c->d_soa = nullptr;
-            c->soa_cap = 0;
-            HIP_TRY(hipMalloc(&c->d_soa, soa.size() * sizeof(float4)));
-            c->soa_cap = soa.size();
-        }
+        if (!soa.empty()) HIP_TRY(grow(&c->d_soa, &c->soa_cap, soa.size()));
         HIP_TRY(hipMemcpy(c->d_soa, soa.data(), soa.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
     c->hdr = hdr;
@@ -2226,8 +2163,7 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camer
     for (uint32_t i = 0; i < hdr.n_objects; i++) {
         uint32_t bits;
         std::memcpy(&bits, &soa[i].w, 4);  // geo[i].w
-        const uint32_t kind = bits & SHAPE_KIND_MASK;
-        if (!(bits & SHAPE_DIAG) || kind == RTC_CYLINDER || kind == RTC_CONE || kind == RTC_TRIANGLE) c->simple = false;
+        if (!simple_shape(bits)) c->simple = false;
     }
     c->has_scene = true;
     if (!same_records) {
@@ -2343,9 +2279,7 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camer
     // register levels need the registers: 13 dwords per level on top of the ~70 the kernel works in
     const char* reg_waves = reg_levels == 0 ? nullptr : reg_levels <= 3 ? "-DRTC_WAVES_PER_SIMD=4" : "-DRTC_WAVES_PER_SIMD=3";
     const uint32_t n = hdr.n_objects;
-    char nm[96];
-    snprintf(nm, sizeof(nm), "render_kernel<%d,%s>", n <= 4 ? 4 : n <= 8 ? 8 : 0, (n <= 8 && c->simple) ? "simple" : "general");
-    c->kernel_name = nm;
+    c->kernel_name = aot_family(c).name();
     c->kernel_id = aot_kernel_id();
     // The options of this scene's kernel are written down whatever the policy says (deep_kernel may need them later);
     // `compile_now`: does the policy want the scene-compiled kernel for ordinary depths.
@@ -2368,7 +2302,7 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camer
     };
     if (hdr.n_trav) {  // a traversal stream (GroupShapes, or the library's own hierarchy): packet walk, compiled per scene like the flat kernels
         const std::string how = scene->n_groups ? "tree" : "tree,bvh";
-        c->kernel_name = "render_kernel<" + how + ">";
+        c->kernel_name = aot_family(c).name(how.c_str());
         // (worlds with divided meshes are compiled whatever the frame's size: the ahead-of-time walk has neither the
         // triangle pre-culling specialisation nor the leaf-sharing lanes -- mesh 512 x 384: 7.9 ms)
         compile_now = policy == 1 || (policy == 2 && (pixels >= (1ull << 18) || hdr.max_leaf_run >= 16u));
@@ -2537,25 +2471,23 @@ static rtc_status render_wavefront(rtc_ctx* c, int32_t depth, const Partition& q
     if (cap_nodes > 0x7fffffffull) return RTC_OK;
     if (cap_rays > c->wf_cap_rays || cap_nodes > c->wf_cap_nodes || !c->d_wf_ctr) {
         HIP_TRY(hipDeviceSynchronize());  // (the pools may be in use by a frame in flight)
-        for (WfRay*& r : c->d_wf_rays) {
-            if (r) (void)hipFree(r);
-            r = nullptr;
-        }
-        if (c->d_wf_nodes) (void)hipFree(c->d_wf_nodes);
-        c->d_wf_nodes = nullptr;
-        c->wf_cap_rays = c->wf_cap_nodes = 0;
-        bool ok = true;
-        for (WfRay*& r : c->d_wf_rays) ok = ok && hipMalloc((void**)&r, cap_rays * sizeof(WfRay)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&c->d_wf_nodes, cap_nodes * sizeof(WfNode)) == hipSuccess;
-        if (ok && !c->d_wf_ctr) ok = hipMalloc((void**)&c->d_wf_ctr, WF_CTR_WORDS * sizeof(uint32_t)) == hipSuccess;
-        if (!ok) {  // not enough memory for the pools: the per-pixel kernel needs none
-            (void)hipGetLastError();
+        auto free_pools = [c]() {
             for (WfRay*& r : c->d_wf_rays) {
                 if (r) (void)hipFree(r);
                 r = nullptr;
             }
             if (c->d_wf_nodes) (void)hipFree(c->d_wf_nodes);
             c->d_wf_nodes = nullptr;
+            c->wf_cap_rays = c->wf_cap_nodes = 0;
+        };
+        free_pools();
+        bool ok = true;
+        for (WfRay*& r : c->d_wf_rays) ok = ok && hipMalloc((void**)&r, cap_rays * sizeof(WfRay)) == hipSuccess;
+        ok = ok && hipMalloc((void**)&c->d_wf_nodes, cap_nodes * sizeof(WfNode)) == hipSuccess;
+        if (ok && !c->d_wf_ctr) ok = hipMalloc((void**)&c->d_wf_ctr, WF_CTR_WORDS * sizeof(uint32_t)) == hipSuccess;
+        if (!ok) {  // not enough memory for the pools: the per-pixel kernel needs none
+            (void)hipGetLastError();
+            free_pools();
             return RTC_OK;
         }
         c->wf_cap_rays = cap_rays, c->wf_cap_nodes = cap_nodes;
@@ -2576,28 +2508,15 @@ static rtc_status render_wavefront(rtc_ctx* c, int32_t depth, const Partition& q
     const size_t n_counts = ((size_t)primary_grid.x * primary_grid.y + (size_t)depth * ray_wgs) * 4;  // one partial per wave of every tracing launch
     if (n_counts > c->block_cap) {
         HIP_TRY(hipDeviceSynchronize());
-        if (c->d_block_counts) HIP_TRY(hipFree(c->d_block_counts));
-        c->d_block_counts = nullptr;
-        c->block_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_block_counts, n_counts * sizeof(uint4)));
-        c->block_cap = n_counts;
+        HIP_TRY(grow(&c->d_block_counts, &c->block_cap, n_counts));
     }
     a.wave_counts = c->d_block_counts;
     unsigned long long* total = c->d_total + 3 * (size_t)slot;
     HIP_TRY(hipMemsetAsync(c->d_wf_ctr, 0, WF_CTR_WORDS * sizeof(uint32_t), stream));
     HIP_TRY(hipMemsetAsync(total, 0, 3 * sizeof(unsigned long long), stream));
-    if (c->events_used == c->events.size()) {
-        if (c->events.size() >= 4096) {
-            c->events_used = 0;
-        } else {
-            std::pair<hipEvent_t, hipEvent_t> e;
-            HIP_TRY(hipEventCreate(&e.first));
-            HIP_TRY(hipEventCreate(&e.second));
-            c->events.push_back(e);
-        }
-    }
-    auto& ev = c->events[c->events_used++];
-    HIP_TRY(hipEventRecord(ev.first, stream));
+    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    HIP_TRY(next_event_pair(c, &ev));
+    HIP_TRY(hipEventRecord(ev->first, stream));
     for (int32_t level = 0; level <= depth; level++) {
         a.level = (uint32_t)level;
         a.in_refl = c->d_wf_rays[2 * ((level + 1) & 1)], a.in_refr = c->d_wf_rays[2 * ((level + 1) & 1) + 1];
@@ -2613,7 +2532,7 @@ static rtc_status render_wavefront(rtc_ctx* c, int32_t depth, const Partition& q
         a.level = (uint32_t)level;
         hipLaunchKernelGGL(wf_combine_kernel, dim3(node_wgs), dim3(256), 0, stream, a);
     }
-    HIP_TRY(hipEventRecord(ev.second, stream));
+    HIP_TRY(hipEventRecord(ev->second, stream));
     hipLaunchKernelGGL(sum_counts_kernel, dim3((uint32_t)((n_counts + SUM_COUNTS_SLICE - 1) / SUM_COUNTS_SLICE)), dim3(1024), 0, stream, c->d_block_counts,
                        (uint32_t)n_counts, total, 0ull);
     HIP_TRY(hipGetLastError());
@@ -2632,464 +2551,341 @@ static rtc_status render_wavefront(rtc_ctx* c, int32_t depth, const Partition& q
     return RTC_OK;
 }
 
-// rtc_ctx_render with a counter slot of the caller's choosing (rtc_internal.h)
-rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* part, void* d_out_rgb, void* stream_, uint32_t slot,
-                                ProgressPlan* plan, bool out_u8) {
-    if (plan) plan->n_chunks = 0u, plan->chunk_rows = 0u;
-    if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: null argument");
-    if (slot >= CTX_TOTAL_SLOTS) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: counter slot %u", slot);
-    if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: no scene/camera set");
-    // a partition that owns no band (height < band_rows * n_parts) has nothing to write and may pass a null buffer
-    if (!d_out_rgb && partition_rows(c->hdr.height, part) != 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: null output buffer");
-    if (depth < 0 || depth > RTC_MAX_DEPTH)
-        return fail(RTC_ERR_INVALID_ARG, "depth %d outside [0, %d]", depth, RTC_MAX_DEPTH);
-    Partition q = resolve(part);
-    if (q.part >= q.n_parts) return fail(RTC_ERR_INVALID_ARG, "partition %u of %u", q.part, q.n_parts);
-    const uint32_t rows = partition_rows(c->hdr.height, part);
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(c->device));
+// What the context's cached lists add to a launch (ctx_render_slot).
+struct LaunchLists {
+    const uint32_t* d_tiles = nullptr;  // RenderArgs::tiles
+    uint32_t* d_ticks = nullptr;        // RenderArgs::wave_ticks
+    BlockList* timed_list = nullptr;    // a list whose own events bracket this launch
+    void* copy_counts_to = nullptr;     // where the launch's wave counts go afterwards, on its stream
+    const rtc_ctx::SceneTileList* scene_tiles = nullptr;
+};
+
+// (a world in which nothing reflects or transmits -- an empty world among them, which the reference renders black at any
+// depth -- never suspends a shade_hit: whatever the depth asked for, the base kernels trace it as they trace depth 8)
+static bool scene_recurses(const rtc_ctx* c) {
+    const size_t stride = padded_count(c->hdr.n_objects);
+    for (uint32_t i = 0; i < c->hdr.n_objects; i++) {
+        const float4 mb = c->soa_host[5 * stride + i], mc = c->soa_host[6 * stride + i];
+        if (!(mb.w == 0.0f) || !(mc.x == 0.0f)) return true;  // reflective, transparency (NaN: recurses)
+    }
+    return false;
+}
+
+// room for one more of the context's block lists (a caller cycling through partitions without end: start over -- nothing may be in flight)
+static rtc_status block_list_room(rtc_ctx* c) {
+    if (c->block_lists.size() >= 256u) {
+        HIP_TRY(hipDeviceSynchronize());
+        drop_block_lists(c);
+    }
+    return RTC_OK;
+}
+
+// Tree worlds with meshes: a block list instead of the regular grid -- the tiles a mesh projects to first, eight
+// lanes per pixel there and one elsewhere (build_block_list).
+// ... and frames that share an area light's cells between a pixel's lanes (small frames: choose_share_log2), when there is a
+// frame before to go by: the list starts with the frame's one lane count everywhere, and the feedback gives the tiles in the
+// penumbra more lanes, the lit and the empty ones fewer (refine_block_list).
+// One list per partition, built on first use and kept until the scene changes: rtc_render_ex renders a frame as
+// several partitions of one context, frame after frame (a single cached list meant a device synchronisation, a
+// rebuild and a blocking copy per chunk launch).
+static rtc_status use_block_list(rtc_ctx* c, const Partition& q, uint32_t rows, int32_t depth, uint32_t share_log2, bool mesh_list, hipStream_t stream,
+                                 LaunchPlan* lp, LaunchLists* L) {
     const Policy& P = c->policy;
-    // camera.rs:76 takes any depth; the kernels' frame stack (one suspended shade_hit per level, world.rs:62-86) holds
-    // RTC_STACK_DEPTH_BASE levels.  Deeper than that, the scene's kernel is compiled once more with a longer stack -- 16, 32,
-    // ... RTC_MAX_DEPTH levels of per-lane scratch -- on first use, and kept with the context.
-    hipFunction_t spec_fn = c->spec_fn;
-    // (a world in which nothing reflects or transmits -- an empty world among them, which the reference renders black at any
-    // depth -- never suspends a shade_hit: whatever the depth asked for, the base kernels trace it as they trace depth 8)
-    bool recurses = false;
-    for (uint32_t i = 0; i < c->hdr.n_objects && !recurses; i++) {
-        const float4 mb = c->soa_host[5 * (size_t)padded_count(c->hdr.n_objects) + i], mc = c->soa_host[6 * (size_t)padded_count(c->hdr.n_objects) + i];
-        recurses = !(mb.w == 0.0f) || !(mc.x == 0.0f);  // reflective, transparency (NaN: recurses)
+    const std::array<uint32_t, 5> key = {q.band_rows, q.n_parts, q.part, share_log2, P.block_feedback ? (uint32_t)depth : 0u};
+    auto it = c->block_lists.find(key);
+    if (it == c->block_lists.end()) {
+        RTC_TRY(block_list_room(c));
+        std::vector<uint32_t> host;
+        if (mesh_list) build_block_list(P.block_order, P.block_s, P.block_s_top, TileMask{c->heavy_tiles.data(), c->heavy_w, c->heavy_h}, c->hdr.width, share_log2, rows, q, &host);
+        else uniform_block_list(share_log2, c->hdr.width, rows, &host);
+        BlockList bl;
+        bl.n = host.size();
+        if (P.block_feedback) bl.host = host;
+        HIP_TRY(grow(&bl.d, &bl.d_cap, host.size(), true));
+        // (a new buffer: no launch in flight can be reading it; the copy is complete when the call returns)
+        hipError_t ce = hipMemcpy(bl.d, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (ce != hipSuccess) {
+            (void)hipFree(bl.d);
+            return fail(RTC_ERR_DEVICE, "block list upload failed: %s", hipGetErrorString(ce));
+        }
+        it = c->block_lists.emplace(key, bl).first;
     }
-    if (depth > RTC_STACK_DEPTH_BASE && !recurses) depth = RTC_STACK_DEPTH_BASE;
-    if (depth > RTC_STACK_DEPTH_BASE && rows > 0u) {
-        rtc_status dst = deep_kernel(c, depth, &spec_fn);
-        if (dst != RTC_OK) return dst;
-    }
-    const uint32_t share_log2 = (spec_fn && c->spec_shares) ? choose_share_log2(c->hdr, rows, P, plan == nullptr) : 0u;  // only kernels compiled for it share lanes
-    const uint32_t bw = 16u >> (share_log2 >> 1), bh = 16u >> ((share_log2 + 1u) >> 1);  // pixels per workgroup (2x2 wave tiles)
-    dim3 grid((c->hdr.width + bw - 1) / bw, (rows + bh - 1) / bh), block(256);
-    // Frames of very many very short waves: several blocks per workgroup (RTC_AMD_BLOCKS_Y=1..8 overrides)
-    uint32_t blocks_y = 1u;
-    if (!(spec_fn && c->spec_blocks_y)) {
-        // (only kernels compiled for it loop over blocks)
-    } else if (P.blocks_y != 0) {
-        blocks_y = (uint32_t)P.blocks_y;
-    } else if ((uint64_t)grid.x * grid.y >= (1u << 15)) {
-        // most workgroups see nothing but the sky: C5 8192^2 0.51 -> 0.43 ms, single_sphere 4096^2 0.088 -> 0.061 ms.  (Where the
-        // waves have work -- hexagons, grouped_grid, whose boxes fill the frame -- four blocks per workgroup cost 8 ... 17 %.)
-        blocks_y = 4u;
-    }
-    grid.y = (grid.y + blocks_y - 1) / blocks_y;
-    // Tree worlds with meshes: a block list instead of the regular grid -- the tiles a mesh projects to first, eight
-    // lanes per pixel there and one elsewhere (build_block_list).  Not when RTC_AMD_SHARE_LOG2 pins one value for all.
-    const uint32_t* d_tiles = nullptr;
-    uint32_t* d_ticks = nullptr;
-    BlockList* timed_list = nullptr;  // a list whose own events bracket this launch
-    void* copy_counts_to = nullptr;
-    const bool mesh_list = spec_fn && c->spec_shares && !c->heavy_tiles.empty() && c->hdr.light_kind == RTC_LIGHT_POINT;
-    // ... and frames that share an area light's cells between a pixel's lanes (small frames: choose_share_log2), when there is a
-    // frame before to go by: the list starts with the frame's one lane count everywhere, and the feedback gives the tiles in the
-    // penumbra more lanes, the lit and the empty ones fewer (refine_block_list).  Not for rtc_render_ex, whose rows leave in order.
-    const bool area_list = spec_fn && c->spec_shares && c->hdr.light_kind == RTC_LIGHT_RECT && share_log2 != 0u && P.block_feedback && plan == nullptr;
-    if ((mesh_list || area_list) && P.share_log2 < 0 && c->hdr.width <= 65532u && rows <= 131068u && rows > 0u) {
-        // one list per partition, built on first use and kept until the scene changes: rtc_render_ex renders a frame as
-        // several partitions of one context, frame after frame (a single cached list meant a device synchronisation, a
-        // rebuild and a blocking copy per chunk launch)
-        const std::array<uint32_t, 5> key = {q.band_rows, q.n_parts, q.part, share_log2, P.block_feedback ? (uint32_t)depth : 0u};
-        auto it = c->block_lists.find(key);
-        if (it == c->block_lists.end()) {
-            if (c->block_lists.size() >= 256u) {  // a caller cycling through partitions without end: start over (nothing may be in flight)
-                HIP_TRY(hipDeviceSynchronize());
-                drop_block_lists(c);
-            }
-            const rtc_ctx_tiles T = {c->heavy_tiles.data(), c->heavy_w, c->heavy_h};
-            std::vector<uint32_t> host;
-            if (mesh_list) {
-                build_block_list(P, T, c->hdr.width, share_log2, rows, q, &host);
-            } else {  // every tile with the frame's lane count, in image order
-                const uint32_t hbw = 16u >> (share_log2 >> 1), hbh = 16u >> ((share_log2 + 1u) >> 1);
-                for (uint32_t y0 = 0; y0 < rows; y0 += 16u)
-                    for (uint32_t x0 = 0; x0 < c->hdr.width; x0 += 16u)
-                        for (uint32_t dy = 0; dy < 16u && y0 + dy < rows; dy += hbh)
-                            for (uint32_t dx = 0; dx < 16u && x0 + dx < c->hdr.width; dx += hbw)
-                                host.push_back(tile_word(share_log2, x0 + dx, y0 + dy));
-            }
-            BlockList bl;
-            bl.n = host.size();
-            if (P.block_feedback) bl.host = host;
-            HIP_TRY(grow(&bl.d, &bl.d_cap, host.size() * sizeof(uint32_t)));
-            // (a new buffer: no launch in flight can be reading it; the copy is complete when the call returns)
-            hipError_t ce = hipMemcpy(bl.d, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (ce != hipSuccess) {
-                (void)hipFree(bl.d);
-                return fail(RTC_ERR_DEVICE, "block list upload failed: %s", hipGetErrorString(ce));
-            }
-            it = c->block_lists.emplace(key, bl).first;
-        }
-        BlockList& bl = it->second;
-        if (P.block_feedback && bl.state == BlockList::TIMED) {
-            const rtc_status st = recut_block_list(c, bl, rows);
-            if (st != RTC_OK) return st;
-        }
-        // (a refined list under scenes that change: every frame is timed -- restart_block_lists decides from them when to re-cut)
-        if (P.block_feedback && (bl.state == BlockList::FRESH || (bl.state == BlockList::REFINED && bl.animated)) && bl.n != 0) {
-            HIP_TRY(grow(&bl.d_ticks, &bl.ticks_cap, 4u * bl.n * sizeof(uint32_t)));
-            HIP_TRY(hipMemsetAsync(bl.d_ticks, 0, 4u * bl.n * sizeof(uint32_t), stream));
-            d_ticks = bl.d_ticks;
-            if (bl.state == BlockList::FRESH) {
-                bl.state = BlockList::TIMED;
-            } else {
-                if (bl.ev0 == nullptr) {
-                    HIP_TRY(hipEventCreate(&bl.ev0));
-                    HIP_TRY(hipEventCreate(&bl.ev1));
-                }
-                timed_list = &bl;
-            }
-        }
-        d_tiles = it->second.d;
-        grid = dim3((uint32_t)it->second.n, 1);
-    }
-    // traced pixels among this partition's rows: x < w-1, y < h-1
-    uint64_t traced_rows = 0;
-    {
-        uint32_t n_bands = (c->hdr.height + q.band_rows - 1) / q.band_rows;
-        for (uint32_t b = q.part; b < n_bands; b += q.n_parts) {
-            uint32_t y0 = b * q.band_rows;
-            uint32_t y1 = y0 + q.band_rows < c->hdr.height ? y0 + q.band_rows : c->hdr.height;
-            uint32_t lim = c->hdr.height - 1;
-            traced_rows += (y1 < lim ? y1 : lim) - (y0 < lim ? y0 : lim);
-        }
-    }
-    c->last_rows = rows;
-    c->last_pixels = traced_rows * (uint64_t)(c->hdr.width - 1);
-    // Level by level instead of pixel by pixel (rtc_wavefront.h): only on request (RTC_AMD_WAVEFRONT=1).  Built in round 3 for
-    // the frames whose time is their longest wave (glass meshes), bit-identical -- and measured slower everywhere: mesh 2048^2
-    // 8.0 ms against 3.8, here_be_dragons 4000 x 1600 9.6 against 3.0 (profiles/r03_wavefront_ab.txt).  A level is a launch, a
-    // launch ends with ITS longest wave -- one packet walk over a divided mesh is hundreds of microseconds -- and a frame of
-    // depth 5 pays six of those tails where the per-pixel kernel pays one; its walks are also the generic ones (no lanes
-    // splitting leaf runs, no per-scene compile).  What the finding asks for is a single persistent launch with a queue of rays
-    // and continuation frames, not level-synchronous passes.  Kept as a verified alternative, not a default.
-    if (c->hdr.n_trav != 0u && rows > 0u && depth >= 1 && depth <= RTC_STACK_DEPTH_BASE && (int)depth < (int)WF_MAX_LEVELS && !c->wf_disabled &&
-        (size_t)rows * c->hdr.width <= (16u << 20) && P.wavefront == 1) {
-        bool used = false;
-        rtc_status wst = render_wavefront(c, depth, q, rows, d_out_rgb, out_u8, stream, slot, &used);
-        if (wst != RTC_OK) return wst;
-        if (used) return RTC_OK;
-    }
-    c->wf_last = false;
-    // Scene rectangle: every primary ray outside the rectangle the scene's box projects to (project_heavy_boxes: exact
-    // camera arithmetic in double, 8 pixels of padding, "everything" if the box reaches behind the camera) sees nothing --
-    // black, one ray.  Where that rectangle is under half the frame (C5: a grid of spheres in the middle of 8192^2) the
-    // kernel is launched over the rectangle's blocks only, preceded by workgroups that zero-fill the rest at memory speed
-    // while the others render; the rays of the pixels outside are added to the count (sum_counts_kernel).
-    // RTC_AMD_SCENE_RECT=0: the whole grid, as before.
-    uint32_t block_x0 = 0u, block_y0 = 0u;
-    unsigned long long extra_rays = 0ull;
-    uint32_t fill_wg_rows = 0u, fill_rows = 0u, fill_period = 1u, fill_rect[4] = {0u, 0u, 0u, 0u};
-    bool rect_launch = false;
-    // Scene tiles (rtc_ctx::scene_tile_mask): the canvas is zero-filled at memory speed (805 MB of an 8192^2 frame: 0.12 ms) and
-    // only the tiles some entry of the world projects to get a workgroup -- C5: 18 k of 262 k, where the bounding rectangle of
-    // them all has 60 k, and a frame of such short waves costs what starting them costs (0.78 waves per ns).  The pixels of
-    // the other tiles are one ray each that sees nothing (sum_counts_kernel's extra_rays).
-    bool tile_launch = false;
-    const uint2* fill_jobs = nullptr;
-    size_t n_fill_jobs = 0;
-    if (d_tiles == nullptr && share_log2 == 0u && rows > 0u && !c->scene_tile_mask.empty() && (q.band_rows & 15u) == 0u &&
-        c->hdr.width <= 65532u && rows <= 131068u) {
-        const std::array<uint32_t, 3> key = {q.band_rows, q.n_parts, q.part};
-        auto it = c->scene_tile_lists.find(key);
-        if (it == c->scene_tile_lists.end()) {
-            std::vector<uint32_t> list;
-            std::vector<uint2> fill;
-            rtc_ctx::SceneTileList tl;
-            const uint32_t n_bands = (c->hdr.height + q.band_rows - 1) / q.band_rows;
-            uint32_t cursor = 0u;
-            for (uint32_t b = q.part; b < n_bands; b += q.n_parts) {
-                const uint32_t y0 = b * q.band_rows, y1 = std::min(c->hdr.height, y0 + q.band_rows);
-                for (uint32_t ty = y0 / 16u; ty * 16u < y1; ty++) {
-                    const uint32_t yl = cursor + (ty * 16u - y0);
-                    uint32_t run0 = 0u, run = 0u;  // the current run of unlisted tiles: [run0, run0 + run)
-                    auto close_run = [&]() {
-                        for (uint32_t k = 0; k < run; k += 64u) fill.push_back(make_uint2((run0 + k) | (std::min(64u, run - k) << 16), yl));
-                        run = 0u;
-                    };
-                    for (uint32_t tx = 0; tx < c->scene_tiles_w; tx++) {
-                        if (!c->scene_tile_mask[(size_t)ty * c->scene_tiles_w + tx]) {
-                            if (run == 0u) run0 = tx;
-                            run++;
-                            continue;
-                        }
-                        close_run();
-                        list.push_back(tile_word(0u, tx * 16u, yl));
-                        const uint32_t px1 = std::min(c->hdr.width - 1u, tx * 16u + 16u), py1 = std::min(std::min(c->hdr.height - 1u, y1), ty * 16u + 16u);
-                        if (px1 > tx * 16u && py1 > ty * 16u) tl.traced_pixels += (unsigned long long)(px1 - tx * 16u) * (py1 - ty * 16u);
-                    }
-                    close_run();
-                }
-                cursor += y1 - y0;
-            }
-            tl.n = list.size();
-            tl.n_fill = fill.size();
-            if (tl.n) {
-                HIP_TRY(hipMalloc((void**)&tl.d, tl.n * sizeof(uint32_t)));
-                HIP_TRY(hipMemcpyAsync(tl.d, list.data(), tl.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                if (tl.n_fill) {
-                    HIP_TRY(hipMalloc((void**)&tl.d_fill, tl.n_fill * sizeof(uint2)));
-                    HIP_TRY(hipMemcpyAsync(tl.d_fill, fill.data(), tl.n_fill * sizeof(uint2), hipMemcpyHostToDevice, stream));
-                }
-                HIP_TRY(hipStreamSynchronize(stream));  // (the host vectors go out of scope)
-            }
-            it = c->scene_tile_lists.emplace(key, tl).first;
-        }
-        const rtc_ctx::SceneTileList& tl = it->second;
-        if (tl.n) {
-            if (!c->fill_stream) {
-                HIP_TRY(hipStreamCreateWithFlags(&c->fill_stream, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-            }
-            fill_jobs = tl.d_fill, n_fill_jobs = tl.n_fill;
-            d_tiles = tl.d;
-            grid = dim3((uint32_t)tl.n, 1);
-            blocks_y = 1u;
-            extra_rays = c->last_pixels - tl.traced_pixels;
-            tile_launch = true;
-        }
-    }
-    if (!tile_launch && d_tiles == nullptr && share_log2 == 0u && rows > 0u && c->scene_rect[0] < c->scene_rect[1] && c->scene_rect_coverage < P.scene_rect_threshold() &&
-        (spec_fn == nullptr || c->spec_rect)) {
-        // local rows of this partition whose global row lies in the rectangle's rows, and the traced ones among them
-        const uint32_t gy0 = c->scene_rect[2] * 16u, gy1 = std::min(c->hdr.height, c->scene_rect[3] * 16u);
-        uint32_t yl0 = rows, yl1 = 0u, cursor = 0u;
-        const uint32_t n_bands = (c->hdr.height + q.band_rows - 1) / q.band_rows;
-        for (uint32_t b = q.part; b < n_bands; b += q.n_parts) {
-            const uint32_t y0 = b * q.band_rows, y1 = std::min(c->hdr.height, y0 + q.band_rows);
-            const uint32_t lo = std::max(y0, gy0), hi = std::min(y1, gy1);
-            if (lo < hi) yl0 = std::min(yl0, cursor + (lo - y0)), yl1 = std::max(yl1, cursor + (hi - y0));
-            cursor += y1 - y0;
-        }
-        rect_launch = true;
-        if (yl0 < yl1) {
-            block_x0 = c->scene_rect[0];
-            block_y0 = yl0 / 16u;
-            // every workgroup of this launch has work: one block each unless told otherwise (C5 0.395 / 0.407 / 0.427 / 0.46 ms
-            // with 1 / 2 / 4 / 8 blocks per workgroup)
-            const uint32_t block_rows = (yl1 - block_y0 * 16u + 15u) / 16u;
-            if (P.blocks_y == 0) blocks_y = 1u;
-            grid = dim3(c->scene_rect[1] - c->scene_rect[0], (block_rows + blocks_y - 1u) / blocks_y);
-        } else {
-            grid = dim3(1, 1);  // none of this partition's rows: one block of the rectangle's columns, for the launch's bookkeeping
-            block_x0 = c->scene_rect[0];
-            block_y0 = 0u;
-            blocks_y = 1u;
-        }
-        // traced pixels (x < w - 1, y < h - 1) inside the launched blocks
-        const uint32_t lx0 = block_x0 * 16u, lx1 = std::min(c->hdr.width - 1u, (block_x0 + grid.x) * 16u);
-        const uint32_t ly0 = block_y0 * 16u, ly1 = std::min(rows, (block_y0 + grid.y * blocks_y) * 16u);
-        uint64_t launched_rows = 0;
-        cursor = 0u;
-        for (uint32_t b = q.part; b < n_bands; b += q.n_parts) {
-            const uint32_t y0 = b * q.band_rows, y1 = std::min(c->hdr.height, y0 + q.band_rows);
-            // local rows [cursor, cursor + y1 - y0) of this band that are launched, and traced (global row < h - 1)
-            const uint32_t a = std::max(cursor, ly0), e = std::min(cursor + (y1 - y0), ly1);
-            if (a < e) {
-                const uint32_t ga = y0 + (a - cursor), ge = y0 + (e - cursor), lim = c->hdr.height - 1u;
-                launched_rows += std::min(ge, lim) - std::min(ga, lim);
-            }
-            cursor += y1 - y0;
-        }
-        extra_rays = c->last_pixels - launched_rows * (uint64_t)(lx1 > lx0 ? lx1 - lx0 : 0u);
-        // what the launched blocks do not cover is zero-filled by the launch's first workgroups (the kernel's fill_outside):
-        // about a thousand of them, a share of the rows each
-        fill_rect[0] = block_x0 * 16u, fill_rect[1] = std::min(c->hdr.width, (block_x0 + grid.x) * 16u);
-        fill_rect[2] = ly0, fill_rect[3] = ly1;
-        // about 160 KB of zeros per workgroup -- C5 (805 MB): 0.350 / 0.329 / 0.313 / 0.329 ms with 256 / 2048 / 4096 / 16384 of
-        // them; a frame of 4096 blocks must not get as many again (RTC_AMD_FILL_WGS: development)
-        const uint64_t frame_bytes = (uint64_t)rows * c->hdr.width * 12u;
-        uint32_t fill_wgs = (uint32_t)std::min<uint64_t>(4096u, std::max<uint64_t>(16u, frame_bytes / (160u << 10)));
-        if (P.fill_wgs != 0u) fill_wgs = P.fill_wgs;
-        fill_wg_rows = std::max(1u, (fill_wgs + grid.x - 1u) / grid.x);
-        fill_rows = (rows + fill_wg_rows * grid.x - 1u) / (fill_wg_rows * grid.x);
-        fill_period = std::max(1u, (grid.y + fill_wg_rows) / fill_wg_rows);  // spread among the rendering rows: the fill shares the memory system with them
-        if (out_u8) {
-            // a frame of bytes: the zeros outside the rectangle are one asynchronous memset in front of the launch (the
-            // kernel's filling workgroups write f32 rows)
-            HIP_TRY(hipMemsetAsync(d_out_rgb, 0, (size_t)rows * c->hdr.width * 3u, stream));
-            fill_wg_rows = 0u, fill_rows = 0u, fill_period = 1u;
-        }
-        grid.y += fill_wg_rows;
-    }
-    // the plain regular grid: blocks permuted within four rows (RenderArgs::swizzle), the grid padded to what that needs --
-    // workgroups of the padding find no pixel of theirs inside the image
-    const bool swizzle = P.swizzle && d_tiles == nullptr && rows > 0u && !rect_launch && blocks_y == 1u;
-    if (swizzle) grid = dim3((grid.x + 1u) & ~1u, (grid.y + 3u) & ~3u);
-    // A regular grid's frames after the first: the same 16 x 16 blocks, started in the order of their longest wave in the frame
-    // before (refine_block_list: a list of one lane per pixel throughout).  Where the grid is the plain one -- one block per
-    // workgroup, no scene rectangle, nobody waiting for rows in image order (rtc_render_ex's progress words) -- and the frame
-    // has a tail worth the list: its longest wave is a tenth of its throughput time or more.
-    if (d_tiles == nullptr && P.block_feedback && P.grid_feedback && plan == nullptr && rows > 0u && !rect_launch && blocks_y == 1u && share_log2 == 0u &&
-        c->hdr.width <= 65532u && rows <= 131068u && !(c->hdr.n_trav != 0u && c->policy.wavefront)) {
-        const std::array<uint32_t, 5> key = {q.band_rows, q.n_parts, q.part, 0xffffffffu, (uint32_t)depth};
-        auto it = c->block_lists.find(key);
-        if (it == c->block_lists.end()) {
-            if (c->block_lists.size() >= 256u) {
-                HIP_TRY(hipDeviceSynchronize());
-                drop_block_lists(c);
-            }
-            BlockList bl;
-            bl.n = (size_t)grid.x * grid.y;
-            bl.state = BlockList::IDLE;
-            it = c->block_lists.emplace(key, bl).first;
-        }
-        BlockList& bl = it->second;
-        if (bl.state == BlockList::TIMED) {
-            const rtc_status st = order_grid(c, bl, grid.x, grid.y, rows);
-            if (st != RTC_OK) return st;
-        }
-        if (bl.state == BlockList::IDLE) {
-            bl.state = BlockList::FRESH;  // (the next frame of this scene, if there is one, is measured)
-        } else if (bl.state == BlockList::FRESH && bl.n == (size_t)grid.x * grid.y) {
-            bl.counts = !(spec_fn && c->spec_shares);
-            bl.swizzled = swizzle;
-            const size_t nt = bl.n;
-            HIP_TRY(grow(&bl.d_ticks, &bl.ticks_cap, 4u * nt * (bl.counts ? sizeof(uint4) : sizeof(uint32_t))));
-            if (bl.counts) {
-                copy_counts_to = bl.d_ticks;  // (after the launch, on its stream)
-            } else {
-                HIP_TRY(hipMemsetAsync(bl.d_ticks, 0, 4u * nt * sizeof(uint32_t), stream));
-                d_ticks = bl.d_ticks;
-            }
+    BlockList& bl = it->second;
+    if (P.block_feedback && bl.state == BlockList::TIMED) RTC_TRY(recut_block_list(c, bl, rows));
+    // (a refined list under scenes that change: every frame is timed -- restart_block_lists decides from them when to re-cut)
+    if (P.block_feedback && (bl.state == BlockList::FRESH || (bl.state == BlockList::REFINED && bl.animated)) && bl.n != 0) {
+        HIP_TRY(grow(&bl.d_ticks, &bl.ticks_cap, 4u * bl.n, true));
+        HIP_TRY(hipMemsetAsync(bl.d_ticks, 0, 4u * bl.n * sizeof(uint32_t), stream));
+        L->d_ticks = bl.d_ticks;
+        if (bl.state == BlockList::FRESH) {
             bl.state = BlockList::TIMED;
-        } else if (bl.state == BlockList::REFINED && bl.listed) {
-            d_tiles = bl.d;
-            grid = dim3((uint32_t)bl.n_listed, 1);
+        } else {
+            if (bl.ev0 == nullptr) {
+                HIP_TRY(hipEventCreate(&bl.ev0));
+                HIP_TRY(hipEventCreate(&bl.ev1));
+            }
+            L->timed_list = &bl;
         }
     }
-    const size_t n_blocks = (size_t)grid.x * grid.y * 4;  // partial counts: one per wave
-    if (n_blocks > c->block_cap) {  // grow-only workspace (first call / larger image only)
-        if (c->d_block_counts) HIP_TRY(hipFree(c->d_block_counts));
-        c->d_block_counts = nullptr;
-        HIP_TRY(hipMalloc(&c->d_block_counts, n_blocks * sizeof(uint4)));
-        c->block_cap = n_blocks;
-    }
-    // progress reporting: a regular grid only (one workgroup per block, every block of the partition launched)
-    uint32_t chunk_block_rows = 1u, n_chunks = 0u;
-    if (plan && plan->d_done && rows > 0u && d_tiles == nullptr && !rect_launch && blocks_y == 1u) {
-        const uint32_t want = std::max(1u, std::min(plan->want_chunks, PROGRESS_MAX_CHUNKS));
-        chunk_block_rows = (grid.y + want - 1u) / want;
-        if (swizzle) chunk_block_rows = (chunk_block_rows + 3u) & ~3u;  // (block rows finish four at a time)
-        n_chunks = (grid.y + chunk_block_rows - 1u) / chunk_block_rows;
-        const size_t words = ((size_t)grid.y + n_chunks) * PROGRESS_STRIDE;
-        if (words > c->progress_cap) {
-            if (c->d_progress) HIP_TRY(hipFree(c->d_progress));
-            c->d_progress = nullptr;
-            c->progress_cap = 0;
-            HIP_TRY(hipMalloc(&c->d_progress, words * sizeof(uint32_t)));
-            c->progress_cap = words;
+    L->d_tiles = bl.d;
+    lp->run_list(bl.n);
+    return RTC_OK;
+}
+
+// Scene tiles (rtc_ctx::scene_tile_mask): the canvas is zero-filled at memory speed (805 MB of an 8192^2 frame: 0.12 ms) and
+// only the tiles some entry of the world projects to get a workgroup -- C5: 18 k of 262 k, where the bounding rectangle of
+// them all has 60 k, and a frame of such short waves costs what starting them costs (0.78 waves per ns).  The partition's
+// list, built and uploaded on first use (an empty one: nothing of the scene in this partition's rows).
+static rtc_status use_scene_tile_list(rtc_ctx* c, const Partition& q, hipStream_t stream, const rtc_ctx::SceneTileList** out) {
+    const std::array<uint32_t, 3> key = {q.band_rows, q.n_parts, q.part};
+    auto it = c->scene_tile_lists.find(key);
+    if (it == c->scene_tile_lists.end()) {
+        SceneTilePlan host;
+        plan_scene_tiles(TileMask{c->scene_tile_mask.data(), c->scene_tiles_w, c->scene_tiles_h}, c->hdr.width, c->hdr.height, q, &host);
+        static_assert(sizeof(FillRun) == sizeof(uint2), "fill_tiles_kernel reads the runs as uint2");
+        rtc_ctx::SceneTileList tl;
+        tl.n = host.tiles.size();
+        tl.n_fill = host.fill.size();
+        tl.traced_pixels = host.traced_pixels;
+        if (tl.n) {
+            HIP_TRY(hipMalloc((void**)&tl.d, tl.n * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpyAsync(tl.d, host.tiles.data(), tl.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            if (tl.n_fill) {
+                HIP_TRY(hipMalloc((void**)&tl.d_fill, tl.n_fill * sizeof(uint2)));
+                HIP_TRY(hipMemcpyAsync(tl.d_fill, host.fill.data(), tl.n_fill * sizeof(uint2), hipMemcpyHostToDevice, stream));
+            }
+            HIP_TRY(hipStreamSynchronize(stream));  // (the host vectors go out of scope)
         }
-        HIP_TRY(hipMemsetAsync(c->d_progress, 0, words * sizeof(uint32_t), stream));
-        plan->n_chunks = n_chunks;
-        plan->chunk_rows = chunk_block_rows * bh;
+        it = c->scene_tile_lists.emplace(key, tl).first;
     }
-    if (rows == 0) {  // nothing to launch: the slot's counters read zero
-        HIP_TRY(hipMemsetAsync(c->d_total + 3 * (size_t)slot, 0, 3 * sizeof(unsigned long long), stream));
-        if (slot == 0) c->rendered = false;
-        return RTC_OK;
+    if (it->second.n && !c->fill_stream) {  // the zero-fill runs beside the render kernel (fork / join by events)
+        HIP_TRY(hipStreamCreateWithFlags(&c->fill_stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     }
+    *out = &it->second;
+    return RTC_OK;
+}
+
+// A regular grid's frames after the first: the same 16 x 16 blocks, started in the order of their longest wave in the frame
+// before (refine_block_list: a list of one lane per pixel throughout).  Where the grid is the plain one -- one block per
+// workgroup, no scene rectangle, nobody waiting for rows in image order (rtc_render_ex's progress words) -- and the frame
+// has a tail worth the list: its longest wave is a tenth of its throughput time or more.
+// timed_waves: the kernel leaves its waves' times (else their work counts are taken).
+static rtc_status use_grid_feedback(rtc_ctx* c, const Partition& q, uint32_t rows, int32_t depth, bool timed_waves, hipStream_t stream, LaunchPlan* lp,
+                                    LaunchLists* L) {
+    const std::array<uint32_t, 5> key = {q.band_rows, q.n_parts, q.part, 0xffffffffu, (uint32_t)depth};
+    auto it = c->block_lists.find(key);
+    if (it == c->block_lists.end()) {
+        RTC_TRY(block_list_room(c));
+        BlockList bl;
+        bl.n = lp->n_workgroups();
+        bl.state = BlockList::IDLE;
+        it = c->block_lists.emplace(key, bl).first;
+    }
+    BlockList& bl = it->second;
+    if (bl.state == BlockList::TIMED) RTC_TRY(order_grid(c, bl, lp->grid_x, lp->grid_y, rows));
+    if (bl.state == BlockList::IDLE) {
+        bl.state = BlockList::FRESH;  // (the next frame of this scene, if there is one, is measured)
+    } else if (bl.state == BlockList::FRESH && bl.n == lp->n_workgroups()) {
+        bl.counts = !timed_waves;
+        bl.swizzled = lp->swizzle;
+        HIP_TRY(grow(&bl.d_ticks, &bl.ticks_cap, 4u * bl.n * (bl.counts ? sizeof(uint4) / sizeof(uint32_t) : 1u), true));
+        if (bl.counts) {
+            L->copy_counts_to = bl.d_ticks;
+        } else {
+            HIP_TRY(hipMemsetAsync(bl.d_ticks, 0, 4u * bl.n * sizeof(uint32_t), stream));
+            L->d_ticks = bl.d_ticks;
+        }
+        bl.state = BlockList::TIMED;
+    } else if (bl.state == BlockList::REFINED && bl.listed) {
+        L->d_tiles = bl.d;
+        lp->run_list(bl.n_listed);
+    }
+    return RTC_OK;
+}
+
+// The FIRST launch of a code object on a queue pays what is not the kernel's: the runtime moves the code to the device and
+// sizes the queue's scratch for it -- 6 to 11 ms in a fresh process for these kernels (tools/first_frame_probe.py: C3's first
+// frame 0.95 ms cold, 0.71 once any context of the process has launched the same code; mesh 11.2 / 3.4).  It is paid once per
+// process and queue, here: one workgroup of the same kernel over zero rows (it finds no pixel of its own and writes only
+// the counters the real launch overwrites), in front of the events that time the frame.
+static rtc_status warm_up(rtc_ctx* c, hipFunction_t spec_fn, hipStream_t stream, const RenderArgs& a) {
+    const auto key = std::make_pair(spec_fn ? (const void*)spec_fn : aot_family(c).key(), (const void*)stream);
+    if (c->warmed.count(key)) return RTC_OK;
+    c->warmed.insert(key);
+    RenderArgs w = a;
+    w.rows = 0u, w.tiles = nullptr, w.wave_ticks = nullptr, w.progress = nullptr, w.done = nullptr, w.fill_wg_rows = 0u, w.swizzle = 0u, w.blocks_y = 1u;
+    HIP_TRY(launch_render(c, spec_fn, dim3(1, 1), stream, w));
+    return RTC_OK;
+}
+
+// A scene-tile launch's zero-fill of the unlisted tiles runs beside the render kernel, on the context's fill stream: memory-bound
+// work under arithmetic.  (The caller joins: the frame's stream waits for ev_join after the render kernel.)
+static rtc_status fork_tile_fill(rtc_ctx* c, const rtc_ctx::SceneTileList& tl, void* d_out, uint32_t rows, bool out_u8, hipStream_t stream) {
+    HIP_TRY(hipEventRecord(c->ev_fork, stream));
+    HIP_TRY(hipStreamWaitEvent(c->fill_stream, c->ev_fork, 0));
+    // 96 workgroups share the jobs: enough to move 690 MB in the time C5's tiles take to render, few enough to leave the chip's wave
+    // slots to the render kernel (C5 8192^2, whole frame: 0.84 / 0.46 / 0.33 / 0.294 / 0.30 / 0.36 / 0.38 ms with 16 / 32 / 64 / 96 /
+    // 128 / 512 / 4096 of them; the bounding rectangle with its interleaved fill: 0.335; profiles/r04_c5_tile_fill.txt)
+    const uint32_t fill_wgs = c->policy.tile_fill_wgs ? c->policy.tile_fill_wgs : 96u;
+    hipLaunchKernelGGL(fill_tiles_kernel, dim3((uint32_t)std::min<size_t>(tl.n_fill, fill_wgs)), dim3(256), 0, c->fill_stream, tl.d_fill,
+                       (uint32_t)tl.n_fill, (uint8_t*)d_out, c->hdr.width, rows, out_u8 ? 3u : 12u);
+    HIP_TRY(hipEventRecord(c->ev_join, c->fill_stream));
+    return RTC_OK;
+}
+
+// RenderArgs of a frame: the one place where a LaunchPlan and the lists' device pointers become kernel arguments
+static RenderArgs render_args(const rtc_ctx* c, const Partition& q, uint32_t rows, int32_t depth, uint32_t share_log2, void* d_out_rgb, bool out_u8,
+                              unsigned long long* total, const ProgressPlan* progress, const LaunchPlan& lp, const LaunchLists& L) {
     RenderArgs a;
     a.hdr = c->hdr;
     a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
     a.out = out_u8 ? nullptr : (float*)d_out_rgb;
     a.out_u8 = out_u8 ? (uint8_t*)d_out_rgb : nullptr;
-    a.progress = n_chunks ? c->d_progress : nullptr;
-    a.done = n_chunks ? plan->d_done : nullptr;
-    a.chunk_block_rows = chunk_block_rows;
-    a.epoch = plan ? plan->epoch : 0u;
+    a.progress = lp.n_chunks ? c->d_progress : nullptr;
+    a.done = lp.n_chunks ? progress->d_done : nullptr;
+    a.chunk_block_rows = lp.chunk_block_rows;
+    a.epoch = progress ? progress->epoch : 0u;
     a.block_counts = c->d_block_counts;
-    a.total = c->d_total + 3 * (size_t)slot;
-    a.rows = rows;
-    a.band_rows = q.band_rows;
-    a.n_parts = q.n_parts;
-    a.part = q.part;
+    a.total = total;
+    a.rows = rows, a.band_rows = q.band_rows, a.n_parts = q.n_parts, a.part = q.part;
     a.depth = depth;
     a.share_log2 = share_log2;
-    a.tiles = d_tiles;
-    a.wave_ticks = d_ticks;
-    a.blocks_y = blocks_y;
-    a.swizzle = (swizzle && d_tiles == nullptr) ? 1u : 0u;
-    a.block_x0 = block_x0;
-    a.block_y0 = block_y0;
-    a.fill_wg_rows = fill_wg_rows, a.fill_rows = fill_rows, a.fill_period = fill_period;
-    a.fill_x0 = fill_rect[0], a.fill_x1 = fill_rect[1], a.fill_y0 = fill_rect[2], a.fill_y1 = fill_rect[3];
-    if (c->events_used == c->events.size()) {
-        if (c->events.size() >= 4096) {
-            c->events_used = 0;  // nobody is reading the timings: recycle
-        } else {
-            std::pair<hipEvent_t, hipEvent_t> e;
-            HIP_TRY(hipEventCreate(&e.first));
-            HIP_TRY(hipEventCreate(&e.second));
-            c->events.push_back(e);
+    a.tiles = L.d_tiles;
+    a.wave_ticks = L.d_ticks;
+    a.blocks_y = lp.blocks_y;
+    a.swizzle = lp.swizzle ? 1u : 0u;
+    a.block_x0 = lp.block_x0, a.block_y0 = lp.block_y0;
+    a.fill_wg_rows = lp.fill_wg_rows, a.fill_rows = lp.fill_rows, a.fill_period = lp.fill_period;
+    a.fill_x0 = lp.fill_rect[0], a.fill_x1 = lp.fill_rect[1], a.fill_y0 = lp.fill_rect[2], a.fill_y1 = lp.fill_rect[3];
+    return a;
+}
+
+// Level by level instead of pixel by pixel (rtc_wavefront.h): only on request (RTC_AMD_WAVEFRONT=1).  Built in round 3 for
+// the frames whose time is their longest wave (glass meshes), bit-identical -- and measured slower everywhere: mesh 2048^2
+// 8.0 ms against 3.8, here_be_dragons 4000 x 1600 9.6 against 3.0 (profiles/r03_wavefront_ab.txt).  A level is a launch, a
+// launch ends with ITS longest wave -- one packet walk over a divided mesh is hundreds of microseconds -- and a frame of
+// depth 5 pays six of those tails where the per-pixel kernel pays one; its walks are also the generic ones (no lanes
+// splitting leaf runs, no per-scene compile).  What the finding asks for is a single persistent launch with a queue of rays
+// and continuation frames, not level-synchronous passes.  Kept as a verified alternative, not a default.
+static bool wavefront_wanted(const rtc_ctx* c, uint32_t rows, int32_t depth) {
+    return c->hdr.n_trav != 0u && rows > 0u && depth >= 1 && depth <= RTC_STACK_DEPTH_BASE && (int)depth < (int)WF_MAX_LEVELS && !c->wf_disabled &&
+           (size_t)rows * c->hdr.width <= (16u << 20) && c->policy.wavefront == 1;
+}
+
+// What a partition with rows that is not run from a mesh / area-light block list is launched as: scene tiles, else the scene
+// rectangle, else the regular grid -- which alone, and only while it is one block per workgroup (plain_grid), is swizzled,
+// re-ordered by the grid feedback or cut into progress chunks.
+static rtc_status settle_shape(rtc_ctx* c, const Partition& q, uint32_t rows, int32_t depth, uint32_t share_log2, hipFunction_t spec_fn, void* d_out_rgb,
+                               bool out_u8, const ProgressPlan* progress, hipStream_t stream, LaunchPlan* lp, LaunchLists* L) {
+    const Policy& P = c->policy;
+    const bool list_words_fit = c->hdr.width <= 65532u && rows <= 131068u;  // (tile_word)
+    if (lp->shape == LaunchPlan::GRID && share_log2 == 0u && !c->scene_tile_mask.empty() && (q.band_rows & 15u) == 0u && list_words_fit) {
+        RTC_TRY(use_scene_tile_list(c, q, stream, &L->scene_tiles));
+        if (L->scene_tiles->n) {
+            lp->run_scene_tiles(L->scene_tiles->n, c->last_pixels - L->scene_tiles->traced_pixels);
+            L->d_tiles = L->scene_tiles->d;
         }
     }
-    auto& ev = c->events[c->events_used++];
-    // The FIRST launch of a code object on a queue pays what is not the kernel's: the runtime moves the code to the device and
-    // sizes the queue's scratch for it -- 6 to 11 ms in a fresh process for these kernels (tools/first_frame_probe.py: C3's first
-    // frame 0.95 ms cold, 0.71 once any context of the process has launched the same code; mesh 11.2 / 3.4).  It is paid once per
-    // process and queue, here: one workgroup of the same kernel over zero rows (it finds no pixel of its own and writes only
-    // the counters the real launch overwrites), in front of the events that time the frame.
-    {
-        const void* fn_key = spec_fn ? (const void*)spec_fn : (const void*)(uintptr_t)(0x1000u + (c->hdr.n_trav ? 1u : c->n_objects <= 4 ? 2u : c->n_objects <= 8 ? 4u : 6u) + (c->simple ? 1u : 0u));
-        const auto key = std::make_pair(fn_key, (const void*)stream);
-        if (!c->warmed.count(key)) {
-            c->warmed.insert(key);
-            RenderArgs w = a;
-            w.rows = 0u, w.tiles = nullptr, w.wave_ticks = nullptr, w.progress = nullptr, w.done = nullptr, w.fill_wg_rows = 0u, w.swizzle = 0u, w.blocks_y = 1u;
-            const dim3 one(1, 1);
-            if (spec_fn) {
-                void* wp[] = {&w};
-                HIP_TRY(hipModuleLaunchKernel(spec_fn, 1, 1, 1, block.x, 1, 1, 0, stream, wp, nullptr));
-            } else if (c->hdr.n_trav) hipLaunchKernelGGL((render_kernel<-1, false>), one, block, 0, stream, w);
-            else if (c->n_objects <= 4 && c->simple) hipLaunchKernelGGL((render_kernel<4, true>), one, block, 0, stream, w);
-            else if (c->n_objects <= 4) hipLaunchKernelGGL((render_kernel<4, false>), one, block, 0, stream, w);
-            else if (c->n_objects <= 8 && c->simple) hipLaunchKernelGGL((render_kernel<8, true>), one, block, 0, stream, w);
-            else if (c->n_objects <= 8) hipLaunchKernelGGL((render_kernel<8, false>), one, block, 0, stream, w);
-            else hipLaunchKernelGGL((render_kernel<0, false>), one, block, 0, stream, w);
-            HIP_TRY(hipGetLastError());
-        }
+    // Scene rectangle: every primary ray outside the rectangle the scene's box projects to (project_heavy_boxes: exact
+    // camera arithmetic in double, 8 pixels of padding, "everything" if the box reaches behind the camera) sees nothing --
+    // black, one ray.  Where that rectangle is under half the frame: plan_rect_launch.  RTC_AMD_SCENE_RECT=0: the whole grid.
+    if (lp->shape == LaunchPlan::GRID && share_log2 == 0u && c->scene_rect[0] < c->scene_rect[1] && c->scene_rect_coverage < P.scene_rect_threshold() &&
+        (spec_fn == nullptr || c->spec_rect)) {
+        plan_rect_launch(lp, c->hdr.width, c->hdr.height, q, rows, c->last_pixels, c->scene_rect, P.blocks_y == 0 ? 1u : lp->blocks_y, out_u8, P.fill_wgs);
+        // a frame of bytes: the zeros outside the rectangle are one asynchronous memset in front of the launch
+        if (out_u8) HIP_TRY(hipMemsetAsync(d_out_rgb, 0, (size_t)rows * c->hdr.width * 3u, stream));
     }
-    HIP_TRY(hipEventRecord(ev.first, stream));
-    if (tile_launch && n_fill_jobs) {  // the zero-fill of the unlisted tiles runs beside the render kernel: memory-bound work under arithmetic
-        HIP_TRY(hipEventRecord(c->ev_fork, stream));
-        HIP_TRY(hipStreamWaitEvent(c->fill_stream, c->ev_fork, 0));
-        // 96 workgroups share the jobs: enough to move 690 MB in the time C5's tiles take to render, few enough to leave the chip's wave
-        // slots to the render kernel (C5 8192^2, whole frame: 0.84 / 0.46 / 0.33 / 0.294 / 0.30 / 0.36 / 0.38 ms with 16 / 32 / 64 / 96 /
-        // 128 / 512 / 4096 of them; the bounding rectangle with its interleaved fill: 0.335; profiles/r04_c5_tile_fill.txt)
-        const uint32_t fill_wgs = P.tile_fill_wgs ? P.tile_fill_wgs : 96u;
-        hipLaunchKernelGGL(fill_tiles_kernel, dim3((uint32_t)std::min<size_t>(n_fill_jobs, fill_wgs)), dim3(256), 0, c->fill_stream, fill_jobs,
-                           (uint32_t)n_fill_jobs, (uint8_t*)d_out_rgb, c->hdr.width, rows, out_u8 ? 3u : 12u);
-        HIP_TRY(hipEventRecord(c->ev_join, c->fill_stream));
+    if (P.swizzle && lp->plain_grid()) lp->pad_for_swizzle();
+    if (lp->plain_grid() && P.block_feedback && P.grid_feedback && progress == nullptr && share_log2 == 0u && list_words_fit &&
+        !(c->hdr.n_trav != 0u && P.wavefront))
+        RTC_TRY(use_grid_feedback(c, q, rows, depth, spec_fn && c->spec_shares, stream, lp, L));
+    // progress reporting: a regular grid only (one workgroup per block, every block of the partition launched)
+    if (progress && progress->d_done && lp->plain_grid()) plan_chunks(lp, progress->want_chunks, PROGRESS_MAX_CHUNKS);
+    return RTC_OK;
+}
+
+// rtc_ctx_render with a counter slot of the caller's choosing (rtc_internal.h)
+rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* part, void* d_out_rgb, void* stream_, uint32_t slot,
+                                ProgressPlan* progress, bool out_u8) {
+    // ---- arguments
+    if (progress) progress->n_chunks = 0u, progress->chunk_rows = 0u;
+    if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: null argument");
+    if (slot >= CTX_TOTAL_SLOTS) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: counter slot %u", slot);
+    if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: no scene/camera set");
+    const uint32_t rows = partition_rows(c->hdr.height, part);
+    // a partition that owns no band (height < band_rows * n_parts) has nothing to write and may pass a null buffer
+    if (!d_out_rgb && rows != 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: null output buffer");
+    if (depth < 0 || depth > RTC_MAX_DEPTH)
+        return fail(RTC_ERR_INVALID_ARG, "depth %d outside [0, %d]", depth, RTC_MAX_DEPTH);
+    const Partition q = resolve(part);
+    if (q.part >= q.n_parts) return fail(RTC_ERR_INVALID_ARG, "partition %u of %u", q.part, q.n_parts);
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    const Policy& P = c->policy;
+    const uint32_t width = c->hdr.width, height = c->hdr.height;
+    // ---- depth and kernel
+    // camera.rs:76 takes any depth; the kernels' frame stack (one suspended shade_hit per level, world.rs:62-86) holds
+    // RTC_STACK_DEPTH_BASE levels.  Deeper than that, the scene's kernel is compiled once more with a longer stack -- 16, 32,
+    // ... RTC_MAX_DEPTH levels of per-lane scratch -- on first use, and kept with the context.
+    hipFunction_t spec_fn = c->spec_fn;
+    if (depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) depth = RTC_STACK_DEPTH_BASE;
+    if (depth > RTC_STACK_DEPTH_BASE && rows > 0u) RTC_TRY(deep_kernel(c, depth, &spec_fn));
+    const bool shares = spec_fn && c->spec_shares;  // only kernels compiled for it share lanes
+    const uint32_t share_log2 = shares ? choose_share_log2(c->hdr, rows, P, progress == nullptr) : 0u;
+    // ---- the launch's shape, and the cached list that goes with it
+    LaunchPlan lp = plan_grid(width, rows, share_log2, spec_fn && c->spec_blocks_y, (uint32_t)P.blocks_y);
+    LaunchLists L;
+    // (block lists: not when RTC_AMD_SHARE_LOG2 pins one value for all; an area light's not for rtc_render_ex, whose rows leave in order)
+    const bool mesh_list = shares && !c->heavy_tiles.empty() && c->hdr.light_kind == RTC_LIGHT_POINT;
+    const bool area_list = shares && c->hdr.light_kind == RTC_LIGHT_RECT && share_log2 != 0u && P.block_feedback && progress == nullptr;
+    const bool list_words_fit = width <= 65532u && rows <= 131068u;  // (tile_word)
+    if ((mesh_list || area_list) && P.share_log2 < 0 && list_words_fit && rows > 0u) RTC_TRY(use_block_list(c, q, rows, depth, share_log2, mesh_list, stream, &lp, &L));
+    c->last_rows = rows;
+    c->last_pixels = traced_pixels(width, height, q);
+    if (wavefront_wanted(c, rows, depth)) {
+        bool used = false;
+        RTC_TRY(render_wavefront(c, depth, q, rows, d_out_rgb, out_u8, stream, slot, &used));
+        if (used) return RTC_OK;
     }
-    if (timed_list) HIP_TRY(hipEventRecord(timed_list->ev0, stream));
-    // instantiation: <= 4 / <= 8 objects get fully unrolled object loops (SIMPLE: all of them
-    // scale+translate-only, no cylinder); anything larger takes the generic loop
-    if (spec_fn) {
-        void* params[] = {&a};
-        HIP_TRY(hipModuleLaunchKernel(spec_fn, grid.x, grid.y, 1, block.x, 1, 1, 0, stream, params, nullptr));
-    } else if (c->hdr.n_trav) hipLaunchKernelGGL((render_kernel<-1, false>), grid, block, 0, stream, a);
-    else if (c->n_objects <= 4 && c->simple) hipLaunchKernelGGL((render_kernel<4, true>), grid, block, 0, stream, a);
-    else if (c->n_objects <= 4) hipLaunchKernelGGL((render_kernel<4, false>), grid, block, 0, stream, a);
-    else if (c->n_objects <= 8 && c->simple) hipLaunchKernelGGL((render_kernel<8, true>), grid, block, 0, stream, a);
-    else if (c->n_objects <= 8) hipLaunchKernelGGL((render_kernel<8, false>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((render_kernel<0, false>), grid, block, 0, stream, a);
-    if (tile_launch && n_fill_jobs) HIP_TRY(hipStreamWaitEvent(stream, c->ev_join, 0));
-    HIP_TRY(hipEventRecord(ev.second, stream));
-    if (timed_list) {
-        HIP_TRY(hipEventRecord(timed_list->ev1, stream));
-        timed_list->ev_recorded = true;
+    c->wf_last = false;
+    unsigned long long* const total = c->d_total + 3 * (size_t)slot;
+    if (rows == 0) {  // nothing to launch: the slot's counters read zero
+        HIP_TRY(hipMemsetAsync(total, 0, 3 * sizeof(unsigned long long), stream));
+        if (slot == 0) c->rendered = false;
+        return RTC_OK;
     }
-    if (copy_counts_to) HIP_TRY(hipMemcpyAsync(copy_counts_to, c->d_block_counts, n_blocks * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
+    RTC_TRY(settle_shape(c, q, rows, depth, share_log2, spec_fn, d_out_rgb, out_u8, progress, stream, &lp, &L));
+    // ---- workspaces (grow-only: first call / larger image only)
+    const size_t n_blocks = lp.n_workgroups() * 4;  // partial counts: one per wave
+    HIP_TRY(grow(&c->d_block_counts, &c->block_cap, n_blocks));
+    if (lp.n_chunks) {
+        const size_t words = lp.progress_words(PROGRESS_STRIDE);
+        HIP_TRY(grow(&c->d_progress, &c->progress_cap, words));
+        HIP_TRY(hipMemsetAsync(c->d_progress, 0, words * sizeof(uint32_t), stream));
+        progress->n_chunks = lp.n_chunks;
+        progress->chunk_rows = lp.chunk_block_rows * lp.block_h;
+    }
+    RenderArgs a = render_args(c, q, rows, depth, share_log2, d_out_rgb, out_u8, total, progress, lp, L);
+    // ---- warm up, time, launch, sum
+    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    HIP_TRY(next_event_pair(c, &ev));
+    RTC_TRY(warm_up(c, spec_fn, stream, a));
+    HIP_TRY(hipEventRecord(ev->first, stream));
+    const bool tile_fill = lp.shape == LaunchPlan::SCENE_TILES && L.scene_tiles->n_fill != 0;
+    if (tile_fill) RTC_TRY(fork_tile_fill(c, *L.scene_tiles, d_out_rgb, rows, out_u8, stream));
+    if (L.timed_list) HIP_TRY(hipEventRecord(L.timed_list->ev0, stream));
+    HIP_TRY(launch_render(c, spec_fn, dim3(lp.grid_x, lp.grid_y), stream, a));
+    if (tile_fill) HIP_TRY(hipStreamWaitEvent(stream, c->ev_join, 0));
+    HIP_TRY(hipEventRecord(ev->second, stream));
+    if (L.timed_list) {
+        HIP_TRY(hipEventRecord(L.timed_list->ev1, stream));
+        L.timed_list->ev_recorded = true;
+    }
+    if (L.copy_counts_to) HIP_TRY(hipMemcpyAsync(L.copy_counts_to, c->d_block_counts, n_blocks * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
     hipLaunchKernelGGL(sum_counts_kernel, dim3((uint32_t)((n_blocks + SUM_COUNTS_SLICE - 1) / SUM_COUNTS_SLICE)), dim3(1024), 0, stream,
-                       c->d_block_counts, (uint32_t)n_blocks, c->d_total + 3 * (size_t)slot, extra_rays);
+                       c->d_block_counts, (uint32_t)n_blocks, total, lp.extra_rays);
     HIP_TRY(hipGetLastError());
     c->rendered = true;
     return RTC_OK;
@@ -3113,11 +2909,7 @@ rtc_status rtc::ctx_collect(rtc_ctx* c, uint32_t n_slots, rtc_stats* out) {
         out->culled_shadow_rays += total[3 * s + 2];
     }
     double sum_ms = 0.0;
-    for (size_t i = 0; i < c->events_used; i++) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->events[i].first, c->events[i].second));
-        sum_ms += ms;
-    }
+    HIP_TRY(sum_event_ms(c, &sum_ms));
     out->kernel_ms = (float)sum_ms;
     out->launches = (uint32_t)c->events_used;
     out->flags = c->jit_note.empty() ? 0u : RTC_STATS_JIT_FALLBACK;
@@ -3138,6 +2930,43 @@ uint32_t rtc_diag_refine_block_list(const uint32_t* list, const uint32_t* ticks,
 }
 double rtc_diag_simulate_dispatch(const uint32_t* cost, uint32_t n, uint32_t slots) {
     return simulate_dispatch(std::vector<uint32_t>(cost, cost + n), slots);
+}
+// ... and rtc_launch_plan.h's arithmetic (tests/test_launch_plan.py).  The band walk: {y0, y1, local0} per band into `bands`
+// (the first min(n, cap) of them; -> n), `facts` = {partition_rows, traced_pixels, does global_row give every local row the
+// row the walk gave it}.
+uint32_t rtc_diag_band_walk(uint32_t height, uint32_t width, const rtc_partition* part, uint32_t* bands, uint32_t cap, uint64_t facts[3]) {
+    const Partition q = resolve(part);
+    uint32_t n = 0;
+    bool inverts = true;
+    for_each_band(height, q, [&](uint32_t y0, uint32_t y1, uint32_t local0) {
+        if (n < cap) bands[3 * n] = y0, bands[3 * n + 1] = y1, bands[3 * n + 2] = local0;
+        n++;
+        for (uint32_t y = y0; y < y1; y++) inverts = inverts && global_row(q, local0 + (y - y0)) == y;
+    });
+    facts[0] = partition_rows(height, part), facts[1] = traced_pixels(width, height, q), facts[2] = inverts ? 1u : 0u;
+    return n;
+}
+// The scene-tile list of a partition: counts = {tiles, fill runs}; -> traced pixels inside the listed tiles.
+uint64_t rtc_diag_scene_tiles(const uint8_t* mask, uint32_t mask_w, uint32_t mask_h, uint32_t width, uint32_t height, const rtc_partition* part,
+                              uint32_t* tiles, uint32_t* fill /* pairs */, uint32_t cap, uint32_t counts[2]) {
+    SceneTilePlan plan;
+    plan_scene_tiles(TileMask{mask, mask_w, mask_h}, width, height, resolve(part), &plan);
+    for (size_t i = 0; i < plan.tiles.size() && i < cap; i++) tiles[i] = plan.tiles[i];
+    for (size_t i = 0; i < plan.fill.size() && i < cap; i++) fill[2 * i] = plan.fill[i].x0_n, fill[2 * i + 1] = plan.fill[i].row;
+    counts[0] = (uint32_t)plan.tiles.size(), counts[1] = (uint32_t)plan.fill.size();
+    return plan.traced_pixels;
+}
+// A scene-rectangle launch of a partition: out = {grid_x, grid_y, blocks_y, block_x0, block_y0, fill_wg_rows, fill_rows, fill_period,
+// fill_rect[4]}; -> extra_rays.
+uint64_t rtc_diag_rect_launch(uint32_t width, uint32_t height, const rtc_partition* part, const uint32_t rect[4], uint32_t blocks_y, int32_t out_u8,
+                              uint32_t fill_wgs, uint32_t out[12]) {
+    const Partition q = resolve(part);
+    LaunchPlan lp;
+    plan_rect_launch(&lp, width, height, q, partition_rows(height, part), traced_pixels(width, height, q), rect, blocks_y, out_u8 != 0, fill_wgs);
+    const uint32_t v[12] = {lp.grid_x, lp.grid_y, lp.blocks_y, lp.block_x0, lp.block_y0, lp.fill_wg_rows, lp.fill_rows, lp.fill_period,
+                            lp.fill_rect[0], lp.fill_rect[1], lp.fill_rect[2], lp.fill_rect[3]};
+    std::memcpy(out, v, sizeof(v));
+    return lp.extra_rays;
 }
 
 rtc_status rtc_ctx_render(rtc_ctx* c, int32_t depth, const rtc_partition* part, void* d_out_rgb, void* stream) {
@@ -3177,20 +3006,12 @@ rtc_status rtc_ctx_render_hits(rtc_ctx* c, const rtc_partition* part, const rtc_
     if (c->policy.hits_tile == 3 || c->policy.hits_tile == 5 || c->policy.hits_tile == 6) a.tile_w_log2 = (uint32_t)c->policy.hits_tile;
     const uint32_t bw = a.tile_w_log2 == 3u ? 16u : 1u << a.tile_w_log2, bh = 256u / bw;
     const dim3 grid((c->hdr.width + bw - 1) / bw, (rows + bh - 1) / bh), block(256);
-    // the families rtc_ctx_render's ahead-of-time branch chooses from, by the same conditions (SIMPLE is a property of
-    // intensity_at alone: the geometry-only kernels exist once per object-loop family)
-#define RTC_LAUNCH_HITS(NOBJ, SIMPLE)                                                                       \
-    do {                                                                                                    \
-        if (light) hipLaunchKernelGGL((hits_kernel<NOBJ, SIMPLE, true>), grid, block, 0, stream, a);         \
-        else hipLaunchKernelGGL((hits_kernel<NOBJ, false, false>), grid, block, 0, stream, a);               \
-    } while (0)
-    if (c->hdr.n_trav) RTC_LAUNCH_HITS(-1, false);
-    else if (c->n_objects <= 4 && c->simple) RTC_LAUNCH_HITS(4, true);
-    else if (c->n_objects <= 4) RTC_LAUNCH_HITS(4, false);
-    else if (c->n_objects <= 8 && c->simple) RTC_LAUNCH_HITS(8, true);
-    else if (c->n_objects <= 8) RTC_LAUNCH_HITS(8, false);
-    else RTC_LAUNCH_HITS(0, false);
-#undef RTC_LAUNCH_HITS
+    // the families rtc_ctx_render's ahead-of-time branch chooses from (SIMPLE is a property of intensity_at alone: the
+    // geometry-only kernels exist once per object-loop family)
+    dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+        if (light) hipLaunchKernelGGL((hits_kernel<decltype(nobj)::value, decltype(simple)::value, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((hits_kernel<decltype(nobj)::value, false, false>), grid, block, 0, stream, a);
+    });
     HIP_TRY(hipGetLastError());
     return RTC_OK;
 }
@@ -3206,11 +3027,7 @@ rtc_status rtc_ctx_stats(rtc_ctx* c, rtc_stats* out) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(total, c->d_total, sizeof(total), hipMemcpyDeviceToHost));
     double sum_ms = 0.0;
-    for (size_t i = 0; i < c->events_used; i++) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->events[i].first, c->events[i].second));
-        sum_ms += ms;
-    }
+    HIP_TRY(sum_event_ms(c, &sum_ms));
     out->rays = total[0];
     out->shaded_hits = total[1];
     out->culled_shadow_rays = total[2];
@@ -3259,18 +3076,8 @@ rtc_status rtc_ctx_to_ppm(rtc_ctx* c, const void* d_rgb, uint32_t width, uint32_
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t words = (3u * width + 31u) / 32u;
-    if ((size_t)height + 1 > c->ppm_rows_cap) {
-        if (c->d_ppm_rows) HIP_TRY(hipFree(c->d_ppm_rows));
-        c->d_ppm_rows = nullptr;
-        HIP_TRY(hipMalloc(&c->d_ppm_rows, ((size_t)height + 1) * sizeof(unsigned long long)));
-        c->ppm_rows_cap = (size_t)height + 1;
-    }
-    if ((size_t)height * words > c->ppm_bits_cap) {
-        if (c->d_ppm_bits) HIP_TRY(hipFree(c->d_ppm_bits));
-        c->d_ppm_bits = nullptr;
-        HIP_TRY(hipMalloc(&c->d_ppm_bits, (size_t)height * words * sizeof(uint32_t)));
-        c->ppm_bits_cap = (size_t)height * words;
-    }
+    HIP_TRY(grow(&c->d_ppm_rows, &c->ppm_rows_cap, (size_t)height + 1));
+    HIP_TRY(grow(&c->d_ppm_bits, &c->ppm_bits_cap, (size_t)height * words));
     char head[40];
     const int head_len = snprintf(head, sizeof(head), "P3\n%u %u\n255\n", width, height);  // canvas.rs:60-63
     HIP_TRY(hipMemcpyAsync(d_text, head, (size_t)head_len, hipMemcpyHostToDevice, stream));
@@ -3397,21 +3204,10 @@ rtc_status rtc_intensity_at(const rtc_scene* scene, const float* points, uint32_
     HIP_TRY(d_out.alloc((size_t)n * 4));
     HIP_TRY(hipMemcpy(d_p.p, points, (size_t)n * 16, hipMemcpyHostToDevice));
     bool simple = !hdr.has_patterns && hdr.n_objects <= 4 && !hdr.n_trav;  // (as rtc_ctx_set_scene decides it for the render kernels)
-    for (uint32_t i = 0; simple && i < hdr.n_objects; i++) {
-        const uint32_t kind = (uint32_t)scene->objects[i].kind;
-        const float* m = scene->objects[i].inv;
-        const bool diag = m[1] == 0.0f && m[2] == 0.0f && m[4] == 0.0f && m[6] == 0.0f && m[8] == 0.0f && m[9] == 0.0f;
-        if (!diag || kind == RTC_CYLINDER || kind == RTC_CONE || kind == RTC_TRIANGLE) simple = false;
-    }
-    if (simple)
-        hipLaunchKernelGGL(intensity_at_kernel_simple, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr,
-                           soa_view((const float4*)soa.p, hdr, (const float*)tex.p), (const float4*)d_p.p, n, (float*)d_out.p);
-    else if (hdr.n_objects <= 4 && !hdr.n_trav)
-        hipLaunchKernelGGL(intensity_at_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr,
-                           soa_view((const float4*)soa.p, hdr, (const float*)tex.p), (const float4*)d_p.p, n, (float*)d_out.p);
-    else
-        hipLaunchKernelGGL(intensity_at_kernel_generic, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr,
-                           soa_view((const float4*)soa.p, hdr, (const float*)tex.p), (const float4*)d_p.p, n, (float*)d_out.p);
+    for (uint32_t i = 0; simple && i < hdr.n_objects; i++) simple = simple_shape(shape_bits(scene->objects[i]));
+    const auto kernel = simple ? intensity_at_kernel_simple : (hdr.n_objects <= 4 && !hdr.n_trav) ? intensity_at_kernel : intensity_at_kernel_generic;
+    hipLaunchKernelGGL(kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr, soa_view((const float4*)soa.p, hdr, (const float*)tex.p),
+                       (const float4*)d_p.p, n, (float*)d_out.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTC_OK;

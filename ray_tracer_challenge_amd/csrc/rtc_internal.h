@@ -47,16 +47,28 @@ inline Partition resolve(const rtc_partition* p) {
     }
     return r;
 }
-inline uint32_t partition_rows(uint32_t height, const rtc_partition* p) {
-    Partition q = resolve(p);
-    if (q.part >= q.n_parts) return 0;
-    uint32_t n_bands = (height + q.band_rows - 1) / q.band_rows;
-    uint32_t rows = 0;
+// The bands a partition owns -- bands part, part + n_parts, ... of band_rows rows -- in image order:
+// f(y0, y1, local0) with the band's global rows [y0, y1) and its first row among the partition's own, compact rows.
+// (A template, not std::function: this runs on the launch path of frames whose kernel takes 11 us.)
+template <class F>
+inline void for_each_band(uint32_t height, const Partition& q, F&& f) {
+    if (q.part >= q.n_parts) return;
+    const uint32_t n_bands = (height + q.band_rows - 1) / q.band_rows;
+    uint32_t local0 = 0;
     for (uint32_t b = q.part; b < n_bands; b += q.n_parts) {
-        uint32_t y0 = b * q.band_rows;
-        uint32_t y1 = y0 + q.band_rows < height ? y0 + q.band_rows : height;
-        rows += y1 - y0;
+        const uint32_t y0 = b * q.band_rows, y1 = y0 + q.band_rows < height ? y0 + q.band_rows : height;
+        f(y0, y1, local0);
+        local0 += y1 - y0;
     }
+}
+// ... and the inverse: the global row of one of the partition's compact rows
+inline uint32_t global_row(const Partition& q, uint32_t local_row) {
+    const uint32_t band = local_row / q.band_rows;
+    return (band * q.n_parts + q.part) * q.band_rows + (local_row - band * q.band_rows);
+}
+inline uint32_t partition_rows(uint32_t height, const rtc_partition* p) {
+    uint32_t rows = 0;
+    for_each_band(height, resolve(p), [&](uint32_t y0, uint32_t y1, uint32_t) { rows += y1 - y0; });
     return rows;
 }
 
@@ -75,7 +87,7 @@ constexpr uint32_t PROGRESS_MAX_CHUNKS = 64;
 // out_u8: the frame is stored as the bytes Canvas::to_ppm prints (scale_color, canvas.rs:39-43) -- `d_out` then holds
 // rows * width * 3 bytes -- instead of f32 RGB.
 rtc_status ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* part, void* d_out, void* stream, uint32_t slot,
-                           ProgressPlan* plan = nullptr, bool out_u8 = false);
+                           ProgressPlan* progress = nullptr, bool out_u8 = false);
 rtc_status ctx_collect(rtc_ctx* c, uint32_t n_slots, rtc_stats* out);
 // A context of the one-call seam (rtc_render_ex): a scene whose kernel is neither in memory nor in the disk cache is rendered by the
 // ahead-of-time kernels the first time this process sees it and compiled when it is rendered again (rtc_device.hip jit_get).

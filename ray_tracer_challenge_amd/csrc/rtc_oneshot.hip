@@ -250,7 +250,6 @@ rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32
     if (g_state.size() < D) g_state.resize(D);
     const uint32_t W = camera->width, H = camera->height;
     const size_t px_bytes = quantize ? 3 : 12, row_out = (size_t)W * px_bytes;
-    const uint32_t n_bands = (H + band_rows - 1) / band_rows;
 
     // is `out` page-locked host memory (then DMA goes straight into it)?
     bool out_pinned = false;
@@ -307,13 +306,10 @@ rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32
         RTC_TRY(rtc_ctx_set_scene(S.ctx, scene, camera));  // a no-op when this very scene is resident already
         rtc_partition part = {band_rows, D, k};
         sh.rows = rtc_partition_rows(H, &part);
-        size_t r = 0;
-        for (uint32_t b = k; b < n_bands; b += D) {
-            const uint32_t y0 = b * band_rows, y1 = std::min(H, y0 + band_rows);
+        for_each_band(H, resolve(&part), [&](uint32_t y0, uint32_t y1, uint32_t local0) {
             if (!sh.bands.empty() && sh.bands.back().y0 + sh.bands.back().rows == y0) sh.bands.back().rows += y1 - y0;  // (one device: one run)
-            else sh.bands.push_back({r, y0, y1 - y0});
-            r += y1 - y0;
-        }
+            else sh.bands.push_back({local0, y0, y1 - y0});
+        });
         RTC_TRY(grow_device(&S.d_out, &S.d_out_cap, std::max<size_t>(1, (size_t)sh.rows * row_out)));
         // chunks of about 4 MB of output, at most 24: the call ends one chunk's transfer after the kernel does, so the last
         // should be short (a 50 MB u8 frame: 6 chunks 1.46 ms, the copy of the last alone 0.46; 12 chunks: see bench.py

@@ -1,4 +1,4 @@
-"""Block lists made from the previous frame's wave times (rtc_device.hip refine_block_list; -m gpu).
+"""Block lists made from the previous frame's wave times (rtc_launch_plan.h refine_block_list; -m gpu).
 
 The first frame of a scene with divided meshes under a point light is rendered from a block list that knows three kinds of
 tile; that launch times its waves, and every later frame's list -- which tiles start first, how many lanes trace a pixel of

@@ -1,4 +1,4 @@
-"""The host side of the frame-to-frame feedback (rtc_device.hip refine_block_list, simulate_dispatch) -- no device needed.
+"""The host side of the frame-to-frame feedback (rtc_launch_plan.h refine_block_list, simulate_dispatch) -- no device needed.
 
 Whatever the wave times say, the list made from them must render every pixel of the partition exactly once: a block list is a
 tiling of the frame by blocks of 16 x 16, 16 x 8, 8 x 8, 8 x 4 or 4 x 4 pixels (1, 2, 4, 8, 16 lanes per pixel), one size per 16 x 16 tile.

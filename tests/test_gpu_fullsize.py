@@ -255,7 +255,7 @@ def test_demo_scenes_whole_frame_at_the_sizes_they_are_timed_at(torch, name, siz
     image = r.render(depth).cpu().numpy()
     st = r.stats()
     # ... and so do the later frames of the same scene, which is what the table times: block lists are made from the frames
-    # before (rtc_device.hip refine_block_list)
+    # before (rtc_launch_plan.h refine_block_list)
     for _ in range(3):
         later = r.render(depth).cpu().numpy()
     later_rays = r.stats()["rays"]

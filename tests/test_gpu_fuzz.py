@@ -189,7 +189,7 @@ def test_random_worlds_match_the_oracle(seed, monkeypatch):
         r = Renderer(world, camera, device=0)
         names.append(r.kernel_name)
         # a scene's first frame, and three of the later ones, whose blocks are scheduled -- and, with several lanes per pixel,
-        # re-cut -- by the frames before (rtc_device.hip refine_block_list, order_grid)
+        # re-cut -- by the frames before (rtc_launch_plan.h refine_block_list, rtc_device.hip order_grid)
         for frame in range(4):
             img = r.render(depth).cpu().numpy()
             H.assert_images_equal(img, exp, "seed %d (%s) frame %d" % (seed, r.kernel_name, frame))
