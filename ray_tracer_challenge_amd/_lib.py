@@ -205,7 +205,9 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
          "rtc_diag_scene_tiles": (C.c_uint64, [C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(rtc_partition),
                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
          "rtc_diag_rect_launch": (C.c_uint64, [C.c_uint32, C.c_uint32, C.POINTER(rtc_partition), C.POINTER(C.c_uint32), C.c_uint32, C.c_int32,
-                                               C.c_uint32, C.POINTER(C.c_uint32)])}
+                                               C.c_uint32, C.POINTER(C.c_uint32)]),
+         # rtc_scene_prep.h on the host: digests of what flatten packs and the text of plan_scene's choice (tests/test_scene_prep.py)
+         "rtc_diag_scene_plan": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)])}
 
 _lib = None
 _loaded = {}  # path -> CDLL

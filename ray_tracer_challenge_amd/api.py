@@ -823,6 +823,15 @@ class World:
         cs = self._c()
         L.check(L.lib().rtc_scene_validate(C.byref(cs.scene), C.byref(camera._cam) if camera is not None else None))
 
+    def scene_plan(self, camera=None):
+        """rtc_diag_scene_plan: what rtc_ctx_set_scene would pack and decide for this world and camera under the current
+        environment, without a GPU -> (digests of the header, the records, the texels and the tile masks; the plan's key=value
+        lines as a dict -- empty without a camera).  Raises RtcError where rtc_scene_validate would."""
+        cs = self._c()
+        text, digests = C.create_string_buffer(1 << 16), (C.c_uint64 * 4)()
+        L.check(L.lib().rtc_diag_scene_plan(C.byref(cs.scene), C.byref(camera._cam) if camera is not None else None, text, len(text), digests))
+        return tuple(digests), dict(line.split("=", 1) for line in text.value.decode().splitlines())
+
     def color_at(self, origins, directions, depth, device=0):
         """World::color_at for a batch of rays (world.rs:88-101); (n,4),(n,4) -> (n,3)."""
         o = np.ascontiguousarray(np.asarray(origins, dtype=f32).reshape(-1, 4))

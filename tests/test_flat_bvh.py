@@ -1,4 +1,4 @@
-"""The library's own bounding-volume hierarchy over FLAT worlds of many bounded objects (rtc_device.hip
+"""The library's own bounding-volume hierarchy over FLAT worlds of many bounded objects (rtc_scene_prep.h
 build_flat_bvh): unlike a GroupShape's box it is not part of the reference's semantics (world.rs:60-77 tests
 every object, in order), so it must never change a bit of the image, a ray count or a shaded-hit count.
 Checked against the oracle, which knows nothing of it, and against the same kernel family with it switched off."""
@@ -87,29 +87,38 @@ def test_coincident_objects_resolve_ties_by_list_order(monkeypatch):
     assert st_on["rays"] == rays == st_off["rays"]
 
 
+def _kernel_name(world, camera):
+    """The kernel a context picks for this scene -- and the one its plan names (rtc_diag_scene_plan; tests/test_scene_prep.py
+    asserts this test's expectations on the plan, without a device): the two cannot drift."""
+    name = Renderer(world, camera, device=0).kernel_name
+    plan = world.scene_plan(camera)[1]
+    assert name == (plan["spec_name"] if plan["compile_now"] == "1" else plan["family_name"]), (name, plan)
+    return name
+
+
 def test_flat_bvh_eligibility(monkeypatch):
     monkeypatch.setenv("RTC_AMD_BVH", "1")
     monkeypatch.setenv("RTC_AMD_SPECIALIZE", "0")
     world, camera = _cloud(7, 20)
-    assert Renderer(world, camera, device=0).kernel_name == "render_kernel<tree,bvh>"
+    assert _kernel_name(world, camera) == "render_kernel<tree,bvh>"
     monkeypatch.setenv("RTC_AMD_SPECIALIZE", "1")
-    assert Renderer(world, camera, device=0).kernel_name == "render_kernel_spec[tree,bvh]"      # spheres and cubes
+    assert _kernel_name(world, camera) == "render_kernel_spec[tree,bvh]"  # spheres and cubes
     balls = P.World([o for o in world.objects if o.kind == world.objects[0].kind] * 2, world.light)
-    assert Renderer(balls, camera, device=0).kernel_name.startswith("render_kernel_spec[tree,bvh;all 0x")
+    assert _kernel_name(balls, camera).startswith("render_kernel_spec[tree,bvh;all 0x")
     monkeypatch.setenv("RTC_AMD_SPECIALIZE", "0")
     few = P.World(world.objects[:15], world.light)                    # too few objects to pay
-    assert Renderer(few, camera, device=0).kernel_name.find("bvh") < 0
+    assert _kernel_name(few, camera).find("bvh") < 0
     floor = P.World(world.objects + [P.Plane()], world.light)         # unbounded object: ray origins unbounded
-    assert Renderer(floor, camera, device=0).kernel_name.find("bvh") < 0
+    assert _kernel_name(floor, camera).find("bvh") < 0
     tilted = P.World(list(world.objects), world.light)
     tilted.objects[3] = P.Sphere(P.chain(P.rotation_z(0.3), P.scaling(1, 2, 1)), world.objects[3].material)
-    assert Renderer(tilted, camera, device=0).kernel_name.find("bvh") < 0
+    assert _kernel_name(tilted, camera).find("bvh") < 0
     speck = P.World(list(world.objects), world.light)                 # a 0.01-radius sphere: > 100 radii from the camera
     speck.objects[5] = P.Sphere(P.scaling(0.01, 0.01, 0.01), world.objects[5].material)
-    assert Renderer(speck, camera, device=0).kernel_name.find("bvh") < 0
+    assert _kernel_name(speck, camera).find("bvh") < 0
     cyl = P.World(list(world.objects), world.light)
     cyl.objects[0] = P.Cylinder(P.identity_4x4(), world.objects[0].material, minimum_y=0.0, maximum_y=1.0)
-    assert Renderer(cyl, camera, device=0).kernel_name.find("bvh") < 0
+    assert _kernel_name(cyl, camera).find("bvh") < 0
 
 
 @pytest.mark.parametrize("size", [(1024, 1024), (2048, 1536)])

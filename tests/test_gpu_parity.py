@@ -549,7 +549,7 @@ def test_lanes_splitting_leaf_runs_change_nothing(name, size, variant, monkeypat
 @pytest.mark.parametrize("name", ["mesh", "here_be_dragons"])
 def test_nodes_at_a_frame_size_that_builds_them_by_default(name, monkeypatch):
     """Frames of more than 40 k waves are traced by two lanes per pixel in the mesh tiles and get the library's own nodes
-    over their long triangle runs by default (rtc_device.hip: clusters_pay).  The small frames above force them on and
+    over their long triangle runs by default (rtc_scene_prep.h: clusters_pay).  The small frames above force them on and
     compare with the oracle; here the default policy itself runs and is compared with the same frame without nodes."""
     from ray_tracer_challenge_amd.renderer import Renderer
     world, camera, depth = getattr(scenes, name)(2048, 1296)

@@ -331,7 +331,7 @@ def _small_tree_world(seed, area_light):
 @pytest.mark.parametrize("seed", range(10))
 @pytest.mark.parametrize("specialise", ["0", "1"])
 def test_small_trees_through_the_unrolled_kernels(seed, specialise, monkeypatch):
-    """Group boxes as gates (rtc_device.hip flatten / SceneHdr::gate_mask) against the oracle's recursive walk and
+    """Group boxes as gates (rtc_scene_prep.h flatten / SceneHdr::gate_mask) against the oracle's recursive walk and
     against the traversal kernel (RTC_AMD_GATES=0)."""
     from ray_tracer_challenge_amd.renderer import Renderer
     world, camera = _small_tree_world(seed, area_light=seed % 2 == 0)

@@ -1,4 +1,4 @@
-"""Two shortcuts for primary rays of fully bounded scenes (rtc_device.hip / render_body): the SCENE BOX -- a ray that
+"""Two shortcuts for primary rays of fully bounded scenes (rtc_scene_prep.h / render_body): the SCENE BOX -- a ray that
 misses the padded box around everything is black after one counted ray, without the exact normalisation and the walk --
 and the SCENE RECTANGLE -- where the pixels that can see anything (that box, and the near side of every top-level plane's
 horizon) lie within a rectangle smaller than the frame, only that rectangle's blocks are rendered, other workgroups of the

@@ -1,4 +1,4 @@
-"""Triangle pre-culling in the tree walks (rtc_kernel_core.h tri_precull, rtc_device.hip triangle_box): a cheap
+"""Triangle pre-culling in the tree walks (rtc_kernel_core.h tri_precull, rtc_scene_prep.h triangle_box): a cheap
 world-space test that skips the exact Moeller-Trumbore evaluation (triangle.rs:45-68) for rays that pass nowhere
 near a triangle.  It is not part of the reference's semantics, so it must agree with the exact f32 evaluation on
 EVERY ray -- including the ones where that evaluation is ill-conditioned and reports hits that are not there
