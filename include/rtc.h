@@ -296,6 +296,11 @@ rtc_status rtc_light_set_jitter_sequence(rtc_light* light, const float* values, 
 rtc_status rtc_camera_new(uint32_t width, uint32_t height, float field_of_view, const float transform[16],
                           rtc_camera* out);                                               /* camera.rs:23-56 */
 void rtc_ray_for_pixel(const rtc_camera* c, uint32_t x, uint32_t y, float origin[4], float direction[4]); /* camera.rs:60-74 */
+/* The fine camera of a supersampled frame (rtc_ctx_set_scene_ss): Camera::new(k W, k H, field_of_view, transform) for a camera
+ * of W x H pixels built by rtc_camera_new -- the same half_width, half_height and inverse transform, pixel_size =
+ * (half_width * 2) / (k W as f32).  k = 1, 2 or 4; any other k, or a fine frame beyond what a launch addresses (2^32 pixels:
+ * the pixel index is the jitter key; 2^17 rows), is RTC_ERR_INVALID_ARG with a message.  Host only. */
+rtc_status rtc_camera_supersampled(const rtc_camera* camera, uint32_t k, rtc_camera* fine);
 
 /* Runs the checks and the flattening rtc_ctx_set_scene performs (shape / pattern kinds, affine transforms, group
  * nesting, light and camera sanity), without touching a device: RTC_OK, or the status rtc_ctx_set_scene would
@@ -311,7 +316,8 @@ rtc_status rtc_scene_validate(const rtc_scene* scene, const rtc_camera* camera);
  * whole image on device `device`, copies it back.  out_rgb: caller-owned host
  * buffer of width*height*3 f32, row-major [y][x][rgb], fully written -- the
  * last row and last column stay black exactly as in the reference
- * (camera.rs:80-81).  stats may be NULL. */
+ * (camera.rs:80-81).  (A supersampled context, rtc_ctx_set_scene_ss, leaves the FINE frame's last row and column black:
+ * its output's last row and column are dimmed, not black.)  stats may be NULL. */
 rtc_status rtc_render(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, int32_t device,
                       float* out_rgb, rtc_stats* stats);
 
@@ -346,6 +352,25 @@ void rtc_ctx_destroy(rtc_ctx* ctx);
  * happens; with records that are resident and another camera (an animation's usual frame): nothing is uploaded; with a scene
  * of the same frame size: what the frames before measured stays the schedule's starting point. */
 rtc_status rtc_ctx_set_scene(rtc_ctx* ctx, const rtc_scene* scene, const rtc_camera* camera);
+/* Supersampled rendering: k x k rays per pixel of `output_camera` (W x H), reduced in the render kernel; k = 2 or 4 (k = 1 is
+ * rtc_ctx_set_scene; anything else, or a fine frame rtc_camera_supersampled refuses: RTC_ERR_INVALID_ARG, decided before any
+ * device call).  Afterwards rtc_ctx_render writes the W x H frame, by definition a fixed-order f32 box filter of the frame F that
+ * rtc_ctx_render produces for the fine camera rtc_camera_supersampled(output_camera, k) -- jitter keys from the fine pixel
+ * index y * k W + x, the reference's black last row and column at the FINE resolution (camera.rs:80-81), so the output's last
+ * row and column are dimmed, not black.  Output pixel (X, Y), per channel, in f32 without fused operations:
+ *   k = 2: ((F[2Y][2X] + F[2Y][2X+1]) + (F[2Y+1][2X] + F[2Y+1][2X+1])) * 0.25f
+ *   k = 4: per row r = (a0 + a1) + (a2 + a3), then ((r0 + r1) + (r2 + r3)) * 0.0625f
+ * Partitions count OUTPUT rows: rtc_partition{band_rows, ...} are bands of band_rows output rows, the buffer is
+ * rtc_partition_rows(H, part) x W x 3 f32.  rtc_stats: rays, shaded_hits and pixels are the fine frame's, rows the output
+ * rows written.  culled_shadow_rays counts the fine frame's rays too, but which shadow rays the light-cone cull answers depends
+ * on which lanes share a wave: it equals a plain render of the fine camera only where both launch one lane per pixel (the
+ * ahead-of-time kernels); a scene's own kernel, whose lanes per pixel are capped for k, may cull other rays -- never other
+ * colours, and `rays` counts culled rays as traced either way.  rtc_ctx_kernel_name / _id name the supersampling kernel ("ss_render_kernel...";
+ * "aot_ss<k>_..." or "spec_..." ids of their own).  The rules of rtc_ctx_set_scene hold: unchanged records are not uploaded,
+ * a scene of the same frame size and factor keeps the schedule.  A later rtc_ctx_set_scene leaves supersampled mode.
+ * rtc_ctx_render_hits on a supersampled context is RTC_ERR_UNSUPPORTED (a first hit per output pixel is not defined).
+ * rtc_render / rtc_render_ex (the one-call seam, its progress words and u8 frames) do not supersample. */
+rtc_status rtc_ctx_set_scene_ss(rtc_ctx* ctx, const rtc_scene* scene, const rtc_camera* output_camera, uint32_t k);
 /* Rows this partition produces (sum of its bands' heights). */
 uint32_t rtc_partition_rows(uint32_t height, const rtc_partition* part);
 /* Launches the render kernel on `stream` (a hipStream_t; NULL = default

@@ -144,6 +144,7 @@ SIGNATURES = {
                                       C.POINTER(rtc_light)]),
     "rtc_camera_new": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float, FP, C.POINTER(rtc_camera)]),
     "rtc_ray_for_pixel": (None, [C.POINTER(rtc_camera), C.c_uint32, C.c_uint32, FP, FP]),
+    "rtc_camera_supersampled": (C.c_int, [C.POINTER(rtc_camera), C.c_uint32, C.POINTER(rtc_camera)]),
     "rtc_render": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.c_int32, FP,
                              C.POINTER(rtc_stats)]),
     "rtc_render_ex": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.POINTER(rtc_opts), C.c_void_p,
@@ -155,6 +156,7 @@ SIGNATURES = {
     "rtc_ctx_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),
     "rtc_ctx_destroy": (None, [C.c_void_p]),
     "rtc_ctx_set_scene": (C.c_int, [C.c_void_p, C.POINTER(rtc_scene), C.POINTER(rtc_camera)]),
+    "rtc_ctx_set_scene_ss": (C.c_int, [C.c_void_p, C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_uint32]),
     "rtc_partition_rows": (C.c_uint32, [C.c_uint32, C.POINTER(rtc_partition)]),
     "rtc_ctx_render": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(rtc_partition), C.c_void_p, C.c_void_p]),
     "rtc_ctx_stats": (C.c_int, [C.c_void_p, C.POINTER(rtc_stats)]),
@@ -206,6 +208,10 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
          "rtc_diag_rect_launch": (C.c_uint64, [C.c_uint32, C.c_uint32, C.POINTER(rtc_partition), C.POINTER(C.c_uint32), C.c_uint32, C.c_int32,
                                                C.c_uint32, C.POINTER(C.c_uint32)]),
+         # supersampled frames: the lanes-per-pixel cap and a block list re-cut under it (tests/test_supersample_boundary.py)
+         "rtc_diag_ss_plan": (C.c_uint32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_double, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
+         "rtc_diag_ctx_share_log2": (C.c_uint32, [C.c_void_p]),
          # rtc_scene_prep.h on the host: digests of what flatten packs and the text of plan_scene's choice (tests/test_scene_prep.py)
          "rtc_diag_scene_plan": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)])}
 

@@ -943,6 +943,19 @@ class Camera:
     def transform_inverse(self):
         return np.array(list(self._cam.inv), dtype=f32).reshape(4, 4)
 
+    def supersampled(self, k):
+        """The fine camera of a supersampled frame (rtc_camera_supersampled): Camera::new(k * width, k * height, field_of_view,
+        transform), the camera whose frame Renderer(world, self, supersample=k) box-filters.  k: 1, 2 or 4."""
+        fine = L.rtc_camera()
+        L.check(L.lib().rtc_camera_supersampled(C.byref(self._cam), int(k), C.byref(fine)))
+        cam = Camera.__new__(Camera)
+        cam._cam = fine
+        cam.width, cam.height = int(fine.width), int(fine.height)
+        cam.field_of_view = self.field_of_view
+        cam.transform = self.transform.copy()
+        cam.last_stats = None
+        return cam
+
     def ray_for_pixel(self, x, y):
         o, d = np.zeros(4, dtype=f32), np.zeros(4, dtype=f32)
         L.lib().rtc_ray_for_pixel(C.byref(self._cam), int(x), int(y), _p(o), _p(d))

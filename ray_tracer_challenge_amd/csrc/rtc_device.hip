@@ -36,6 +36,7 @@
 #include "rtc_launch_plan.h"
 #include "rtc_kernel_core.h"
 #include "rtc_hits.h"
+#include "rtc_supersample.h"
 #include "rtc_wavefront.h"
 #include "rtc_scene_prep.h"
 
@@ -118,6 +119,9 @@ struct rtc_ctx {
     Policy policy;  // the environment's switches as they were when the context was created
     SceneHdr hdr;
     bool has_scene = false;
+    // Supersampling (rtc_ctx_set_scene_ss; rtc_supersample.h): 1, or k = 2 / 4 -- `hdr` is then the FINE camera's, and everything that
+    // plans, schedules and feeds back does so in fine space; only the canvas and rtc_stats.rows speak of the output frame
+    uint32_t ss_k = 1u;
     float4* d_soa = nullptr;
     size_t soa_cap = 0;  // float4 entries
     float* d_texels = nullptr;  // UVImage canvases (RGB f32), grow-only
@@ -198,6 +202,7 @@ struct rtc_ctx {
     size_t events_used = 0;
     bool rendered = false;
     uint32_t last_rows = 0;
+    uint32_t last_share_log2 = 0;  // lanes per pixel (log2) the last launch was planned with (rtc_diag_ctx_share_log2)
     uint64_t last_pixels = 0;
 };
 
@@ -312,9 +317,8 @@ bool read_file(const std::string& path, std::string* out) {
 // written by ray_tracer_challenge_amd/build.py before every compile (under hiprtc the header needs no other file).  A
 // deployment is librtc_amd.so alone -- no csrc/ or include/ beside it.  RTC_AMD_JIT_SOURCE=<path> (development) reads
 // the header from disk instead, so a kernel experiment needs no rebuild of the library.
-const char k_core_src[] =
+// (k_ss_src: rtc_supersample.h likewise, for a scene's supersampling kernel)
 #include "rtc_kernel_core_embed.inc"
-    ;
 
 std::string jit_cache_dir(const Policy& P) {  // RTC_AMD_JIT_CACHE=<dir>, or 0 / off to keep compiled kernels in memory only; default <lib dir>/jit_cache
     if (!P.jit_cache.empty()) return (P.jit_cache == "0" || P.jit_cache == "off") ? std::string() : P.jit_cache;
@@ -339,11 +343,23 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
         *id = it->second.id;
         return RTC_OK;
     }
+    // -DRTC_SPEC_SS=k: the scene's supersampling kernel -- rtc_supersample.h beside the core, its own entry point
+    bool ss = false;
+    for (const auto& d : defines) ss = ss || d.rfind("-DRTC_SPEC_SS=", 0) == 0;
+    const char* const entry = ss ? "ss_render_kernel_spec" : "render_kernel_spec";
     std::string core_file;
     const char* core = k_core_src;
     if (!P.jit_source.empty()) {  // development builds only (Policy)
         if (!read_file(P.jit_source, &core_file)) return fail(RTC_ERR_DEVICE, "scene specialisation: cannot read the kernel source %s", P.jit_source.c_str());
         core = core_file.c_str();
+    }
+    // (... and rtc_supersample.h from the same directory, when it is there: an experiment in either header needs no rebuild)
+    std::string ss_file;
+    const char* ss_src = k_ss_src;
+    if (ss && !P.jit_source.empty()) {
+        const size_t slash = P.jit_source.find_last_of('/');
+        const std::string beside = (slash == std::string::npos ? std::string() : P.jit_source.substr(0, slash + 1)) + "rtc_supersample.h";
+        if (read_file(beside, &ss_file)) ss_src = ss_file.c_str();
     }
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize"};
     for (const auto& d : defines) opts.push_back(d);
@@ -375,14 +391,16 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
     // profiles/r04_ab_compilers.txt).  Sharing the entry is what lets a profiled run measure the very code object a plain run
     // compiled -- profiles/run_profile.sh compiles first, plainly -- and the id below says which binary it was.)
     char name[64];
-    snprintf(name, sizeof(name), "spec_%016llx.hsaco", (unsigned long long)fnv1a(opt_text, fnv1a(core)));
+    uint64_t source_hash = fnv1a(opt_text, fnv1a(core));
+    if (ss) source_hash = fnv1a(ss_src, source_hash);  // (the plain kernels' names do not move)
+    snprintf(name, sizeof(name), "spec_%016llx.hsaco", (unsigned long long)source_hash);
     const std::string cache_dir = jit_cache_dir(P), cache_path = cache_dir + "/" + name;
     auto compile = [&](std::string* code) -> rtc_status {
         hiprtcProgram prog;
-        const char* src = "#include \"rtc_kernel_core.h\"\n";
-        const char* headers[] = {core};
-        const char* header_names[] = {"rtc_kernel_core.h"};
-        if (hiprtcCreateProgram(&prog, src, "rtc_scene_spec.hip", 1, headers, header_names) != HIPRTC_SUCCESS)
+        const char* src = ss ? "#include \"rtc_supersample.h\"\n" : "#include \"rtc_kernel_core.h\"\n";
+        const char* headers[] = {core, ss_src};
+        const char* header_names[] = {"rtc_kernel_core.h", "rtc_supersample.h"};
+        if (hiprtcCreateProgram(&prog, src, "rtc_scene_spec.hip", ss ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
             return fail(RTC_ERR_DEVICE, "hiprtcCreateProgram failed");
         std::vector<const char*> copts;
         for (const auto& o : opts) copts.push_back(o.c_str());
@@ -439,7 +457,7 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
     }
     JitModule m;
     hipError_t le = hipModuleLoadData(&m.mod, code.data());
-    if (le == hipSuccess) le = hipModuleGetFunction(&m.fn, m.mod, "render_kernel_spec");
+    if (le == hipSuccess) le = hipModuleGetFunction(&m.fn, m.mod, entry);
     if (le != hipSuccess && cached) {
         // a cached code object that does not load (truncated, or from another toolchain): drop it and compile once
         (void)hipGetLastError();
@@ -447,7 +465,7 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
         rtc_status st = compile(&code);
         if (st != RTC_OK) return st;
         le = hipModuleLoadData(&m.mod, code.data());
-        if (le == hipSuccess) le = hipModuleGetFunction(&m.fn, m.mod, "render_kernel_spec");
+        if (le == hipSuccess) le = hipModuleGetFunction(&m.fn, m.mod, entry);
     }
     if (le != hipSuccess) return fail(RTC_ERR_DEVICE, "scene specialisation: the compiled kernel does not load: %s", hipGetErrorString(le));
     // The id names the code object itself: "spec_<hash of source, options, compiler>.<checksum of the compiled code>".  The second
@@ -467,6 +485,12 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
 std::string aot_kernel_id() {
     char b[40];
     snprintf(b, sizeof(b), "aot_%016llx", (unsigned long long)fnv1a(k_core_src));
+    return b;
+}
+// ... and its supersampling kernels: the core's text and rtc_supersample.h's
+std::string aot_ss_kernel_id(uint32_t k) {
+    char b[48];
+    snprintf(b, sizeof(b), "aot_ss%u_%016llx", k, (unsigned long long)fnv1a(k_ss_src, fnv1a(k_core_src)));
     return b;
 }
 
@@ -638,7 +662,7 @@ static rtc_status recut_block_list(rtc_ctx* c, BlockList& bl, uint32_t rows) {
     const uint32_t* ticks = (const uint32_t*)staging;
     HIP_TRY(hipMemcpy(staging, bl.d_ticks, 4u * bl.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     refine_block_list(bl.host, ticks, c->hdr.width, rows, 0.85 * 4.0 * compute_units(c) * c->tree_waves, 0.01 * P.feedback_pct, 0.01 * P.feedback_down_pct,
-                      &refined, P.feedback_max_s, &throughput_ticks);
+                      &refined, P.feedback_max_s, &throughput_ticks, ss_max_share_log2(c->ss_k));
     if (P.jit_print) {
         size_t by_s[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};  // blocks by lanes per pixel (log2), before and after
         for (uint32_t t : bl.host.empty() ? refined : bl.host) by_s[0][tile_s(t)]++;
@@ -726,6 +750,20 @@ static rtc_status order_grid(rtc_ctx* c, BlockList& bl, uint32_t gx, uint32_t gy
 
 // One launch of the scene's render kernel: the scene-compiled one, or the context's ahead-of-time family.
 static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hipStream_t stream, RenderArgs& a) {
+    if (c->ss_k != 1u) {  // a supersampled context: `a` is the fine frame's, a.out the output canvas (rtc_supersample.h)
+        SsRenderArgs sa;
+        sa.fine = a;
+        sa.out_width = a.hdr.width / c->ss_k, sa.out_rows = a.rows / c->ss_k;
+        if (spec_fn) {
+            void* params[] = {&sa};
+            return hipModuleLaunchKernel(spec_fn, grid.x, grid.y, 1, 256, 1, 1, 0, stream, params, nullptr);
+        }
+        dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+            if (c->ss_k == 2u) hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
+            else hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, sa);
+        });
+        return hipGetLastError();
+    }
     if (spec_fn) {
         void* params[] = {&a};
         return hipModuleLaunchKernel(spec_fn, grid.x, grid.y, 1, 256, 1, 1, 0, stream, params, nullptr);
@@ -739,10 +777,11 @@ static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hi
 // The policy wanted a scene-compiled kernel and hiprtc did not deliver one.  RTC_AMD_SPECIALIZE=1: an error.  Default
 // policy: the ahead-of-time kernel renders the same image -- several times slower on area-light scenes -- so say so:
 // rtc_ctx_jit_status(), rtc_stats.flags, one line on stderr per process.
+static std::string ctx_aot_id(const rtc_ctx* c) { return c->ss_k != 1u ? aot_ss_kernel_id(c->ss_k) : aot_kernel_id(); }
 static rtc_status jit_failed(rtc_ctx* c, int policy, rtc_status jst) {
     c->spec_fn = nullptr;
     c->spec_shares = false;
-    c->kernel_id = aot_kernel_id();
+    c->kernel_id = ctx_aot_id(c);
     c->jit_note = rtc_last_error();
     if (policy == 1) {
         c->has_scene = false;
@@ -779,7 +818,11 @@ static rtc_status compile_deferred(rtc_ctx* c) {
     return RTC_OK;
 }
 
-rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera* camera) {
+}  // extern "C"
+
+// rtc_ctx_set_scene (k = 1), and rtc_ctx_set_scene_ss with the FINE camera (k = 2, 4; rtc_camera_supersampled has checked it):
+// a supersampled context flattens, plans, schedules and feeds back in fine space, with the code that exists.
+static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera* camera, uint32_t k) {
     if (!c) return fail(RTC_ERR_INVALID_ARG, "ctx is NULL");
     SceneHdr hdr;
     std::vector<float4> soa;
@@ -792,12 +835,13 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camer
     HIP_TRY(hipSetDevice(c->device));
     const bool resident = same_records(c, soa, texels);
     // the very scene that is resident (records, camera, light; the switches are the context's for life): nothing to replace
-    if (resident && std::memcmp(&hdr, &c->hdr, sizeof(hdr)) == 0) return c->jit_deferred ? compile_deferred(c) : RTC_OK;
+    if (resident && c->ss_k == k && std::memcmp(&hdr, &c->hdr, sizeof(hdr)) == 0) return c->jit_deferred ? compile_deferred(c) : RTC_OK;
     // Renders are asynchronous on caller streams (torch's are non-blocking: the null-stream copies below do not order
     // against them), and a render still in flight reads the records and the counters this call replaces.  Wait for
     // everything the context has launched before touching them.  (rtc.h: one stream at a time per context.)
     HIP_TRY(hipDeviceSynchronize());
-    const bool same_frame = c->has_scene && c->hdr.width == hdr.width && c->hdr.height == hdr.height;  // (block lists: below)
+    // (block lists: below; another factor is another kernel and other lane caps -- its lists start afresh)
+    const bool same_frame = c->has_scene && c->hdr.width == hdr.width && c->hdr.height == hdr.height && c->ss_k == k;
     // until the new scene is fully resident the context has none: a failed allocation below must not leave a stale
     // capacity beside a null pointer, nor a render path that believes the old scene is still there
     // (only the camera has moved -- an animation's usual frame: the records and texels that are resident stay)
@@ -816,6 +860,7 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camer
     }
     ScenePlan plan = plan_scene(P, hdr, soa, scene, camera, heavy_boxes, region);  // which kernel will render this scene
     c->hdr = hdr;
+    c->ss_k = k;
     c->n_objects = hdr.n_objects;
     c->has_scene = true;
     if (!resident) {
@@ -838,9 +883,30 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camer
     c->wf_pays = plan.wf_pays;
     c->wf_disabled = false;
     c->kernel_name = plan.family_name;
-    c->kernel_id = aot_kernel_id();
     c->spec_defs = plan.spec_defs;
     c->spec_name = plan.spec_name;
+    if (k != 1u) {
+        // Scene tiles, the scene rectangle and several blocks per workgroup address the canvas by fine pixels and are not carried
+        // over: such scenes are a plain grid here, where the scene-box early-out still applies.
+        c->scene_tile_mask.clear();
+        c->scene_rect[0] = c->scene_rect[1] = c->scene_rect[2] = c->scene_rect[3] = 0u;
+        c->spec_blocks_y = c->spec_rect = false;
+        c->wf_pays = false;
+        const std::string tag = std::to_string(k);
+        auto rename = [&](std::string* name) {  // render_kernel<...> -> ss_render_kernel<...;ss=k>, render_kernel_spec[...] likewise
+            if (name->empty()) return;
+            name->insert(0, "ss_");
+            name->insert(name->size() - 1, ";ss=" + tag);
+        };
+        rename(&c->kernel_name), rename(&c->spec_name);
+        if (!c->spec_defs.empty()) {
+            // (the supersampling body has neither the loop over blocks nor the rectangle's offsets: their options are off in its key)
+            for (auto& d : c->spec_defs)
+                if (d == "-DRTC_SPEC_BLOCKS_Y=1" || d == "-DRTC_SPEC_RECT=1") d.back() = '0';
+            c->spec_defs.push_back("-DRTC_SPEC_SS=" + tag);
+        }
+    }
+    c->kernel_id = ctx_aot_id(c);
     c->jit_deferred = false;
     if (plan.compile_now && !c->spec_defs.empty()) {
         rtc_status jst = jit_get(P, c->device, c->spec_defs, &c->spec_fn, &c->kernel_id, c->lazy_jit && P.specialise == 2);
@@ -849,13 +915,23 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camer
         } else if (c->spec_fn != nullptr) {
             c->kernel_name = c->spec_name;
         } else {
-            c->kernel_id = aot_kernel_id();  // (lazy: this frame by the ahead-of-time kernel, whose name kernel_name already holds)
+            c->kernel_id = ctx_aot_id(c);  // (lazy: this frame by the ahead-of-time kernel, whose name kernel_name already holds)
             c->jit_deferred = true;
         }
     }
     return RTC_OK;
 }
 
+extern "C" {
+rtc_status rtc_ctx_set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera* camera) { return set_scene(c, scene, camera, 1u); }
+
+// The argument checks come first, the context's among them: all of them are decided on the host, before any device call.
+rtc_status rtc_ctx_set_scene_ss(rtc_ctx* c, const rtc_scene* scene, const rtc_camera* output_camera, uint32_t k) {
+    if (k == 1u) return set_scene(c, scene, output_camera, 1u);
+    rtc_camera fine;
+    RTC_TRY(rtc_camera_supersampled(output_camera, k, &fine));
+    return set_scene(c, scene, &fine, k);
+}
 }  // extern "C"
 
 // The scene's kernel with a frame stack of at least `depth` levels (ctx_render_slot).  The options are the scene's own
@@ -1022,7 +1098,8 @@ static rtc_status use_block_list(rtc_ctx* c, const Partition& q, uint32_t rows, 
     if (it == c->block_lists.end()) {
         RTC_TRY(block_list_room(c));
         std::vector<uint32_t> host;
-        if (mesh_list) build_block_list(P.block_order, P.block_s, P.block_s_top, TileMask{c->heavy_tiles.data(), c->heavy_w, c->heavy_h}, c->hdr.width, share_log2, rows, q, &host);
+        if (mesh_list) build_block_list(P.block_order, P.block_s, P.block_s_top, TileMask{c->heavy_tiles.data(), c->heavy_w, c->heavy_h}, c->hdr.width, share_log2, rows, q, &host,
+                                        ss_max_share_log2(c->ss_k));
         else uniform_block_list(share_log2, c->hdr.width, rows, &host);
         BlockList bl;
         bl.n = host.size();
@@ -1137,7 +1214,7 @@ static rtc_status use_grid_feedback(rtc_ctx* c, const Partition& q, uint32_t row
 // process and queue, here: one workgroup of the same kernel over zero rows (it finds no pixel of its own and writes only
 // the counters the real launch overwrites), in front of the events that time the frame.
 static rtc_status warm_up(rtc_ctx* c, hipFunction_t spec_fn, hipStream_t stream, const RenderArgs& a) {
-    const auto key = std::make_pair(spec_fn ? (const void*)spec_fn : aot_family(c).key(), (const void*)stream);
+    const auto key = std::make_pair(spec_fn ? (const void*)spec_fn : aot_family(c).key(c->ss_k), (const void*)stream);
     if (c->warmed.count(key)) return RTC_OK;
     c->warmed.insert(key);
     RenderArgs w = a;
@@ -1197,7 +1274,7 @@ static RenderArgs render_args(const rtc_ctx* c, const Partition& q, uint32_t row
 // and continuation frames, not level-synchronous passes.  Kept as a verified alternative, not a default.
 static bool wavefront_wanted(const rtc_ctx* c, uint32_t rows, int32_t depth) {
     return c->hdr.n_trav != 0u && rows > 0u && depth >= 1 && depth <= RTC_STACK_DEPTH_BASE && (int)depth < (int)WF_MAX_LEVELS && !c->wf_disabled &&
-           (size_t)rows * c->hdr.width <= (16u << 20) && c->policy.wavefront == 1;
+           (size_t)rows * c->hdr.width <= (16u << 20) && c->policy.wavefront == 1 && c->ss_k == 1u;
 }
 
 // What a partition with rows that is not run from a mesh / area-light block list is launched as: scene tiles, else the scene
@@ -1240,6 +1317,17 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: null argument");
     if (slot >= CTX_TOTAL_SLOTS) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: counter slot %u", slot);
     if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: no scene/camera set");
+    // A supersampled context: the caller's partition counts OUTPUT rows -- bands of band_rows output rows are k * band_rows fine
+    // rows -- and from here on everything is the fine frame's: c->hdr, `rows`, the launch's shape, its lists and their feedback.
+    const uint32_t ss_k = c->ss_k;
+    rtc_partition fine_part;
+    if (ss_k != 1u) {
+        if (progress || out_u8) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render: a supersampled context renders f32 frames without progress words");
+        const Partition o = resolve(part);
+        if (o.band_rows > 0xffffffffu / ss_k) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: band_rows %u times the supersampling factor %u", o.band_rows, ss_k);
+        fine_part.band_rows = o.band_rows * ss_k, fine_part.n_parts = o.n_parts, fine_part.part = o.part;
+        part = &fine_part;
+    }
     const uint32_t rows = partition_rows(c->hdr.height, part);
     // a partition that owns no band (height < band_rows * n_parts) has nothing to write and may pass a null buffer
     if (!d_out_rgb && rows != 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: null output buffer");
@@ -1259,16 +1347,18 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     if (depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) depth = RTC_STACK_DEPTH_BASE;
     if (depth > RTC_STACK_DEPTH_BASE && rows > 0u) RTC_TRY(deep_kernel(c, depth, &spec_fn));
     const bool shares = spec_fn && c->spec_shares;  // only kernels compiled for it share lanes
-    const uint32_t share_log2 = shares ? choose_share_log2(c->hdr, rows, P, progress == nullptr) : 0u;
+    // (supersampled: capped so that a k x k group lies in one wave's tile, rtc_launch_plan.h)
+    const uint32_t share_log2 = shares ? std::min(choose_share_log2(c->hdr, rows, P, progress == nullptr), ss_max_share_log2(ss_k)) : 0u;
     // ---- the launch's shape, and the cached list that goes with it
-    LaunchPlan lp = plan_grid(width, rows, share_log2, spec_fn && c->spec_blocks_y, (uint32_t)P.blocks_y);
+    LaunchPlan lp = plan_grid(width, rows, share_log2, spec_fn && c->spec_blocks_y && ss_k == 1u, (uint32_t)P.blocks_y);
     LaunchLists L;
     // (block lists: not when RTC_AMD_SHARE_LOG2 pins one value for all; an area light's not for rtc_render_ex, whose rows leave in order)
     const bool mesh_list = shares && !c->heavy_tiles.empty() && c->hdr.light_kind == RTC_LIGHT_POINT;
     const bool area_list = shares && c->hdr.light_kind == RTC_LIGHT_RECT && share_log2 != 0u && P.block_feedback && progress == nullptr;
     const bool list_words_fit = width <= 65532u && rows <= 131068u;  // (tile_word)
     if ((mesh_list || area_list) && P.share_log2 < 0 && list_words_fit && rows > 0u) RTC_TRY(use_block_list(c, q, rows, depth, share_log2, mesh_list, stream, &lp, &L));
-    c->last_rows = rows;
+    c->last_rows = rows / ss_k;  // (rows written to the caller's buffer)
+    c->last_share_log2 = share_log2;
     c->last_pixels = traced_pixels(width, height, q);
     if (wavefront_wanted(c, rows, depth)) {
         bool used = false;
@@ -1395,6 +1485,23 @@ uint64_t rtc_diag_rect_launch(uint32_t width, uint32_t height, const rtc_partiti
     return lp.extra_rays;
 }
 
+// The lanes per pixel (log2) the context's last rtc_ctx_render was planned with -- a block list's entries may differ per tile, under
+// the same cap (tests/test_gpu_supersample.py: the cap in effect under a pinned RTC_AMD_SHARE_LOG2).
+uint32_t rtc_diag_ctx_share_log2(rtc_ctx* c) { return c ? c->last_share_log2 : 0u; }
+// Supersampled frames (tests/test_supersample_boundary.py): -> the lanes per pixel (log2) a frame of factor k is planned with when the
+// frame's own choice is share_log2; and, with a list, that list re-cut from `ticks` as a supersampled context re-cuts it (the
+// first min(*n_out, cap) blocks into `out`) -- list == NULL: the uniform list a lane-sharing frame starts from.
+uint32_t rtc_diag_ss_plan(uint32_t k, uint32_t share_log2, const uint32_t* list, const uint32_t* ticks, uint32_t n, uint32_t width, uint32_t rows,
+                          double wave_slots, uint32_t* out, uint32_t cap, uint32_t* n_out) {
+    const uint32_t max_s = ss_max_share_log2(k), s = std::min(share_log2, max_s);
+    std::vector<uint32_t> made;
+    if (list && ticks) refine_block_list(std::vector<uint32_t>(list, list + n), ticks, width, rows, wave_slots, 0.85, 0.40, &made, 4u, nullptr, max_s);
+    else uniform_block_list(s, width, rows, &made);
+    for (size_t i = 0; out && i < made.size() && i < cap; i++) out[i] = made[i];
+    if (n_out) *n_out = (uint32_t)made.size();
+    return s;
+}
+
 // A scene's preparation on the host, under the environment's policy (as rtc_scene_validate): flatten, then plan_scene.
 // digests: FNV-1a of the SceneHdr's bytes, of the records, of the texels, and of the plan's three tile masks together; text: the
 // plan, one key=value per line.  A null camera (the batched entry points' case): the first three digests only.
@@ -1440,6 +1547,7 @@ rtc_status rtc_ctx_render_hits(rtc_ctx* c, const rtc_partition* part, const rtc_
     HitPlanes planes;
     if (!hit_planes_view(d_out, &planes)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: no plane requested");
     if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: no scene/camera set");
+    if (c->ss_k != 1u) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_hits: the context is supersampled (%u x %u rays per pixel): a first hit per output pixel is not defined", c->ss_k, c->ss_k);
     const Partition q = resolve(part);
     if (q.part >= q.n_parts) return fail(RTC_ERR_INVALID_ARG, "partition %u of %u", q.part, q.n_parts);
     // (rtc_ctx_set_scene refuses RTC_JITTER_SEQUENCE lights: no resident scene has one)

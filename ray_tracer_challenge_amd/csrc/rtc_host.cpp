@@ -543,10 +543,9 @@ rtc_status rtc_light_set_jitter_sequence(rtc_light* light, const float* values, 
     return RTC_OK;
 }
 
-rtc_status rtc_camera_new(uint32_t width, uint32_t height, float fov, const float transform[16], rtc_camera* out) {
-    if (!out || !transform) return fail(RTC_ERR_INVALID_ARG, "rtc_camera_new: null argument");
-    if (width == 0 || height == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_camera_new: empty canvas");
-    // camera.rs:35-46; f32::tan -> libm tanf
+// camera.rs:35-46 for a canvas of width x height pixels; f32::tan -> libm tanf.  (One copy: rtc_camera_supersampled's fine camera is
+// Camera::new at k times the size, by this arithmetic.)
+static void camera_extents(uint32_t width, uint32_t height, float fov, rtc_camera* out) {
     float half_view = tanf(fov / 2.0f);
     float aspect = (float)width / (float)height;
     if (aspect >= 1.0f) {
@@ -559,8 +558,34 @@ rtc_status rtc_camera_new(uint32_t width, uint32_t height, float fov, const floa
     out->pixel_size = (out->half_width * 2.0f) / (float)width;
     out->width = width;
     out->height = height;
+}
+
+rtc_status rtc_camera_new(uint32_t width, uint32_t height, float fov, const float transform[16], rtc_camera* out) {
+    if (!out || !transform) return fail(RTC_ERR_INVALID_ARG, "rtc_camera_new: null argument");
+    if (width == 0 || height == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_camera_new: empty canvas");
+    camera_extents(width, height, fov, out);
     out->field_of_view = fov;
     inverse4(transform, out->inv);
+    return RTC_OK;
+}
+
+// The fine camera of a supersampled frame: Camera::new(k W, k H, field_of_view, transform).  W / H and k W / k H are the same real
+// number and both divisions are correctly rounded (k W and k H are exact in f32 whenever W and H are; beyond 2^24 both round, and the
+// comparison below decides), so the aspect branch and the half extents come out as the output camera's -- checked, not assumed.
+rtc_status rtc_camera_supersampled(const rtc_camera* camera, uint32_t k, rtc_camera* fine) {
+    if (!camera || !fine) return fail(RTC_ERR_INVALID_ARG, "rtc_camera_supersampled: null argument");
+    if (k != 1u && k != 2u && k != 4u) return fail(RTC_ERR_INVALID_ARG, "supersampling factor %u: 1, 2 or 4 rays per pixel side", k);
+    if (camera->width == 0 || camera->height == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_camera_supersampled: empty canvas");
+    // what the launch machinery addresses: the fine pixel index (the jitter key) in 32 bits, local rows below 2^17
+    const uint64_t fw = (uint64_t)camera->width * k, fh = (uint64_t)camera->height * k;
+    if (fw * fh > 0xffffffffull || fh >= (1ull << 17))
+        return fail(RTC_ERR_INVALID_ARG, "supersampling %u x %u by %u: the fine frame of %llu x %llu pixels exceeds 2^32 pixels or 2^17 rows", camera->width,
+                    camera->height, k, (unsigned long long)fw, (unsigned long long)fh);
+    rtc_camera f = *camera;
+    camera_extents((uint32_t)fw, (uint32_t)fh, camera->field_of_view, &f);  // camera.rs:35-46 for (k W, k H)
+    if (std::memcmp(&f.half_width, &camera->half_width, sizeof(float)) != 0 || std::memcmp(&f.half_height, &camera->half_height, sizeof(float)) != 0)
+        return fail(RTC_ERR_INVALID_ARG, "supersampling %u x %u by %u: the fine camera's half extents differ from the output camera's", camera->width, camera->height, k);
+    *fine = f;
     return RTC_OK;
 }
 

@@ -27,6 +27,11 @@ inline uint32_t tile_word(uint32_t s, uint32_t x0, uint32_t y0) { return (s & 3u
 inline uint32_t tile_s(uint32_t t) { return (t >> 30) | ((t >> 13) & 4u); }
 inline uint32_t tile_x0(uint32_t t) { return ((t >> 16) & 0x3fffu) << 2; }
 inline uint32_t tile_y0(uint32_t t) { return (t & 0x7fffu) << 2; }
+// Supersampled frames (rtc_supersample.h): the k x k fine pixels of an output pixel are added up across the lanes of ONE wave, so a
+// k x k group must lie in one wave's tile.  Wave tiles are 8 x 8, 8 x 4, 4 x 4, 4 x 2 and 2 x 2 pixels for s = 0 .. 4 lanes per
+// pixel (log2), at origins that are multiples of their size: any s serves k = 2, k = 4 needs s <= 2.  (Block origins are
+// multiples of 4 pixels: groups never straddle blocks.)  k = 1: no cap.
+inline uint32_t ss_max_share_log2(uint32_t k) { return k == 4u ? 2u : 4u; }
 // the blocks of the 16 x 16 tile at (x0, y0) at 2^s lanes per pixel, clipped to the partition
 inline void push_tile_blocks(std::vector<uint32_t>* out, uint32_t s, uint32_t x0, uint32_t y0, uint32_t width, uint32_t rows) {
     const uint32_t hbw = 16u >> (s >> 1), hbh = 16u >> ((s + 1u) >> 1);
@@ -38,7 +43,7 @@ inline void push_tile_blocks(std::vector<uint32_t>* out, uint32_t s, uint32_t x0
 // them, whole, one lane per pixel.
 // block_order, block_s, block_s_top: the policy's switches of those names.
 inline void build_block_list(bool block_order, int block_s, int block_s_top, const TileMask& T, uint32_t width, uint32_t mesh_share_log2, uint32_t rows,
-                             const Partition& q, std::vector<uint32_t>* out) {
+                             const Partition& q, std::vector<uint32_t>* out, uint32_t cap_s = 4u /* ss_max_share_log2 */) {
     out->clear();
     std::vector<uint32_t> light;
     uint32_t hs = mesh_share_log2;  // lanes per pixel (log2) in the mesh tiles; RTC_AMD_BLOCK_S=0..3: development
@@ -52,6 +57,7 @@ inline void build_block_list(bool block_order, int block_s, int block_s_top, con
     if (hs == 1u && ((uint64_t)width * rows + 63u) / 64u > 60000u) hs = 0u;
     if (block_s >= 0) hs = hs_top = (uint32_t)block_s;
     if (block_s_top >= 0) hs_top = (uint32_t)block_s_top;
+    hs = std::min(hs, cap_s), hs_top = std::min(hs_top, cap_s);
     for (uint32_t rank = 3u; rank >= 1u; rank--) {
         const uint32_t s = rank == 3u ? hs_top : hs;
         for (uint32_t yl0 = 0; yl0 < rows; yl0 += 16u) {
@@ -77,7 +83,8 @@ inline void build_block_list(bool block_order, int block_s, int block_s_top, con
 // longest wave.  Which lanes trace a pixel and when changes nothing about its value (tests/test_gpu_fullsize.py compares first
 // and later frames with the oracle).
 inline void refine_block_list(const std::vector<uint32_t>& list, const uint32_t* ticks /* [4 list.size()] */, uint32_t width, uint32_t rows, double wave_slots,
-                              double threshold, double down, std::vector<uint32_t>* out, uint32_t max_s = 4u, double* throughput_ticks = nullptr) {
+                              double threshold, double down, std::vector<uint32_t>* out, uint32_t max_s = 4u, double* throughput_ticks = nullptr,
+                              uint32_t cap_s = 4u /* ss_max_share_log2: entries above it come back capped */) {
     struct Tile {
         uint32_t x0, y0, s;
         uint64_t longest = 0;
@@ -94,7 +101,7 @@ inline void refine_block_list(const std::vector<uint32_t>& list, const uint32_t*
         if (slot < 0) {
             slot = (int32_t)tiles.size();
             Tile n;
-            n.x0 = x0 & ~15u, n.y0 = y0 & ~15u, n.s = tile_s(t);
+            n.x0 = x0 & ~15u, n.y0 = y0 & ~15u, n.s = std::min(tile_s(t), cap_s);
             tiles.push_back(n);
         }
         Tile& tile = tiles[(size_t)slot];
@@ -106,7 +113,7 @@ inline void refine_block_list(const std::vector<uint32_t>& list, const uint32_t*
     if (throughput_ticks) *throughput_ticks = throughput;
     for (Tile& t : tiles) {
         t.predicted = (double)t.longest;
-        while (t.s < max_s && t.predicted > threshold * throughput) t.s++, t.predicted *= 0.7;  // (up to sixteen lanes per pixel)
+        while (t.s < std::min(max_s, cap_s) && t.predicted > threshold * throughput) t.s++, t.predicted *= 0.7;  // (up to sixteen lanes per pixel)
         while (t.s > 0u && t.predicted / 0.7 < down * throughput) t.s--, t.predicted /= 0.7;
     }
     // the tiles by predicted longest wave, longest first, equal ones in list order: a radix sort of the (non-negative) doubles' bit

@@ -1324,7 +1324,8 @@ inline rtc_status flatten(const Policy& P, const rtc_scene* scene, const rtc_cam
 struct KernelFamily {
     int nobj;  // -1, 4, 8, 0
     bool simple;
-    const void* key() const { return (const void*)(uintptr_t)(0x1000 + 2 * (nobj + 1) + (simple ? 1 : 0)); }  // (no code object's address)
+    // (no code object's address; ss_k: the supersampling instantiations of the family, rtc_supersample.h, are kernels of their own)
+    const void* key(uint32_t ss_k = 1u) const { return (const void*)(uintptr_t)(0x1000 + 0x100 * ss_k + 2 * (nobj + 1) + (simple ? 1 : 0)); }
     std::string name(const char* tree_how = "tree") const {
         if (nobj < 0) return std::string("render_kernel<") + tree_how + ">";
         return "render_kernel<" + std::to_string(nobj) + (simple ? ",simple>" : ",general>");

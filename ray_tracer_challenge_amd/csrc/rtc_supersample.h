@@ -1,0 +1,179 @@
+// rtc_supersample.h -- supersampled rendering (rtc_ctx_set_scene_ss): K x K rays per output pixel, reduced in the kernel.
+//
+// By definition the supersampled frame is a fixed-order f32 box filter of the frame the render path produces for the FINE
+// camera (Camera::new(K W, K H, fov, transform), camera.rs:23-56): output pixel (X, Y) is a pairwise tree over its K x K block
+// of that frame, along x first, then along y, times 1 / K^2 -- see include/rtc.h.  The K x K samples of an output pixel sit
+// in neighbouring lanes of one wave's tile, so the fine frame never exists in memory: every lane traces its fine pixel as
+// render_body does, an xor-butterfly across the lanes adds the block up (IEEE addition is commutative: every lane of the
+// block ends with the same bits), and one lane per output pixel stores.
+//
+// Included by rtc_device.hip after rtc_kernel_core.h (ahead-of-time instantiations) and handed to hiprtc beside it
+// (-DRTC_SPEC_SS=K: ss_render_kernel_spec).  As rtc_hits.h: every expression below is either one of the core's device
+// functions or restates a line of render_body with the same operations in the same order -- block and lane placement,
+// ray_for_pixel, the scene-box early-out, the counter epilogue.  The core itself is not touched: its text is hashed into the
+// kernel ids.  Not restated, because the host never asks a supersampled launch for them: scene rectangle launches and their
+// zero-filling workgroups, several blocks per workgroup, progress words, the u8 canvas.
+#ifndef RTC_SUPERSAMPLE_H
+#define RTC_SUPERSAMPLE_H
+
+#include "rtc_kernel_core.h"
+
+namespace rtc {
+
+// The fine frame's RenderArgs -- its SceneHdr is the fine camera's, rows / band_rows count fine rows, tiles / share_log2 /
+// swizzle / wave_ticks / block_counts are what render_body takes -- except that `out` is the OUTPUT canvas:
+// [out_rows][out_width][3] f32, out_width = hdr.width / K, out_rows = rows / K.
+struct SsRenderArgs {
+    RenderArgs fine;
+    uint32_t out_width, out_rows;
+};
+
+// How a lane reads another lane's value.  With lanes-per-pixel a run-time value (the lane-sharing kernels) the masks are run-time
+// shifts: __shfl_xor (ds_bpermute_b32) takes any mask.
+DI float ss_xor_lane(float v, uint32_t mask) { return __shfl_xor(v, (int)mask, 64); }
+// With one lane per pixel the masks are 1, 2, 8 and 16: the first three are DPP controls, folded into the v_add_f32 itself --
+// quad_perm:[1,0,3,2], quad_perm:[2,3,0,1], row_ror:8 (a rotation by 8 within a row of 16 lanes is the xor) -- and the fourth,
+// which crosses rows of 16, is ds_swizzle_b32 in bit mode (and 0x1f, or 0, xor 0x10).  Measured against ds_bpermute:
+// profiles/supersample_xlane_ab.txt.
+template <int CTRL>
+DI float ss_dpp(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)); }
+DI float ss_swizzle_xor16(float v) { return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x401f)); }
+
+// One channel of the K x K block this lane's fine pixel belongs to, in the contract's order: pixel slots q ^ 1 (and q ^ 2)
+// along x, then q ^ tile width (and twice it) along y, each shifted by the wave's lanes-per-pixel.  Every lane of the wave
+// takes part; the K^2 lanes of a block (times 2^sl: a pixel's lanes hold the same bits) all end with the block's value.
+template <int K>
+DI float ss_reduce(float v, uint32_t sl, uint32_t tw_log2) {
+    static_assert(K == 2 || K == 4, "supersampling factor");
+    if (!Counters::SHARE_LANES) {  // sl = 0, an 8 x 8 tile: slots are lanes, the steps are lanes ^ 1, 2, 8, 16
+        v = v + ss_dpp<0xB1>(v);
+        if constexpr (K == 4) v = v + ss_dpp<0x4E>(v);
+        v = v + ss_dpp<0x128>(v);
+        if constexpr (K == 4) v = v + ss_swizzle_xor16(v);
+        return v * (1.0f / (float)(K * K));
+    }
+    const uint32_t sx = 1u << sl, sy = 1u << (sl + tw_log2);
+    v = v + ss_xor_lane(v, sx);
+    if constexpr (K == 4) v = v + ss_xor_lane(v, 2u * sx);
+    v = v + ss_xor_lane(v, sy);
+    if constexpr (K == 4) v = v + ss_xor_lane(v, 2u * sy);
+    return v * (1.0f / (float)(K * K));  // 0.25f / 0.0625f: exact constants
+}
+
+template <int NOBJ, bool SIMPLE, int K>
+DI void ss_render_body(const SsRenderArgs& SA) {
+    const RenderArgs& A = SA.fine;
+    const SceneHdr& H = A.hdr;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // Where this lane's fine pixel is: render_body's `where`, regular grid (swizzled or not) or block list
+    uint32_t sl = Counters::SHARE_LANES ? A.share_log2 : 0u;  // lanes per pixel (log2)
+    uint32_t bx0, by0;                                         // fine pixel origin of this workgroup's block
+    if (A.tiles != nullptr) {
+        const uint32_t t = A.tiles[blockIdx.x];  // wave-uniform: a scalar load
+        if (Counters::SHARE_LANES) sl = (t >> 30) | ((t >> 13) & 4u);
+        bx0 = ((t >> 16) & 0x3fffu) << 2;
+        by0 = (t & 0x7fffu) << 2;
+    } else {
+        uint32_t gx = blockIdx.x, gy = blockIdx.y;
+        if (A.swizzle != 0u) {  // (RenderArgs::swizzle)
+            const uint32_t j = (gy & 3u) * gridDim.x + gx, r = j & 7u;
+            gy = (gy & ~3u) + (r >> 1);
+            gx = 2u * (j >> 3) + (r & 1u);
+        }
+        bx0 = gx << (4u - (sl >> 1));
+        by0 = gy << (4u - ((sl + 1u) >> 1));
+    }
+    const uint32_t q = lane >> sl;  // q: the fine pixel's slot in the wave's tile
+    const uint32_t tw_log2 = 3u - (sl >> 1), th_log2 = 3u - ((sl + 1u) >> 1);
+    const uint32_t qx = q & ((1u << tw_log2) - 1u), qy = q >> tw_log2;
+    const uint32_t x = bx0 + ((wave & 1u) << tw_log2) + qx;
+    const uint32_t yl = by0 + ((wave >> 1) << th_log2) + qy;
+    Counters cnt = {0u, 0u, sl};
+    const bool timed = Counters::SHARE_LANES && A.wave_ticks != nullptr;  // wave-uniform
+    uint32_t ticks0 = 0u;
+    if (timed) ticks0 = (uint32_t)wall_clock64();
+    __shared__ float stash_lds[LDS_SLOTS * 256];
+    const LaneStash stash = {stash_lds + threadIdx.x, 256u};
+    // A lane outside the fine frame contributes zero.  Such lanes only ever form whole K x K blocks: the fine width, the fine
+    // rows of a partition and every band are multiples of K, and so is every tile's origin.
+    V3 col = v3(0.0f, 0.0f, 0.0f);
+    if (x < H.width && yl < A.rows) {
+        // compact local row -> global row of the fine image
+        const uint32_t band = yl / A.band_rows;
+        const uint32_t y = (band * A.n_parts + A.part) * A.band_rows + (yl - band * A.band_rows);
+        // camera.rs:80-81 at the fine resolution: the fine frame's last row and column stay black, so the output's are dimmed
+        if (x < H.width - 1u && y < H.height - 1u) {
+            // ray_for_pixel, camera.rs:60-74
+            float x_offset = ((float)x + 0.5f) * H.pixel_size;
+            float y_offset = ((float)y + 0.5f) * H.pixel_size;
+            float world_x = H.half_w - x_offset;
+            float world_y = H.half_h - y_offset;
+            const float* c = H.cam;
+            V3 pixel = {c[0] * world_x + c[1] * world_y + c[2] * -1.0f + c[3],
+                        c[4] * world_x + c[5] * world_y + c[6] * -1.0f + c[7],
+                        c[8] * world_x + c[9] * world_y + c[10] * -1.0f + c[11]};
+            V3 origin = v3(H.cam_origin[0], H.cam_origin[1], H.cam_origin[2]);
+            // the scene-box early-out of render_body
+            bool sees_nothing = false;
+            if (H.has_scene_box) {
+                const V3 du = pixel - origin;
+                const V3 iu = v3(__builtin_amdgcn_rcpf(du.x), __builtin_amdgcn_rcpf(du.y), __builtin_amdgcn_rcpf(du.z));
+                float tmin;
+                sees_nothing = !aabb_hit(origin, iu, make_float4(H.scene_box[0], H.scene_box[1], H.scene_box[2], 0.0f),
+                                         make_float4(H.scene_box[3], H.scene_box[4], H.scene_box[5], 0.0f), tmin);
+            }
+            if (sees_nothing) {
+                cnt.rays += cnt.lead();
+            } else {
+                V3 direction = norm3(pixel - origin);
+                col = color_at<NOBJ, SIMPLE>(H, A.soa, origin, direction, A.depth, y * H.width + x, cnt, stash);  // jitter key: the FINE pixel index
+            }
+        }
+    }
+    // The reduction, after the divergent region: every lane of the wave takes part.  No LDS round trip and no workgroup
+    // barrier -- a finished wave must be able to leave (render_body's epilogue says why).
+    col.x = ss_reduce<K>(col.x, sl, tw_log2);
+    col.y = ss_reduce<K>(col.y, sl, tw_log2);
+    col.z = ss_reduce<K>(col.z, sl, tw_log2);
+    // One lane per output pixel stores: the block's first slot, the lead lane of a pixel's lanes.  Three dword stores, 1 / K^2 of
+    // the fine frame's.
+    if (cnt.lead() && (qx & (uint32_t)(K - 1)) == 0u && (qy & (uint32_t)(K - 1)) == 0u) {
+        const uint32_t ox = x / (uint32_t)K, oy = yl / (uint32_t)K;
+        if (ox < SA.out_width && oy < SA.out_rows) {
+            float* dst = A.out + ((size_t)oy * SA.out_width + ox) * 3;
+            dst[0] = col.x;
+            dst[1] = col.y;
+            dst[2] = col.z;
+        }
+    }
+    // work statistics: wave reduce, then one partial per wave (render_body's epilogue)
+    uint32_t rays = cnt.rays, shaded = cnt.shaded_count(), culled = cnt.culled_count();
+    for (int off = 32; off > 0; off >>= 1) {
+        rays += __shfl_down(rays, off, 64);
+        shaded += __shfl_down(shaded, off, 64);
+        culled += __shfl_down(culled, off, 64);
+    }
+    const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4u;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 3) A.total[threadIdx.x] = 0ull;  // for sum_counts_kernel's atomics
+    if (lane == 0) A.block_counts[slot + wave] = make_uint4(rays, shaded, culled, 0u);
+    if (timed && lane == 0) A.wave_ticks[slot + wave] = (uint32_t)wall_clock64() - ticks0;
+}
+
+#ifdef RTC_SPEC_LIST
+#ifdef RTC_SPEC_SS
+}  // namespace rtc
+// The supersampling kernel of a scene-specialised (hiprtc) build.
+extern "C" __global__ __launch_bounds__(256, RTC_WAVES_PER_SIMD) void ss_render_kernel_spec(rtc::SsRenderArgs A) {
+    rtc::ss_render_body<RTC_SPEC_NOBJ, RTC_SPEC_SIMPLE != 0, RTC_SPEC_SS>(A);
+}
+namespace rtc {
+#endif
+#else
+template <int NOBJ, bool SIMPLE, int K>
+__global__ __launch_bounds__(256, RTC_WAVES_PER_SIMD) void ss_render_kernel(SsRenderArgs A) {
+    ss_render_body<NOBJ, SIMPLE, K>(A);
+}
+#endif
+
+}  // namespace rtc
+#endif  // RTC_SUPERSAMPLE_H

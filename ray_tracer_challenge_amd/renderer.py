@@ -13,7 +13,10 @@ from . import _lib as L
 
 
 class Renderer:
-    def __init__(self, world, camera, device=None):
+    """supersample = k (1, 2 or 4): k x k rays per pixel of `camera`, reduced in the render kernel (rtc_ctx_set_scene_ss).
+    width / height, alloc() and rows() speak of the output frame -- `camera`'s -- whatever k is."""
+
+    def __init__(self, world, camera, device=None, supersample=1):
         if not torch.cuda.is_available():
             raise L.RtcError(L.RTC_ERR_NO_DEVICE, "no GPU visible to torch; the render path has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
@@ -22,21 +25,27 @@ class Renderer:
         self._lib = L.lib()  # the library that owns this context (tests load a second one beside it: _lib.use_library)
         L.check(self._lib.rtc_ctx_create(self.device.index, C.byref(self._ctx)))
         self._keep = None
-        self.set_scene(world, camera)
+        self.supersample = 1
+        self.set_scene(world, camera, supersample=supersample)
 
-    def set_scene(self, world, camera):
-        cs = world._c()
+    def _set(self, cs, camera, k):
+        if k == 1:
+            L.check(self._lib.rtc_ctx_set_scene(self._ctx, C.byref(cs.scene), C.byref(camera._cam)), self._lib)
+        else:
+            L.check(self._lib.rtc_ctx_set_scene_ss(self._ctx, C.byref(cs.scene), C.byref(camera._cam), k), self._lib)
         self._keep = (cs, camera)
-        L.check(self._lib.rtc_ctx_set_scene(self._ctx, C.byref(cs.scene), C.byref(camera._cam)))
+        self.supersample = k
         self.width, self.height = camera.width, camera.height
+
+    def set_scene(self, world, camera, supersample=1):
+        """supersample=1 (the default) leaves supersampled mode."""
+        self._set(world._c(), camera, int(supersample))
 
     def set_camera(self, camera):
         """Another camera on the world that is resident (an animation's usual frame): the world is not flattened again on the
-        Python side, and the library, finding the records unchanged, uploads none of them."""
-        cs = self._keep[0]
-        self._keep = (cs, camera)
-        L.check(self._lib.rtc_ctx_set_scene(self._ctx, C.byref(cs.scene), C.byref(camera._cam)))
-        self.width, self.height = camera.width, camera.height
+        Python side, and the library, finding the records unchanged, uploads none of them.
+        The supersampling factor stays."""
+        self._set(self._keep[0], camera, self.supersample)
 
     def close(self):
         if self._ctx:
