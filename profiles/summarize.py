@@ -23,7 +23,8 @@ shutil.copy(stats, os.path.join(here, "%s_kernel_stats.csv" % tag))
 agg, meta = collections.defaultdict(list), {}
 for f in glob.glob(os.path.join(src, "pmc_*", "*", "*_counter_collection.csv")):
     for r in csv.DictReader(open(f)):
-        if "render_kernel" in r["Kernel_Name"]:
+        # (the one-workgroup warm-up launch is a render_kernel dispatch too -- see kernel_trace below: frames only)
+        if "render_kernel" in r["Kernel_Name"] and int(r["Grid_Size"]) > 256:
             agg[r["Counter_Name"]].append(float(r["Counter_Value"]))
             meta = {"kernel": r["Kernel_Name"], "grid": r["Grid_Size"], "workgroup": r["Workgroup_Size"],
                     "vgpr": r["VGPR_Count"], "sgpr": r["SGPR_Count"], "scratch_bytes_per_lane": r["Scratch_Size"]}

@@ -6,9 +6,9 @@
 // light = world.light.intensity_at(comps.over_point, world) (world.rs:75) with the jitter key (pixel index, path 1) -- the
 // key color_at gives a pixel's primary hit.
 //
-// Ahead-of-time only, included by rtc_device.hip after rtc_kernel_core.h: every expression below is either one of the
-// core's device functions or restates a line of color_at (rtc_kernel_core.h) with the same operations in the same order, so
-// the planes hold the bits the render used.  The core itself is not touched: its text is hashed into the kernel ids.
+// Ahead-of-time only, included by rtc_device.hip after rtc_kernel_core.h.  A pixel's ray is the core's (image_row,
+// primary_ray: what render_body calls); first_hit below is either one of the core's device functions or restates a line of
+// color_at (rtc_kernel_core.h) with the same operations in the same order, so the planes hold the bits the render used.
 #ifndef RTC_HITS_H
 #define RTC_HITS_H
 
@@ -139,7 +139,7 @@ struct HitsArgs {
 #ifndef RTC_HITS_LIGHT_WAVES
 #define RTC_HITS_LIGHT_WAVES 4
 #endif
-// rtc_ctx_render_hits: one lane per pixel, render_body's ray_for_pixel arithmetic and band -> row mapping.
+// rtc_ctx_render_hits: one lane per pixel, render_body's primary ray (image_row, primary_ray).
 template <int NOBJ, bool SIMPLE, bool LIGHT>
 __global__ __launch_bounds__(256, LIGHT ? RTC_HITS_LIGHT_WAVES : 1) void hits_kernel(HitsArgs A) {
     const SceneHdr& H = A.hdr;
@@ -151,34 +151,16 @@ __global__ __launch_bounds__(256, LIGHT ? RTC_HITS_LIGHT_WAVES : 1) void hits_ke
     const uint32_t yl = by0 + ((square ? wave >> 1 : wave) << thl) + (lane >> twl);
     if (!(x < H.width && yl < A.rows)) return;
     const size_t idx = (size_t)yl * H.width + x;
-    // compact local row -> global row of the image
-    const uint32_t band = yl / A.band_rows;
-    const uint32_t y = (band * A.n_parts + A.part) * A.band_rows + (yl - band * A.band_rows);
+    const uint32_t y = image_row(yl, A.band_rows, A.n_parts, A.part);
     // camera.rs:80-81: `0..height-1` x `0..width-1` -- the last row and column are never traced: misses
     if (!(x < H.width - 1u && y < H.height - 1u)) {
         store_miss(A.planes, idx);
         return;
     }
-    // ray_for_pixel, camera.rs:60-74
-    float x_offset = ((float)x + 0.5f) * H.pixel_size;
-    float y_offset = ((float)y + 0.5f) * H.pixel_size;
-    float world_x = H.half_w - x_offset;
-    float world_y = H.half_h - y_offset;
-    const float* c = H.cam;
-    V3 pixel = {c[0] * world_x + c[1] * world_y + c[2] * -1.0f + c[3],
-                c[4] * world_x + c[5] * world_y + c[6] * -1.0f + c[7],
-                c[8] * world_x + c[9] * world_y + c[10] * -1.0f + c[11]};
-    V3 origin = v3(H.cam_origin[0], H.cam_origin[1], H.cam_origin[2]);
-    // the scene-box early-out of render_body: a ray that misses the padded box around everything hits nothing
-    if (H.has_scene_box) {
-        const V3 du = pixel - origin;
-        const V3 iu = v3(__builtin_amdgcn_rcpf(du.x), __builtin_amdgcn_rcpf(du.y), __builtin_amdgcn_rcpf(du.z));
-        float tmin;
-        if (!aabb_hit(origin, iu, make_float4(H.scene_box[0], H.scene_box[1], H.scene_box[2], 0.0f),
-                      make_float4(H.scene_box[3], H.scene_box[4], H.scene_box[5], 0.0f), tmin)) {
-            store_miss(A.planes, idx);
-            return;
-        }
+    V3 origin, pixel;
+    if (primary_ray(H, x, y, origin, pixel)) {  // misses the padded box around everything: hits nothing
+        store_miss(A.planes, idx);
+        return;
     }
     V3 direction = norm3(pixel - origin);
     first_hit<NOBJ, SIMPLE, LIGHT>(H, A.soa, origin, direction, y * H.width + x, A.planes, idx);

@@ -495,7 +495,7 @@ struct SceneHdr {
     uint32_t has_tbox;
     float cull_c[3], cull_r2;
     float tri_guard;  // TRI_GUARD (the boxes' padding is derived from it on the host)
-    // Small trees in the unrolled kernels (rtc_device.hip flatten): group boxes as gates.  gate_box[g] = min.xyz, max.xyz;
+    // Small trees in the unrolled kernels (rtc_scene_prep.h flatten): group boxes as gates.  gate_box[g] = min.xyz, max.xyz;
     // bit g of gate_mask[i]: object i sits inside group g and is only intersected by rays that hit g's box
     uint32_t has_scene_box;   // scene_box bounds everything a primary ray can hit (render_body)
     float scene_box[6];       // min.xyz, max.xyz, padded
@@ -547,7 +547,7 @@ struct SceneSoA {
     //   group: { bounds.min.xyz, skip }, { bounds.max.xyz, slack }, unused   skip = entry index after the group's subtree,
     //          slack = 1e-3 * the box's largest |coordinate| (pruning margin, see for_each_object)
     //   leaf : { 0, 0, 0, object index }, { 0, 0, 0, -1 }, unused
-    //   leaf, a triangle with a pre-culling box (tri_precull; world space, padded on the host -- rtc_device.hip triangle_box):
+    //   leaf, a triangle with a pre-culling box (tri_precull; world space, padded on the host -- rtc_scene_prep.h triangle_box):
     //          { box.min.xyz, object index }, { box.max.xyz, -2 }, { unit normal.xyz, 1 if the next entry is such a leaf too }
     const float4* __restrict__ trav;
     // Triangles (shape/triangle.rs:9-17), 3 records per object, read only for RTC_TRIANGLE objects:
@@ -3051,7 +3051,7 @@ struct RenderArgs {
     // Block list: workgroup b renders the block tiles[b] = (s & 3) << 30 | (x0 / 4) << 16 | (s >> 2) << 15 | (y0 / 4) -- pixel origin
     // (x0, local row y0 < 2^17) and, in kernels compiled for lane sharing, ITS OWN lanes-per-pixel 2^s, s = 0 .. 4 -- instead of block
     // (blockIdx.x, blockIdx.y) of a regular grid.  For tree worlds with long leaf runs the host lists the blocks of image regions a mesh projects to first and
-    // with more lanes per pixel, the rest after them with one (rtc_device.hip build_block_list): such a frame's time is that of
+    // with more lanes per pixel, the rest after them with one (rtc_launch_plan.h build_block_list): such a frame's time is that of
     // its slowest waves, so those start first and are cut up.  From a scene's second frame on, any list is made from the wave
     // times of the frame before (refine_block_list).  nullptr: regular grid.
     const uint32_t* tiles;
@@ -3071,7 +3071,7 @@ struct RenderArgs {
     uint32_t swizzle;
     // regular grid: the launch covers the blocks from (block_x0, block_y0) on -- of a frame whose scene can only be seen
     // inside a rectangle of pixel columns [fill_x0, fill_x1) x local rows [fill_y0, fill_y1) only that rectangle is rendered
-    // (rtc_device.hip: scene rectangle); fill_wg_rows rows of the grid, spread evenly among the rendering ones, are
+    // (rtc_scene_prep.h plan_scene: scene rectangle); fill_wg_rows rows of the grid, spread evenly among the rendering ones, are
     // workgroups that zero-fill everything outside it instead, fill_rows local rows each.
     uint32_t block_x0, block_y0;
     uint32_t fill_wg_rows, fill_rows, fill_x0, fill_x1, fill_y0, fill_y1;
@@ -3115,6 +3115,119 @@ DI void fill_outside(const RenderArgs& A, uint32_t fill_row) {
     }
 }
 
+// What the kernels with one lane per pixel share -- render_body, ss_render_body (rtc_supersample.h), hits_kernel (rtc_hits.h)
+// and wf_trace_kernel<true> (rtc_wavefront.h): the one definition of a pixel's image row, of its primary ray and of the
+// counters' wave reduce.
+
+// Compact local row of a partition -> global row of the image: the partition owns every n_parts-th band of band_rows rows.
+DI uint32_t image_row(uint32_t yl, uint32_t band_rows, uint32_t n_parts, uint32_t part) {
+    const uint32_t band = yl / band_rows;
+    return (band * n_parts + part) * band_rows + (yl - band * band_rows);
+}
+
+// ray_for_pixel, camera.rs:60-74, up to its normalisation: the ray of pixel (x, image row y) starts at `origin` and runs
+// through `pixel`; the caller forms norm3(pixel - origin) where it goes on to trace.  Returns whether the ray misses the
+// scene's box, and so sees nothing.
+// The box is around everything a primary ray could hit (SceneHdr::scene_box, built and padded on the host when every
+// top-level object is bounded): a ray that misses it -- tested with the unnormalised direction and approximate
+// reciprocals, which move the ray by parts in 1e6 against a padding of 10 % of the box / 1 % of the camera's
+// distance -- hits nothing, so color_at would return black after one counted ray.  Saves the exact square root
+// and divisions of norm() and the walk on every such pixel (95 % of C5's).
+// (Handing out the unnormalised pair and leaving the branch to the caller is deliberate: a helper that normalises inside and
+// returns early on a miss compiled to more spills in render_kernel<4, true> -- LABNOTES.md, "one definition of the primary ray".)
+DI bool primary_ray(const SceneHdr& H, uint32_t x, uint32_t y, V3& origin, V3& pixel) {
+    float x_offset = ((float)x + 0.5f) * H.pixel_size;
+    float y_offset = ((float)y + 0.5f) * H.pixel_size;
+    float world_x = H.half_w - x_offset;
+    float world_y = H.half_h - y_offset;
+    const float* c = H.cam;
+    pixel = {c[0] * world_x + c[1] * world_y + c[2] * -1.0f + c[3],
+             c[4] * world_x + c[5] * world_y + c[6] * -1.0f + c[7],
+             c[8] * world_x + c[9] * world_y + c[10] * -1.0f + c[11]};
+    origin = v3(H.cam_origin[0], H.cam_origin[1], H.cam_origin[2]);
+    bool sees_nothing = false;
+    if (H.has_scene_box) {
+        const V3 du = pixel - origin;
+        const V3 iu = v3(__builtin_amdgcn_rcpf(du.x), __builtin_amdgcn_rcpf(du.y), __builtin_amdgcn_rcpf(du.z));
+        float tmin;
+        sees_nothing = !aabb_hit(origin, iu, make_float4(H.scene_box[0], H.scene_box[1], H.scene_box[2], 0.0f),
+                                 make_float4(H.scene_box[3], H.scene_box[4], H.scene_box[5], 0.0f), tmin);
+    }
+    return sees_nothing;
+}
+
+// work statistics: the wave's {rays, shaded hits, culled shadow rays, 0}, whole in lane 0
+DI uint4 reduce_wave_counts(const Counters& cnt) {
+    uint32_t rays = cnt.rays, shaded = cnt.shaded_count(), culled = cnt.culled_count();
+    for (int off = 32; off > 0; off >>= 1) {
+        rays += __shfl_down(rays, off, 64);
+        shaded += __shfl_down(shaded, off, 64);
+        culled += __shfl_down(culled, off, 64);
+    }
+    return make_uint4(rays, shaded, culled, 0u);
+}
+
+// Where a lane's pixel is, for render_body and ss_render_body: block `rep` (< blocks_y) of this workgroup, in a block list
+// (RenderArgs::tiles) or a regular grid -- swizzled, or, with RECT_LAUNCH, of a scene rectangle launch with its zero-filling
+// workgroups.  `fills`: this workgroup is one of those (wave-uniform; it renders nothing).
+// (`lane`, `wave`: the caller's own values, handed in.  Formed again in here from threadIdx.x, the same values cost render_kernel<-1, false>
+// eight more bytes of scratch per lane and moved every other instantiation's -- LABNOTES.md, "one definition of the primary ray".)
+struct Where {
+    uint32_t x, yl, sl, grid_y;
+    bool fills;
+};
+template <bool RECT_LAUNCH>
+DI Where where_is_lane(const RenderArgs& A, uint32_t lane, uint32_t wave, uint32_t blocks_y, uint32_t rep) {
+    Where w;
+    w.sl = Counters::SHARE_LANES ? A.share_log2 : 0u;  // lanes per pixel (log2)
+    w.fills = false;
+    w.grid_y = blockIdx.y;
+    uint32_t bx0, by0;  // pixel origin of this workgroup's block
+    if (A.tiles != nullptr) {
+        const uint32_t t = A.tiles[blockIdx.x];  // wave-uniform: a scalar load
+        if (Counters::SHARE_LANES) w.sl = (t >> 30) | ((t >> 13) & 4u);  // (a kernel without lane sharing is only ever given lists of whole blocks)
+        bx0 = ((t >> 16) & 0x3fffu) << 2;
+        by0 = (t & 0x7fffu) << 2;
+    } else {
+        uint32_t block_x0 = 0u, block_y0 = 0u;
+        if constexpr (RECT_LAUNCH) {
+            block_x0 = A.block_x0, block_y0 = A.block_y0;
+            if (A.fill_wg_rows != 0u) {
+                const uint32_t j = blockIdx.y / A.fill_period;
+                w.fills = j < A.fill_wg_rows && blockIdx.y == j * A.fill_period;
+                if (w.fills) w.grid_y = j;
+                else w.grid_y = blockIdx.y - min(A.fill_wg_rows, j + 1u);
+            }
+        }
+        uint32_t gx = blockIdx.x, gy = w.grid_y;
+        if (A.swizzle != 0u) {  // (RenderArgs::swizzle; never together with a rectangle, fills or several blocks per workgroup)
+            const uint32_t j = (gy & 3u) * gridDim.x + gx, r = j & 7u;
+            gy = (gy & ~3u) + (r >> 1);
+            gx = 2u * (j >> 3) + (r & 1u);
+        }
+        bx0 = (gx + block_x0) << (4u - (w.sl >> 1));
+        by0 = (gy * blocks_y + rep + block_y0) << (4u - ((w.sl + 1u) >> 1));
+    }
+    const uint32_t q = lane >> w.sl;  // q: the pixel's slot in the wave's tile
+    const uint32_t tw_log2 = 3u - (w.sl >> 1), th_log2 = 3u - ((w.sl + 1u) >> 1);
+    w.x = bx0 + ((wave & 1u) << tw_log2) + (q & ((1u << tw_log2) - 1u));
+    w.yl = by0 + ((wave >> 1) << th_log2) + (q >> tw_log2);
+    return w;
+}
+
+// The counter epilogue of render_body and ss_render_body: one partial per wave, and the wave's running time where the host
+// cuts its block lists by it (RenderArgs::wave_ticks; `timed`, `ticks0`: wave-uniform, the clock at the wave's start).
+DI void store_wave_counts(const RenderArgs& A, const Counters& cnt, bool timed, uint32_t ticks0) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint4 counts = reduce_wave_counts(cnt);
+    const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4u;
+    // one partial per WAVE and no workgroup barrier: a wave that is done leaves (where neighbouring tiles differ a lot in
+    // depth of recursion -- the edge of a glass ball -- the waiting waves were holding the slots of the next workgroup)
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 3) A.total[threadIdx.x] = 0ull;  // for sum_counts_kernel's atomics
+    if (lane == 0) A.block_counts[slot + wave] = counts;
+    if (timed && lane == 0) A.wave_ticks[slot + wave] = (uint32_t)wall_clock64() - ticks0;
+}
+
 // Camera::render (camera.rs:76-91): one lane per pixel, 8x8 pixel tile per
 // wave, 2x2 waves per 256-thread workgroup.  NOBJ: see for_each_object.
 #ifndef RTC_WAVES_PER_SIMD
@@ -3150,48 +3263,7 @@ DI void render_body(const RenderArgs& A) {
     // front of color_at decides on which side of a cliff the allocation lands -- reflect_refract's kernel, 102 registers: 21
     // spilled with the block list's entry fetched by a scalar load, 69 with the same entry fetched by a vector load, 69 with a
     // clock read at the wave's start.  Hence: a plain load here, and wave times only in the kernels that cut their lists.)
-    struct Where {
-        uint32_t x, yl, sl, grid_y;
-        bool fills;
-    };
-    auto where = [&](uint32_t rep) {
-        Where w;
-        w.sl = Counters::SHARE_LANES ? A.share_log2 : 0u;  // lanes per pixel (log2)
-        w.fills = false;
-        w.grid_y = blockIdx.y;
-        uint32_t bx0, by0;  // pixel origin of this workgroup's block
-        if (A.tiles != nullptr) {
-            const uint32_t t = A.tiles[blockIdx.x];  // wave-uniform: a scalar load
-            if (Counters::SHARE_LANES) w.sl = (t >> 30) | ((t >> 13) & 4u);  // (a kernel without lane sharing is only ever given lists of whole blocks)
-            bx0 = ((t >> 16) & 0x3fffu) << 2;
-            by0 = (t & 0x7fffu) << 2;
-        } else {
-            uint32_t block_x0 = 0u, block_y0 = 0u;
-            if constexpr (RECT_LAUNCH) {
-                block_x0 = A.block_x0, block_y0 = A.block_y0;
-                if (A.fill_wg_rows != 0u) {
-                    const uint32_t j = blockIdx.y / A.fill_period;
-                    w.fills = j < A.fill_wg_rows && blockIdx.y == j * A.fill_period;
-                    if (w.fills) w.grid_y = j;
-                    else w.grid_y = blockIdx.y - min(A.fill_wg_rows, j + 1u);
-                }
-            }
-            uint32_t gx = blockIdx.x, gy = w.grid_y;
-            if (A.swizzle != 0u) {  // (RenderArgs::swizzle; never together with a rectangle, fills or several blocks per workgroup)
-                const uint32_t j = (gy & 3u) * gridDim.x + gx, r = j & 7u;
-                gy = (gy & ~3u) + (r >> 1);
-                gx = 2u * (j >> 3) + (r & 1u);
-            }
-            bx0 = (gx + block_x0) << (4u - (w.sl >> 1));
-            by0 = (gy * blocks_y + rep + block_y0) << (4u - ((w.sl + 1u) >> 1));
-        }
-        const uint32_t q = lane >> w.sl;  // q: the pixel's slot in the wave's tile
-        const uint32_t tw_log2 = 3u - (w.sl >> 1), th_log2 = 3u - ((w.sl + 1u) >> 1);
-        w.x = bx0 + ((wave & 1u) << tw_log2) + (q & ((1u << tw_log2) - 1u));
-        w.yl = by0 + ((wave >> 1) << th_log2) + (q >> tw_log2);
-        return w;
-    };
-    const Where w0 = where(0u);
+    const Where w0 = where_is_lane<RECT_LAUNCH>(A, lane, wave, blocks_y, 0u);
     const uint32_t sl = w0.sl;
     Counters cnt = {0u, 0u, sl};
     const bool timed = Counters::SHARE_LANES && A.wave_ticks != nullptr;  // wave-uniform
@@ -3214,38 +3286,15 @@ DI void render_body(const RenderArgs& A) {
         if (w0.fills) fill_outside(A, w0.grid_y);
     }
     for (uint32_t rep = 0; rep < blocks_y; rep++) {
-    const Where w = where(rep);
+    const Where w = where_is_lane<RECT_LAUNCH>(A, lane, wave, blocks_y, rep);
     const uint32_t x = w.x, yl = w.yl;
     if ((!RECT_LAUNCH || !w.fills) && x < H.width && yl < A.rows) {
-        // compact local row -> global row of the image
-        const uint32_t band = yl / A.band_rows;
-        const uint32_t y = (band * A.n_parts + A.part) * A.band_rows + (yl - band * A.band_rows);
+        const uint32_t y = image_row(yl, A.band_rows, A.n_parts, A.part);
         V3 col = v3(0.0f, 0.0f, 0.0f);
         // camera.rs:80-81: `0..height-1` x `0..width-1` -- the last row and column stay black
         if (x < H.width - 1u && y < H.height - 1u) {
-            // ray_for_pixel, camera.rs:60-74
-            float x_offset = ((float)x + 0.5f) * H.pixel_size;
-            float y_offset = ((float)y + 0.5f) * H.pixel_size;
-            float world_x = H.half_w - x_offset;
-            float world_y = H.half_h - y_offset;
-            const float* c = H.cam;
-            V3 pixel = {c[0] * world_x + c[1] * world_y + c[2] * -1.0f + c[3],
-                        c[4] * world_x + c[5] * world_y + c[6] * -1.0f + c[7],
-                        c[8] * world_x + c[9] * world_y + c[10] * -1.0f + c[11]};
-            V3 origin = v3(H.cam_origin[0], H.cam_origin[1], H.cam_origin[2]);
-            // A box around everything a primary ray could hit (SceneHdr::scene_box, built and padded on the host when every
-            // top-level object is bounded): a ray that misses it -- tested with the unnormalised direction and approximate
-            // reciprocals, which move the ray by parts in 1e6 against a padding of 10 % of the box / 1 % of the camera's
-            // distance -- hits nothing, so color_at would return black after one counted ray.  Saves the exact square root
-            // and divisions of norm() and the walk on every such pixel (95 % of C5's).
-            bool sees_nothing = false;
-            if (H.has_scene_box) {
-                const V3 du = pixel - origin;
-                const V3 iu = v3(__builtin_amdgcn_rcpf(du.x), __builtin_amdgcn_rcpf(du.y), __builtin_amdgcn_rcpf(du.z));
-                float tmin;
-                sees_nothing = !aabb_hit(origin, iu, make_float4(H.scene_box[0], H.scene_box[1], H.scene_box[2], 0.0f),
-                                         make_float4(H.scene_box[3], H.scene_box[4], H.scene_box[5], 0.0f), tmin);
-            }
+            V3 origin, pixel;
+            const bool sees_nothing = primary_ray(H, x, y, origin, pixel);
             if (sees_nothing) {
                 cnt.rays += cnt.lead();
             } else {
@@ -3266,7 +3315,7 @@ DI void render_body(const RenderArgs& A) {
         // an LDS round trip and registers in front of every wave's exit.)
         if (cnt.lead()) {
             const bool through = A.progress != nullptr;  // wave-uniform: write-through stores (RenderArgs::progress)
-            const Where ws = where(rep);
+            const Where ws = where_is_lane<RECT_LAUNCH>(A, lane, wave, blocks_y, rep);
             if (A.out_u8 != nullptr) {  // wave-uniform: scale_color on the way out (the arithmetic of quantize_kernel)
                 uint8_t* dst = A.out_u8 + ((size_t)ws.yl * H.width + ws.x) * 3;
                 const uint8_t r = (uint8_t)fmaxf(fminf(col.x * 255.0f, 255.0f), 0.0f), g = (uint8_t)fmaxf(fminf(col.y * 255.0f, 255.0f), 0.0f),
@@ -3293,19 +3342,7 @@ DI void render_body(const RenderArgs& A) {
         }
     }
     }
-    // work statistics: wave reduce, then one partial per wave
-    uint32_t rays = cnt.rays, shaded = cnt.shaded_count(), culled = cnt.culled_count();
-    for (int off = 32; off > 0; off >>= 1) {
-        rays += __shfl_down(rays, off, 64);
-        shaded += __shfl_down(shaded, off, 64);
-        culled += __shfl_down(culled, off, 64);
-    }
-    const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4u;
-    // one partial per WAVE and no workgroup barrier: a wave that is done leaves (where neighbouring tiles differ a lot in
-    // depth of recursion -- the edge of a glass ball -- the waiting waves were holding the slots of the next workgroup)
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 3) A.total[threadIdx.x] = 0ull;  // for sum_counts_kernel's atomics
-    if (lane == 0) A.block_counts[slot + wave] = make_uint4(rays, shaded, culled, 0u);
-    if (timed && lane == 0) A.wave_ticks[slot + wave] = (uint32_t)wall_clock64() - ticks0;
+    store_wave_counts(A, cnt, timed, ticks0);
     if (A.progress != nullptr) {  // see RenderArgs::progress
         // every store of this wave has been acknowledged -- and, being write-through, is in memory -- before the wave counts
         // itself done
@@ -3385,7 +3422,7 @@ __global__ __launch_bounds__(1024) void sum_counts_kernel(const uint4* __restric
     }
 }
 
-// Scene tiles (rtc_device.hip ctx_render_slot): the tiles of the canvas no entry of the world projects to are black.  One
+// Scene tiles (rtc_launch_plan.h plan_scene_tiles): the tiles of the canvas no entry of the world projects to are black.  One
 // workgroup per job {x0 | n << 16 (tiles), local row y0}: sixteen rows of n tiles' columns, zeroed with 16-byte stores where rows are
 // aligned to that (f32 rows of widths that are multiples of four; byte rows always start on a multiple of 48 columns' worth).
 __global__ __launch_bounds__(256) void fill_tiles_kernel(const uint2* __restrict__ jobs, uint32_t n_jobs, uint8_t* __restrict__ out, uint32_t width, uint32_t rows,

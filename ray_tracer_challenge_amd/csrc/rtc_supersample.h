@@ -8,11 +8,11 @@
 // block ends with the same bits), and one lane per output pixel stores.
 //
 // Included by rtc_device.hip after rtc_kernel_core.h (ahead-of-time instantiations) and handed to hiprtc beside it
-// (-DRTC_SPEC_SS=K: ss_render_kernel_spec).  As rtc_hits.h: every expression below is either one of the core's device
-// functions or restates a line of render_body with the same operations in the same order -- block and lane placement,
-// ray_for_pixel, the scene-box early-out, the counter epilogue.  The core itself is not touched: its text is hashed into the
-// kernel ids.  Not restated, because the host never asks a supersampled launch for them: scene rectangle launches and their
-// zero-filling workgroups, several blocks per workgroup, progress words, the u8 canvas.
+// (-DRTC_SPEC_SS=K: ss_render_kernel_spec).  Everything up to the reduce is the core's own device functions, the ones
+// render_body calls: where_is_lane (never a scene rectangle launch, one block per workgroup), primary_ray, color_at,
+// store_wave_counts -- all but image_row, whose two lines are written out below.  Not supported, because the host never
+// asks a supersampled launch for them: scene rectangle launches and their zero-filling workgroups, several blocks per
+// workgroup, progress words, the u8 canvas.
 #ifndef RTC_SUPERSAMPLE_H
 #define RTC_SUPERSAMPLE_H
 
@@ -64,30 +64,12 @@ template <int NOBJ, bool SIMPLE, int K>
 DI void ss_render_body(const SsRenderArgs& SA) {
     const RenderArgs& A = SA.fine;
     const SceneHdr& H = A.hdr;
+    // Where this lane's fine pixel is: regular grid (swizzled or not) or block list
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    // Where this lane's fine pixel is: render_body's `where`, regular grid (swizzled or not) or block list
-    uint32_t sl = Counters::SHARE_LANES ? A.share_log2 : 0u;  // lanes per pixel (log2)
-    uint32_t bx0, by0;                                         // fine pixel origin of this workgroup's block
-    if (A.tiles != nullptr) {
-        const uint32_t t = A.tiles[blockIdx.x];  // wave-uniform: a scalar load
-        if (Counters::SHARE_LANES) sl = (t >> 30) | ((t >> 13) & 4u);
-        bx0 = ((t >> 16) & 0x3fffu) << 2;
-        by0 = (t & 0x7fffu) << 2;
-    } else {
-        uint32_t gx = blockIdx.x, gy = blockIdx.y;
-        if (A.swizzle != 0u) {  // (RenderArgs::swizzle)
-            const uint32_t j = (gy & 3u) * gridDim.x + gx, r = j & 7u;
-            gy = (gy & ~3u) + (r >> 1);
-            gx = 2u * (j >> 3) + (r & 1u);
-        }
-        bx0 = gx << (4u - (sl >> 1));
-        by0 = gy << (4u - ((sl + 1u) >> 1));
-    }
-    const uint32_t q = lane >> sl;  // q: the fine pixel's slot in the wave's tile
-    const uint32_t tw_log2 = 3u - (sl >> 1), th_log2 = 3u - ((sl + 1u) >> 1);
+    const Where w = where_is_lane<false>(A, lane, wave, 1u, 0u);
+    const uint32_t sl = w.sl, x = w.x, yl = w.yl;
+    const uint32_t tw_log2 = 3u - (sl >> 1), q = lane >> sl;  // the tile's width and the fine pixel's slot in it, as where_is_lane has them
     const uint32_t qx = q & ((1u << tw_log2) - 1u), qy = q >> tw_log2;
-    const uint32_t x = bx0 + ((wave & 1u) << tw_log2) + qx;
-    const uint32_t yl = by0 + ((wave >> 1) << th_log2) + qy;
     Counters cnt = {0u, 0u, sl};
     const bool timed = Counters::SHARE_LANES && A.wave_ticks != nullptr;  // wave-uniform
     uint32_t ticks0 = 0u;
@@ -98,30 +80,16 @@ DI void ss_render_body(const SsRenderArgs& SA) {
     // rows of a partition and every band are multiples of K, and so is every tile's origin.
     V3 col = v3(0.0f, 0.0f, 0.0f);
     if (x < H.width && yl < A.rows) {
-        // compact local row -> global row of the fine image
+        // compact local row -> global row of the fine image: image_row's expression, written out.  The one shared call that is not
+        // neutral here: with image_row called, ten of the twelve ahead-of-time instantiations of this body spill differently (4 - 8 B
+        // of scratch per lane either way) and <4, simple, 4> runs 6 % slower; written out, all twelve have the figures they had
+        // before (LABNOTES.md, "one definition of the primary ray").
         const uint32_t band = yl / A.band_rows;
         const uint32_t y = (band * A.n_parts + A.part) * A.band_rows + (yl - band * A.band_rows);
         // camera.rs:80-81 at the fine resolution: the fine frame's last row and column stay black, so the output's are dimmed
         if (x < H.width - 1u && y < H.height - 1u) {
-            // ray_for_pixel, camera.rs:60-74
-            float x_offset = ((float)x + 0.5f) * H.pixel_size;
-            float y_offset = ((float)y + 0.5f) * H.pixel_size;
-            float world_x = H.half_w - x_offset;
-            float world_y = H.half_h - y_offset;
-            const float* c = H.cam;
-            V3 pixel = {c[0] * world_x + c[1] * world_y + c[2] * -1.0f + c[3],
-                        c[4] * world_x + c[5] * world_y + c[6] * -1.0f + c[7],
-                        c[8] * world_x + c[9] * world_y + c[10] * -1.0f + c[11]};
-            V3 origin = v3(H.cam_origin[0], H.cam_origin[1], H.cam_origin[2]);
-            // the scene-box early-out of render_body
-            bool sees_nothing = false;
-            if (H.has_scene_box) {
-                const V3 du = pixel - origin;
-                const V3 iu = v3(__builtin_amdgcn_rcpf(du.x), __builtin_amdgcn_rcpf(du.y), __builtin_amdgcn_rcpf(du.z));
-                float tmin;
-                sees_nothing = !aabb_hit(origin, iu, make_float4(H.scene_box[0], H.scene_box[1], H.scene_box[2], 0.0f),
-                                         make_float4(H.scene_box[3], H.scene_box[4], H.scene_box[5], 0.0f), tmin);
-            }
+            V3 origin, pixel;
+            const bool sees_nothing = primary_ray(H, x, y, origin, pixel);
             if (sees_nothing) {
                 cnt.rays += cnt.lead();
             } else {
@@ -131,7 +99,7 @@ DI void ss_render_body(const SsRenderArgs& SA) {
         }
     }
     // The reduction, after the divergent region: every lane of the wave takes part.  No LDS round trip and no workgroup
-    // barrier -- a finished wave must be able to leave (render_body's epilogue says why).
+    // barrier -- a finished wave must be able to leave (store_wave_counts says why).
     col.x = ss_reduce<K>(col.x, sl, tw_log2);
     col.y = ss_reduce<K>(col.y, sl, tw_log2);
     col.z = ss_reduce<K>(col.z, sl, tw_log2);
@@ -146,17 +114,7 @@ DI void ss_render_body(const SsRenderArgs& SA) {
             dst[2] = col.z;
         }
     }
-    // work statistics: wave reduce, then one partial per wave (render_body's epilogue)
-    uint32_t rays = cnt.rays, shaded = cnt.shaded_count(), culled = cnt.culled_count();
-    for (int off = 32; off > 0; off >>= 1) {
-        rays += __shfl_down(rays, off, 64);
-        shaded += __shfl_down(shaded, off, 64);
-        culled += __shfl_down(culled, off, 64);
-    }
-    const size_t slot = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4u;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 3) A.total[threadIdx.x] = 0ull;  // for sum_counts_kernel's atomics
-    if (lane == 0) A.block_counts[slot + wave] = make_uint4(rays, shaded, culled, 0u);
-    if (timed && lane == 0) A.wave_ticks[slot + wave] = (uint32_t)wall_clock64() - ticks0;
+    store_wave_counts(A, cnt, timed, ticks0);
 }
 
 #ifdef RTC_SPEC_LIST

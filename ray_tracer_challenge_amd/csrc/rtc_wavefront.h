@@ -6,8 +6,8 @@
 // frame while the rest of the chip is idle (LABNOTES.md section 9, "when the waves run": mesh 2048^2 is throughput until
 // 2.6 ms and ends at 3.9).  Here the unit of scheduling is one ray:
 //
-//   level 0        one lane per pixel traces the primary ray (ray_for_pixel + World::color_at's hit and shade_hit, world.rs:
-//                  62-101); a hit with children becomes a NODE in HBM -- the suspended shade_hit: surface colour, the
+//   level 0        one lane per pixel traces the primary ray (the core's image_row and primary_ray, which render_body calls too,
+//                  then World::color_at's hit and shade_hit, world.rs:62-101); a hit with children becomes a NODE in HBM -- the suspended shade_hit: surface colour, the
 //                  material's reflective / transparency, Schlick's R, where the result goes -- and its child rays are
 //                  appended to the next level's ray lists (reflection children to one list, refraction children to the other:
 //                  neighbouring pixels' children stay neighbours, which is what the packet walk's economy rests on);
@@ -144,28 +144,13 @@ __global__ __launch_bounds__(256, 6) void wf_trace_kernel(WfArgs A) {
         const uint32_t x = (blockIdx.x << 4) + ((wave & 1u) << 3) + (lane & 7u);
         const uint32_t yl = (blockIdx.y << 4) + ((wave >> 1) << 3) + (lane >> 3);
         if (x < H.width && yl < A.rows) {
-            const uint32_t band = yl / A.band_rows;
-            const uint32_t y = (band * A.n_parts + A.part) * A.band_rows + (yl - band * A.band_rows);
+            const uint32_t y = image_row(yl, A.band_rows, A.n_parts, A.part);
             parent = -(int32_t)(1u + yl * H.width + x);
             // camera.rs:80-81: the last row and column stay black
             if (x < H.width - 1u && y < H.height - 1u) {
-                // ray_for_pixel, camera.rs:60-74 (as render_body)
-                float x_offset = ((float)x + 0.5f) * H.pixel_size;
-                float y_offset = ((float)y + 0.5f) * H.pixel_size;
-                float world_x = H.half_w - x_offset;
-                float world_y = H.half_h - y_offset;
-                const float* c = H.cam;
-                V3 pix = {c[0] * world_x + c[1] * world_y + c[2] * -1.0f + c[3], c[4] * world_x + c[5] * world_y + c[6] * -1.0f + c[7],
-                          c[8] * world_x + c[9] * world_y + c[10] * -1.0f + c[11]};
-                V3 origin = v3(H.cam_origin[0], H.cam_origin[1], H.cam_origin[2]);
-                bool sees_nothing = false;
-                if (H.has_scene_box) {  // render_body's early-out: a ray that misses the padded box of everything is black after one counted ray
-                    const V3 du = pix - origin;
-                    const V3 iu = v3(__builtin_amdgcn_rcpf(du.x), __builtin_amdgcn_rcpf(du.y), __builtin_amdgcn_rcpf(du.z));
-                    float tmin;
-                    sees_nothing = !aabb_hit(origin, iu, make_float4(H.scene_box[0], H.scene_box[1], H.scene_box[2], 0.0f),
-                                             make_float4(H.scene_box[3], H.scene_box[4], H.scene_box[5], 0.0f), tmin);
-                }
+                V3 origin, pix;
+                // (render_body's early-out: a ray that misses the padded box of everything is black after one counted ray)
+                const bool sees_nothing = primary_ray(H, x, y, origin, pix);
                 if (sees_nothing) {
                     cnt.rays += 1u;
                     wf_store_pixel(A, yl * H.width + x, v3(0.0f, 0.0f, 0.0f));
@@ -290,14 +275,9 @@ __global__ __launch_bounds__(256, 6) void wf_trace_kernel(WfArgs A) {
     }
     if constexpr (PRIMARY) break;
     }
-    // ---- statistics: one set of atomics per wave
-    uint32_t rays = cnt.rays, shaded = cnt.shaded & CNT_SHADED_MASK, culled = cnt.shaded >> CNT_CULLED_SHIFT;
-    for (int off = 32; off > 0; off >>= 1) {
-        rays += __shfl_down(rays, off, 64);
-        shaded += __shfl_down(shaded, off, 64);
-        culled += __shfl_down(culled, off, 64);
-    }
-    if (lane == 0) A.wave_counts[A.count_base + ((blockIdx.y * gridDim.x + blockIdx.x) << 2) + (threadIdx.x >> 6)] = make_uint4(rays, shaded, culled, 0u);
+    // ---- statistics: one partial per wave
+    const uint4 counts = reduce_wave_counts(cnt);
+    if (lane == 0) A.wave_counts[A.count_base + ((blockIdx.y * gridDim.x + blockIdx.x) << 2) + (threadIdx.x >> 6)] = counts;
 }
 
 // after a level has been traced: how many nodes exist now (the combine pass's range for that level)

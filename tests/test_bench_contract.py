@@ -148,7 +148,7 @@ def test_kernel_ids_of_the_committed_summaries_name_the_code_object():
     """Since round 4 a scene kernel's id ends in the checksum of its code object (two compilers gave two binaries for one source):
     the summaries of the round carry that form."""
     import re
-    for p in glob.glob(os.path.join(ROOT, "profiles", "r04_*_pmc.json")):
+    for p in glob.glob(os.path.join(ROOT, "profiles", "r0[4-9]_*_pmc.json")):
         kid = json.load(open(p))["kernel_id"]
         assert re.fullmatch(r"spec_[0-9a-f]{16}\.[0-9a-f]{8}", kid), (p, kid)
 

@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""development (no GPU needed): what the compiler makes of every kernel, from one csrc directory or from two side by side.
+
+    python tools/codegen_table.py CSRC [OTHER_CSRC] [--out FILE]
+
+Per kernel: VGPRs, SGPRs, scratch bytes per lane, LDS bytes (the code object's metadata), instructions and `scratch_`
+instructions (counted in the assembly).  Covered: every kernel of the ahead-of-time library (rtc_device.hip, rtc_oneshot.hip,
+build.py's flags, device only); the scene kernels of the eight profiled workloads (tools/check_profile_ids.sh), their options
+taken from World.scene_plan(camera) and compiled as tools/spec_asm.sh does; and C3's supersampling scene kernel at k = 2
+(the fine camera's options as rtc_ctx_set_scene_ss rewrites them).  With two directories the rows are compared and every
+figure that differs is marked.
+
+Build first (python -m ray_tracer_challenge_amd.build --all, in this tree and in the tree of any other directory named): the
+scenes' option lists come from this tree's library, and rtc_device.hip includes the literal the build generates beside it.
+The figures are read from the assembly as this compiler writes it: one metadata entry per kernel, opening with .agpr_count,
+and a kernel's instructions between its label and its .Lfunc_end."""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from ray_tracer_challenge_amd import scenes  # noqa: E402
+
+SCENES = [("C3", "soft_shadows", 4096, 4096), ("C4", "glass_and_mirror", 4096, 4096), ("C5", "sphere_grid", 8192, 8192),
+          ("hexagons", "hexagons", 4096, 2048), ("mesh", "mesh", 2048, 2048), ("dragons", "here_be_dragons", 1000, 400),
+          ("reflect_refract", "reflect_refract", 4096, 2048), ("first_textures", "first_textures", 4096, 2048)]
+FIGURES = ("vgpr", "sgpr", "scratch", "lds", "insts", "scratch_insts")
+
+
+def scene_defs(name, w, h, ss=0):
+    kw = {"jitter": ("hashed", scenes.DEFAULT_SEED)} if name == "soft_shadows" else {}
+    world, camera, _ = getattr(scenes, name)(w, h, **kw)
+    if ss:
+        camera = camera.supersampled(ss)
+    defs = world.scene_plan(camera)[1]["spec_defs"].split()
+    if ss:
+        defs = [d[:-1] + "0" if d in ("-DRTC_SPEC_BLOCKS_Y=1", "-DRTC_SPEC_RECT=1") else d for d in defs] + ["-DRTC_SPEC_SS=%d" % ss]
+    if not any(d.startswith("-DRTC_WAVES_PER_SIMD=") for d in defs):
+        defs.append("-DRTC_WAVES_PER_SIMD=7")
+    return defs
+
+
+def compile_asm(csrc, source, defs, out):
+    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-I" + csrc,
+           "-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S", "-o", out, source] + defs
+    subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+    return out
+
+
+def read_asm(path):
+    """{kernel: figures} of one assembly file."""
+    text = open(path).read()
+    rows = {}
+    for m in re.finditer(r"^  - \.agpr_count:.*?(?=^  - \.agpr_count:|^amdhsa\.target)", text, re.S | re.M):
+        f = dict(re.findall(r"^\s+\.(\w+):\s+(.*)$", m.group(0), re.M))
+        rows[f["name"].strip("'")] = {"vgpr": int(f["vgpr_count"]), "sgpr": int(f["sgpr_count"]), "scratch": int(f["private_segment_fixed_size"]),
+                                      "lds": int(f["group_segment_fixed_size"])}
+    for name, r in rows.items():
+        body = text[text.index("\n%s:" % name):]
+        body = body[:body.index(".Lfunc_end")]
+        insts = [ln.split()[0] for ln in body.splitlines() if re.match(r"^\t[a-z]", ln)]
+        r["insts"], r["scratch_insts"] = len(insts), sum(1 for i in insts if i.startswith("scratch_"))
+    return rows
+
+
+def demangle(names):
+    if not names:
+        return {}
+    out = subprocess.run(["c++filt"] + list(names), capture_output=True, text=True).stdout.split("\n")
+    return {n: re.sub(r"^void rtc::|\(rtc::\w+\)$|\(.*\)$", "", d) for n, d in zip(names, out)}
+
+
+def table(csrc, tmp, tag):
+    jobs = [("aot " + s, os.path.join(csrc, s), []) for s in ("rtc_device.hip", "rtc_oneshot.hip")]
+    spec, ss = os.path.join(tmp, "spec.hip"), os.path.join(tmp, "ss.hip")
+    open(spec, "w").write('#include "rtc_kernel_core.h"\n')
+    open(ss, "w").write('#include "rtc_supersample.h"\n')
+    for scene, name, w, h in SCENES:
+        jobs.append(("scene " + scene, spec, scene_defs(name, w, h)))
+    jobs.append(("scene C3 ss=2", ss, scene_defs("soft_shadows", 4096, 4096, ss=2)))
+    with ThreadPoolExecutor(8) as ex:
+        files = list(ex.map(lambda j: compile_asm(csrc, j[1], j[2], os.path.join(tmp, "%s_%s.s" % (tag, j[0].replace(" ", "_").replace("=", "")))), jobs))
+    rows = {}
+    for (kind, _, _), f in zip(jobs, files):
+        r = read_asm(f)
+        pretty = demangle(list(r))
+        for k, v in r.items():
+            rows["%s: %s" % (kind, pretty[k])] = v
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("csrc", nargs="+")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    own = os.path.join(ROOT, "ray_tracer_challenge_amd", "csrc")
+    with tempfile.TemporaryDirectory() as tmp:
+        tables = [table(os.path.abspath(c), tmp, "t%d" % i) for i, c in enumerate(args.csrc)]
+    lines = ["figures per kernel: VGPRs / SGPRs / scratch bytes per lane / LDS bytes / instructions / scratch_ instructions"]
+    if len(tables) == 2:
+        lines.append("first: %s   second: %s   (* a figure that differs)" % tuple(os.path.relpath(os.path.abspath(c), ROOT) if os.path.abspath(c) == own else "the parent's csrc" for c in args.csrc))
+    differing = []
+    for k in sorted(set().union(*tables)):
+        cells = [" / ".join(str(t[k][f]) for f in FIGURES) if k in t else "-" for t in tables]
+        mark = ""
+        if len(tables) == 2 and cells[0] != cells[1]:
+            which = [f for f in FIGURES if k not in tables[0] or k not in tables[1] or tables[0][k][f] != tables[1][k][f]]
+            mark = "   * " + ", ".join(which)
+            differing.append((k, which))
+        lines.append("%-110s %s%s" % (k, "   |   ".join("%-36s" % c for c in cells), mark))
+    if len(tables) == 2:
+        hard = [k for k, which in differing if set(which) & {"vgpr", "scratch", "lds"}]
+        lines.append("kernels with a differing figure: %d of %d; with differing VGPRs, scratch bytes or LDS bytes: %d%s"
+                     % (len(differing), len(set().union(*tables)), len(hard), "".join("\n    " + k for k in hard)))
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if args.out:
+        open(args.out, "w").write(text)
+
+
+if __name__ == "__main__":
+    main()
