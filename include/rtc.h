@@ -456,6 +456,49 @@ rtc_status rtc_hit_at(const rtc_scene* scene, const float* origins, const float*
  * A null context, no plane requested: RTC_ERR_INVALID_ARG (decided before any device call). */
 rtc_status rtc_ctx_render_hits(rtc_ctx* ctx, const rtc_partition* part, const rtc_hit_planes* d_out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Ray streams: the caller's rays against the context's resident scene, on the device.
+ * ---------------------------------------------------------------------- */
+/* World::color_at (world.rs:88-101) for n caller rays against the context's resident scene.  DEVICE pointers:
+ * d_origins, d_directions n x 4 f32 (16-byte aligned; x, y, z are read, w is ignored: a ray is a point and a vector
+ * by position); d_keys n x u32 or NULL -- ray i draws its light samples as pixel d_keys[i] (NULL: i), the key a render
+ * gives pixel y*W+x; d_out_rgb n x 3 f32.  Asynchronous on `stream`.  depth 0 .. RTC_MAX_DEPTH as rtc_ctx_render.
+ * The direction is used as given (the reference's color_at does not normalise it either).  Rays with non-finite
+ * components are the caller's error: their colour is unspecified.
+ * One lane per ray, ray i in thread i: a wave is 64 consecutive rays, and rays that are neighbours in space trace fastest
+ * as neighbours in the buffers.  The kernel is the context's ahead-of-time family or, where rtc_ctx_set_scene's
+ * specialisation policy -- with n in the place of the frame's pixel count; RTC_AMD_SPECIALIZE=0|1 as there -- asks for
+ * it, the scene's own, compiled by the first trace that wants it (a context that never traces pays nothing) and cached
+ * like every scene kernel; depth above 8 takes the deep-stack variant, as for rtc_ctx_render.  A supersampled context
+ * traces like any other.
+ * RTC_ERR_INVALID_ARG, decided before any device call: a null context, no scene set, a null ray or output pointer with
+ * n > 0, origins / directions not 16-byte aligned, keys / output not 4-byte aligned, depth out of range.  n == 0: RTC_OK,
+ * nothing is launched.
+ * rtc_ctx_stats after a trace reports that launch: rays, shaded_hits and culled_shadow_rays as a render counts them,
+ * pixels = n, rows = 0, kernel_ms and launches over the traces since the last such report.  Everything else a trace leaves
+ * alone -- block lists, measured wave times, grid feedback, the render kernels' warm-up, rtc_ctx_kernel_name / _id: a
+ * render after a trace is scheduled and reported as if the trace had not happened.  (rtc_ctx_render_hits, which leaves
+ * rtc_ctx_stats alone, leaves it alone here too: after trace, render_hits, the stats are still the trace's.)
+ * One stream at a time, as for the whole context: the trace's counter partials and totals exist once per context, so two traces
+ * in flight on different streams compute the right colours and race on what rtc_ctx_stats reports.
+ * The argument checks come in this order, the context's last, so that each is reported by name whatever else is wrong:
+ * ray and output pointers, alignment, depth, context, scene. */
+rtc_status rtc_ctx_trace(rtc_ctx* ctx, int32_t depth, const void* d_origins, const void* d_directions,
+                         const void* d_keys, uint32_t n, void* d_out_rgb, void* stream);
+/* ray_for_pixel (camera.rs:60-74) of `camera` for image rows [y0, y0 + n_rows), every column, in image order, written
+ * to DEVICE buffers in rtc_ctx_trace's layout (origin.w 1, direction.w 0, key y*W+x); any of the three may be NULL.
+ * The camera is an argument, not the context's, and no scene need be set.  The rays are the render kernels' own (one device
+ * function makes both), the last row and column included, which a render never traces (camera.rs:80-81).
+ * RTC_ERR_INVALID_ARG, decided before any device call: a null camera or context, misaligned pointers as for rtc_ctx_trace,
+ * y0 + n_rows > height, more than 2^32 - 1 rays.  A camera whose inverse transform is not affine: RTC_ERR_UNSUPPORTED, as
+ * rtc_ctx_set_scene answers it.  n_rows == 0: RTC_OK, nothing is launched. */
+rtc_status rtc_ctx_camera_rays(rtc_ctx* ctx, const rtc_camera* camera, uint32_t y0, uint32_t n_rows,
+                               void* d_origins, void* d_directions, void* d_keys, void* stream);
+/* The kernel of the context's last rtc_ctx_trace and the code it names ("trace_kernel<...>" / "trace_kernel_spec[...]";
+ * "aot_trace_..." or "spec_..." ids of their own, as rtc_ctx_kernel_name / _id).  "" before the first trace of the current scene. */
+const char* rtc_ctx_trace_kernel_name(rtc_ctx* ctx);
+const char* rtc_ctx_trace_kernel_id(rtc_ctx* ctx);
+
 /* Batched Light::intensity_at (light.rs:10) for n world points (n*4 f32). */
 rtc_status rtc_intensity_at(const rtc_scene* scene, const float* points, uint32_t n, int32_t device,
                             float* out);

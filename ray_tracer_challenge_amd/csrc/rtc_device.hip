@@ -37,6 +37,7 @@
 #include "rtc_kernel_core.h"
 #include "rtc_hits.h"
 #include "rtc_supersample.h"
+#include "rtc_trace.h"
 #include "rtc_wavefront.h"
 #include "rtc_scene_prep.h"
 
@@ -142,7 +143,8 @@ struct rtc_ctx {
     // the policy left the scene to the ahead-of-time kernels -- deep_defs() then writes the options from scratch)
     std::vector<std::string> spec_defs;
     std::string spec_name;
-    std::map<int, hipFunction_t> deep_fn;
+    typedef std::map<int, std::pair<hipFunction_t, std::string>> DeepKernels;  // by stack depth: the kernel and its id
+    DeepKernels deep_fn;
     std::string kernel_name;          // what rtc_ctx_render launches, for rtc_ctx_kernel_name()
     // Block list of the current scene (RenderArgs::tiles): which 16 x 16 pixel tiles of the image a mesh projects to
     // (row-major bitmap, empty: no block list), and the list last built -- for the partition it was built for
@@ -201,6 +203,27 @@ struct rtc_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
     bool rendered = false;
+    // Ray streams (rtc_ctx_trace; rtc_trace.h).  Everything a trace needs it has of its own -- kernel, names, counters, events,
+    // warm-up bookkeeping -- so that the frame schedule and what rtc_ctx_render reports never see it.
+    struct Trace {
+        std::vector<std::string> defs;    // the scene's kernel options as a ray stream takes them (-DRTC_SPEC_TRACE=1); empty: a world without objects
+        std::string family_name, spec_name;  // "trace_kernel<...>", "trace_kernel_spec[...]"
+        bool compile_any_size = false, compile_never = false;  // ScenePlan's: what wants_scene_kernel takes beside the number of rays
+        hipFunction_t fn = nullptr;       // the scene's ray-stream kernel, compiled by the first trace that asks for it
+        std::string fn_id;
+        bool failed = false;              // ... or hiprtc did not deliver it: the ahead-of-time kernel from then on (note says why)
+        std::string note;
+        DeepKernels deep;                 // as rtc_ctx::deep_fn
+        std::string name, id;             // of the last trace's kernel ("" before the first trace of the current scene)
+        uint4* d_counts = nullptr;        // one partial per wave
+        size_t counts_cap = 0;
+        unsigned long long* d_total = nullptr;  // {rays, shaded hits, culled shadow rays} of the last trace
+        std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // around the trace kernels since the last rtc_ctx_stats that reported a trace
+        size_t events_used = 0;
+        std::set<std::pair<const void*, const void*>> warmed;  // (kernel, stream) pairs launched once
+        uint64_t last_n = 0;
+        bool last = false;                // the context's last launch was a trace: rtc_ctx_stats reports it
+    } trace;
     uint32_t last_rows = 0;
     uint32_t last_share_log2 = 0;  // lanes per pixel (log2) the last launch was planned with (rtc_diag_ctx_share_log2)
     uint64_t last_pixels = 0;
@@ -346,20 +369,24 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
     // -DRTC_SPEC_SS=k: the scene's supersampling kernel -- rtc_supersample.h beside the core, its own entry point
     bool ss = false;
     for (const auto& d : defines) ss = ss || d.rfind("-DRTC_SPEC_SS=", 0) == 0;
-    const char* const entry = ss ? "ss_render_kernel_spec" : "render_kernel_spec";
+    // -DRTC_SPEC_TRACE=1: the scene's ray-stream kernel -- rtc_trace.h beside the core, likewise (never both)
+    bool trace = false;
+    for (const auto& d : defines) trace = trace || d.rfind("-DRTC_SPEC_TRACE=", 0) == 0;
+    const char* const entry = ss ? "ss_render_kernel_spec" : trace ? "trace_kernel_spec" : "render_kernel_spec";
     std::string core_file;
     const char* core = k_core_src;
     if (!P.jit_source.empty()) {  // development builds only (Policy)
         if (!read_file(P.jit_source, &core_file)) return fail(RTC_ERR_DEVICE, "scene specialisation: cannot read the kernel source %s", P.jit_source.c_str());
         core = core_file.c_str();
     }
-    // (... and rtc_supersample.h from the same directory, when it is there: an experiment in either header needs no rebuild)
-    std::string ss_file;
-    const char* ss_src = k_ss_src;
-    if (ss && !P.jit_source.empty()) {
+    // (... and rtc_supersample.h / rtc_trace.h from the same directory, when it is there: an experiment in either header needs no rebuild)
+    std::string beside_file;
+    const char* beside_src = trace ? k_trace_src : k_ss_src;  // the header beside the core, whichever it is
+    const char* const beside_name = trace ? "rtc_trace.h" : "rtc_supersample.h";
+    if ((ss || trace) && !P.jit_source.empty()) {
         const size_t slash = P.jit_source.find_last_of('/');
-        const std::string beside = (slash == std::string::npos ? std::string() : P.jit_source.substr(0, slash + 1)) + "rtc_supersample.h";
-        if (read_file(beside, &ss_file)) ss_src = ss_file.c_str();
+        const std::string beside = (slash == std::string::npos ? std::string() : P.jit_source.substr(0, slash + 1)) + beside_name;
+        if (read_file(beside, &beside_file)) beside_src = beside_file.c_str();
     }
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize"};
     for (const auto& d : defines) opts.push_back(d);
@@ -385,6 +412,8 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
     (void)hiprtcVersion(&rtc_major, &rtc_minor);
     opt_text += "hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) + " abi " + std::to_string(RTC_ABI_VERSION) +
                 " args " + std::to_string(sizeof(RenderArgs)) + "\n";
+    // (a ray-stream kernel takes TraceArgs: its layout is rtc_trace.h's text, hashed below, and its size is in the key as well)
+    if (trace) opt_text += "trace args " + std::to_string(sizeof(TraceArgs)) + "\n";
     // (Not in the key: WHICH libhiprtc this process holds.  A Python process that imported torch first compiles with the wheel's
     // bundled compiler, the same script under rocprofv3 -- which puts /opt/rocm/lib first in LD_LIBRARY_PATH -- with the system's;
     // both report one hiprtcVersion and emit different, equally valid code for these kernels (same images, same speed:
@@ -392,15 +421,15 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
     // compiled -- profiles/run_profile.sh compiles first, plainly -- and the id below says which binary it was.)
     char name[64];
     uint64_t source_hash = fnv1a(opt_text, fnv1a(core));
-    if (ss) source_hash = fnv1a(ss_src, source_hash);  // (the plain kernels' names do not move)
+    if (ss || trace) source_hash = fnv1a(beside_src, source_hash);  // (the plain kernels' names do not move)
     snprintf(name, sizeof(name), "spec_%016llx.hsaco", (unsigned long long)source_hash);
     const std::string cache_dir = jit_cache_dir(P), cache_path = cache_dir + "/" + name;
     auto compile = [&](std::string* code) -> rtc_status {
         hiprtcProgram prog;
-        const char* src = ss ? "#include \"rtc_supersample.h\"\n" : "#include \"rtc_kernel_core.h\"\n";
-        const char* headers[] = {core, ss_src};
-        const char* header_names[] = {"rtc_kernel_core.h", "rtc_supersample.h"};
-        if (hiprtcCreateProgram(&prog, src, "rtc_scene_spec.hip", ss ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
+        const char* src = ss ? "#include \"rtc_supersample.h\"\n" : trace ? "#include \"rtc_trace.h\"\n" : "#include \"rtc_kernel_core.h\"\n";
+        const char* headers[] = {core, beside_src};
+        const char* header_names[] = {"rtc_kernel_core.h", beside_name};
+        if (hiprtcCreateProgram(&prog, src, "rtc_scene_spec.hip", (ss || trace) ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
             return fail(RTC_ERR_DEVICE, "hiprtcCreateProgram failed");
         std::vector<const char*> copts;
         for (const auto& o : opts) copts.push_back(o.c_str());
@@ -491,6 +520,12 @@ std::string aot_kernel_id() {
 std::string aot_ss_kernel_id(uint32_t k) {
     char b[48];
     snprintf(b, sizeof(b), "aot_ss%u_%016llx", k, (unsigned long long)fnv1a(k_ss_src, fnv1a(k_core_src)));
+    return b;
+}
+// ... and its ray-stream kernels: the core's text and rtc_trace.h's
+std::string aot_trace_kernel_id() {
+    char b[48];
+    snprintf(b, sizeof(b), "aot_trace_%016llx", (unsigned long long)fnv1a(k_trace_src, fnv1a(k_core_src)));
     return b;
 }
 
@@ -600,35 +635,44 @@ void rtc_ctx_destroy(rtc_ctx* c) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
     }
+    if (c->trace.d_counts) (void)hipFree(c->trace.d_counts);
+    if (c->trace.d_total) (void)hipFree(c->trace.d_total);
+    for (auto& e : c->trace.events) {
+        (void)hipEventDestroy(e.first);
+        (void)hipEventDestroy(e.second);
+    }
     delete c;
 }
 
 // ... and what the pairs in use measured, added up
-static hipError_t sum_event_ms(const rtc_ctx* c, double* sum_ms) {
-    for (size_t i = 0; i < c->events_used; i++) {
+typedef std::vector<std::pair<hipEvent_t, hipEvent_t>> EventPairs;
+static hipError_t sum_event_ms(const EventPairs& events, size_t used, double* sum_ms) {
+    for (size_t i = 0; i < used; i++) {
         float ms = 0.0f;
-        const hipError_t e = hipEventElapsedTime(&ms, c->events[i].first, c->events[i].second);
+        const hipError_t e = hipEventElapsedTime(&ms, events[i].first, events[i].second);
         if (e != hipSuccess) return e;
         *sum_ms += ms;
     }
     return hipSuccess;
 }
-// the next HIP-event pair of the launches since the last rtc_ctx_stats
-static hipError_t next_event_pair(rtc_ctx* c, std::pair<hipEvent_t, hipEvent_t>** out) {
-    if (c->events_used == c->events.size()) {
-        if (c->events.size() >= 4096) {
-            c->events_used = 0;  // nobody is reading the timings: recycle
+static hipError_t sum_event_ms(const rtc_ctx* c, double* sum_ms) { return sum_event_ms(c->events, c->events_used, sum_ms); }
+// the next HIP-event pair of the launches since the last rtc_ctx_stats (the renders' pairs, or the traces')
+static hipError_t next_event_pair(EventPairs& events, size_t& used, std::pair<hipEvent_t, hipEvent_t>** out) {
+    if (used == events.size()) {
+        if (events.size() >= 4096) {
+            used = 0;  // nobody is reading the timings: recycle
         } else {
             std::pair<hipEvent_t, hipEvent_t> e;
             hipError_t err = hipEventCreate(&e.first);
             if (err == hipSuccess) err = hipEventCreate(&e.second);
             if (err != hipSuccess) return err;
-            c->events.push_back(e);
+            events.push_back(e);
         }
     }
-    *out = &c->events[c->events_used++];
+    *out = &events[used++];
     return hipSuccess;
 }
+static hipError_t next_event_pair(rtc_ctx* c, std::pair<hipEvent_t, hipEvent_t>** out) { return next_event_pair(c->events, c->events_used, out); }
 static hipError_t feedback_staging(rtc_ctx* c, size_t bytes, void** p) {  // (the caller has synchronised the device: nothing is using the old one)
     if (c->h_feedback == nullptr || c->h_feedback_cap < bytes) {
         if (c->h_feedback) (void)hipHostFree(c->h_feedback);
@@ -885,6 +929,23 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     c->kernel_name = plan.family_name;
     c->spec_defs = plan.spec_defs;
     c->spec_name = plan.spec_name;
+    {
+        // Ray streams (rtc_ctx_trace): the scene's options with the launch shapes a stream does not have switched off, names of
+        // its own, no kernel yet -- the first trace that wants the scene's kernel compiles it.  (The same for a plain and a
+        // supersampled context: color_at does not read the camera.)
+        rtc_ctx::Trace& t = c->trace;
+        t.defs.clear();
+        // (lane sharing among them: a stream runs one lane per ray, and its kernel must not depend on the size of a frame it does not draw)
+        for (const auto& d : plan.spec_defs)
+            t.defs.push_back((d == "-DRTC_SPEC_BLOCKS_Y=1" || d == "-DRTC_SPEC_RECT=1" || d == "-DRTC_SPEC_SHARE=1") ? d.substr(0, d.size() - 1) + "0" : d);
+        if (!t.defs.empty()) t.defs.push_back("-DRTC_SPEC_TRACE=1");
+        auto renamed = [](const std::string& name) { return name.rfind("render_", 0) == 0 ? "trace_" + name.substr(7) : name; };
+        t.family_name = renamed(plan.family_name), t.spec_name = renamed(plan.spec_name);
+        t.compile_any_size = plan.compile_any_size, t.compile_never = plan.compile_never;
+        t.fn = nullptr, t.failed = false, t.last = false;
+        t.fn_id.clear(), t.note.clear(), t.name.clear(), t.id.clear();
+        t.deep.clear();
+    }
     if (k != 1u) {
         // Scene tiles, the scene rectangle and several blocks per workgroup address the canvas by fine pixels and are not carried
         // over: such scenes are a plain grid here, where the scene-box early-out still applies.
@@ -938,26 +999,27 @@ rtc_status rtc_ctx_set_scene_ss(rtc_ctx* c, const rtc_scene* scene, const rtc_ca
 // (rtc_ctx_set_scene wrote them down) plus -DRTC_SPEC_MAX_DEPTH; the recursion frames of such a kernel all live in per-lane
 // scratch -- the LDS placement of the first levels (a tuning of the depth-5 glass-and-mirror frame) is not carried over.
 // Always a scene-compiled kernel, whatever RTC_AMD_SPECIALIZE says: the ahead-of-time kernels stop at RTC_STACK_DEPTH_BASE.
-static rtc_status deep_kernel(rtc_ctx* c, int32_t depth, hipFunction_t* out) {
+// (`scene_defs`, `kernels`: the render's -- rtc_ctx::spec_defs, deep_fn -- or the ray streams' -- Trace::defs, deep)
+static rtc_status deep_kernel(rtc_ctx* c, int32_t depth, const std::vector<std::string>& scene_defs, rtc_ctx::DeepKernels& kernels, hipFunction_t* out,
+                              std::string* out_id = nullptr) {
     int cap = 2 * RTC_STACK_DEPTH_BASE;
     while (cap < depth) cap *= 2;
     if (cap > RTC_MAX_DEPTH) cap = RTC_MAX_DEPTH;
-    auto it = c->deep_fn.find(cap);
-    if (it != c->deep_fn.end()) {
-        *out = it->second;
-        return RTC_OK;
+    auto it = kernels.find(cap);
+    if (it == kernels.end()) {
+        if (scene_defs.empty()) return fail(RTC_ERR_INVALID_ARG, "depth %d: no kernel options recorded for this scene", depth);
+        std::vector<std::string> defs;
+        for (const auto& d : scene_defs)
+            if (d.rfind("-DRTC_SPEC_LDS_FRAMES=", 0) != 0) defs.push_back(d);
+        defs.push_back("-DRTC_SPEC_MAX_DEPTH=" + std::to_string(cap));
+        hipFunction_t fn = nullptr;
+        std::string id;
+        rtc_status st = jit_get(c->policy, c->device, defs, &fn, &id);
+        if (st != RTC_OK) return st;  // (the message is hiprtc's)
+        it = kernels.emplace(cap, std::make_pair(fn, id)).first;
     }
-    if (c->spec_defs.empty()) return fail(RTC_ERR_INVALID_ARG, "depth %d: no kernel options recorded for this scene", depth);
-    std::vector<std::string> defs;
-    for (const auto& d : c->spec_defs)
-        if (d.rfind("-DRTC_SPEC_LDS_FRAMES=", 0) != 0) defs.push_back(d);
-    defs.push_back("-DRTC_SPEC_MAX_DEPTH=" + std::to_string(cap));
-    hipFunction_t fn = nullptr;
-    std::string id;
-    rtc_status st = jit_get(c->policy, c->device, defs, &fn, &id);
-    if (st != RTC_OK) return st;  // (the message is hiprtc's)
-    c->deep_fn[cap] = fn;
-    *out = fn;
+    *out = it->second.first;
+    if (out_id) *out_id = it->second.second;
     return RTC_OK;
 }
 
@@ -1345,7 +1407,7 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     // ... RTC_MAX_DEPTH levels of per-lane scratch -- on first use, and kept with the context.
     hipFunction_t spec_fn = c->spec_fn;
     if (depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) depth = RTC_STACK_DEPTH_BASE;
-    if (depth > RTC_STACK_DEPTH_BASE && rows > 0u) RTC_TRY(deep_kernel(c, depth, &spec_fn));
+    if (depth > RTC_STACK_DEPTH_BASE && rows > 0u) RTC_TRY(deep_kernel(c, depth, c->spec_defs, c->deep_fn, &spec_fn));
     const bool shares = spec_fn && c->spec_shares;  // only kernels compiled for it share lanes
     // (supersampled: capped so that a k x k group lies in one wave's tile, rtc_launch_plan.h)
     const uint32_t share_log2 = shares ? std::min(choose_share_log2(c->hdr, rows, P, progress == nullptr), ss_max_share_log2(ss_k)) : 0u;
@@ -1357,6 +1419,7 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     const bool area_list = shares && c->hdr.light_kind == RTC_LIGHT_RECT && share_log2 != 0u && P.block_feedback && progress == nullptr;
     const bool list_words_fit = width <= 65532u && rows <= 131068u;  // (tile_word)
     if ((mesh_list || area_list) && P.share_log2 < 0 && list_words_fit && rows > 0u) RTC_TRY(use_block_list(c, q, rows, depth, share_log2, mesh_list, stream, &lp, &L));
+    c->trace.last = false;       // (rtc_ctx_stats reports renders again)
     c->last_rows = rows / ss_k;  // (rows written to the caller's buffer)
     c->last_share_log2 = share_log2;
     c->last_pixels = traced_pixels(width, height, q);
@@ -1584,26 +1647,175 @@ rtc_status rtc_ctx_render_hits(rtc_ctx* c, const rtc_partition* part, const rtc_
     return RTC_OK;
 }
 
-rtc_status rtc_ctx_stats(rtc_ctx* c, rtc_stats* out) {
-    if (!c || !out) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_stats: null argument");
-    std::memset(out, 0, sizeof(*out));
-    out->rows = c->last_rows;
-    out->pixels = c->last_pixels;
-    if (!c->rendered) return RTC_OK;
+}  // extern "C"
+
+// ---- ray streams (rtc_trace.h) ---------------------------------------------------
+// The scene's ray-stream kernel for this trace, or null: the ahead-of-time family.  `want`: the specialisation policy asks for
+// the scene's own kernel (rtc_ctx_set_scene's policy with the number of rays in the place of the frame's pixels); deeper than
+// the ahead-of-time stack it is always a scene kernel, compiled with a longer one (deep_kernel).  Compiled on first use.
+static rtc_status trace_kernel_for(rtc_ctx* c, int32_t depth, bool want, hipFunction_t* fn, std::string* id) {
+    rtc_ctx::Trace& t = c->trace;
+    *fn = nullptr;
+    if (depth > RTC_STACK_DEPTH_BASE) return deep_kernel(c, depth, t.defs, t.deep, fn, id);
+    if (!want || t.failed) return RTC_OK;
+    if (t.fn == nullptr) {
+        const rtc_status jst = jit_get(c->policy, c->device, t.defs, &t.fn, &t.fn_id);
+        if (jst != RTC_OK) {  // as jit_failed: RTC_AMD_SPECIALIZE=1 an error, else the ahead-of-time kernel, and say so
+            t.fn = nullptr;
+            t.failed = true;
+            t.note = rtc_last_error();
+            if (c->policy.specialise == 1) return jst;
+            static bool warned = false;
+            if (!warned && !c->policy.quiet) {
+                warned = true;
+                std::fprintf(stderr, "librtc_amd: scene specialisation unavailable, tracing with the slower ahead-of-time kernel %s: %.300s\n",
+                             t.family_name.c_str(), t.note.c_str());
+            }
+            return RTC_OK;
+        }
+    }
+    *fn = t.fn, *id = t.fn_id;
+    return RTC_OK;
+}
+
+static hipError_t launch_trace(rtc_ctx* c, hipFunction_t fn, uint32_t n_workgroups, hipStream_t stream, TraceArgs& a) {
+    if (fn) {
+        void* params[] = {&a};
+        return hipModuleLaunchKernel(fn, n_workgroups, 1, 1, 256, 1, 1, 0, stream, params, nullptr);
+    }
+    dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+        hipLaunchKernelGGL((trace_kernel<decltype(nobj)::value, decltype(simple)::value>), dim3(n_workgroups), dim3(256), 0, stream, a);
+    });
+    return hipGetLastError();
+}
+
+extern "C" {
+
+// The argument checks come first, the context's last among them: all are decided on the host, before any device call.
+rtc_status rtc_ctx_trace(rtc_ctx* c, int32_t depth, const void* d_origins, const void* d_directions, const void* d_keys, uint32_t n,
+                         void* d_out_rgb, void* stream_) {
+    if (n > 0u && (!d_origins || !d_directions)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: null ray buffer");
+    if (n > 0u && !d_out_rgb) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: null output buffer");
+    if (((uintptr_t)d_origins & 15u) || ((uintptr_t)d_directions & 15u))
+        return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: origins and directions must be 16-byte aligned");
+    if (((uintptr_t)d_keys & 3u) || ((uintptr_t)d_out_rgb & 3u)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: keys and output must be 4-byte aligned");
+    if (depth < 0 || depth > RTC_MAX_DEPTH) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: depth %d outside [0, %d]", depth, RTC_MAX_DEPTH);
+    if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: ctx is NULL");
+    if (!c->has_scene) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: no scene set");
+    if (n == 0u) return RTC_OK;
+    // (rtc_ctx_set_scene refuses RTC_JITTER_SEQUENCE lights: no resident scene has one)
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    rtc_ctx::Trace& t = c->trace;
+    const Policy& P = c->policy;
+    if (depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) depth = RTC_STACK_DEPTH_BASE;  // (as rtc_ctx_render)
+    const bool want = !t.defs.empty() && wants_scene_kernel(P, n, t.compile_any_size, t.compile_never);
+    hipFunction_t fn = nullptr;
+    std::string id;
+    RTC_TRY(trace_kernel_for(c, depth, want, &fn, &id));
+    t.name = fn ? t.spec_name : t.family_name;
+    t.id = fn ? id : aot_trace_kernel_id();
+    // workspaces (grow-only; a trace in flight on this stream may still be writing the old partials: grow frees, which waits)
+    const uint32_t n_workgroups = (uint32_t)(((uint64_t)n + 255u) / 256u);
+    const size_t n_counts = (size_t)n_workgroups * 4u;
+    HIP_TRY(grow(&t.d_counts, &t.counts_cap, n_counts));
+    if (!t.d_total) HIP_TRY(hipMalloc((void**)&t.d_total, 3 * sizeof(unsigned long long)));
+    TraceArgs a;
+    a.hdr = c->hdr;
+    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.origins = (const float4*)d_origins, a.directions = (const float4*)d_directions, a.keys = (const uint32_t*)d_keys;
+    a.out = (float*)d_out_rgb;
+    a.wave_counts = t.d_counts;
+    a.total = t.d_total;
+    a.n = n;
+    a.depth = depth;
+    // warm up (warm_up: a code object's first launch on a queue, in front of the events), time, launch, sum
+    const auto key = std::make_pair(fn ? (const void*)fn : aot_family(c).key(), (const void*)stream);
+    if (t.warmed.insert(key).second) {
+        TraceArgs w = a;
+        w.n = 0u;
+        HIP_TRY(launch_trace(c, fn, 1u, stream, w));
+    }
+    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    HIP_TRY(next_event_pair(t.events, t.events_used, &ev));
+    HIP_TRY(hipEventRecord(ev->first, stream));
+    HIP_TRY(launch_trace(c, fn, n_workgroups, stream, a));
+    HIP_TRY(hipEventRecord(ev->second, stream));
+    hipLaunchKernelGGL(sum_counts_kernel, dim3((uint32_t)((n_counts + SUM_COUNTS_SLICE - 1) / SUM_COUNTS_SLICE)), dim3(1024), 0, stream, t.d_counts,
+                       (uint32_t)n_counts, t.d_total, 0ull);
+    HIP_TRY(hipGetLastError());
+    t.last_n = n;
+    t.last = true;
+    return RTC_OK;
+}
+
+rtc_status rtc_ctx_camera_rays(rtc_ctx* c, const rtc_camera* camera, uint32_t y0, uint32_t n_rows, void* d_origins, void* d_directions, void* d_keys,
+                               void* stream_) {
+    if (!camera) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_camera_rays: camera is NULL");
+    if (((uintptr_t)d_origins & 15u) || ((uintptr_t)d_directions & 15u))
+        return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_camera_rays: origins and directions must be 16-byte aligned");
+    if ((uintptr_t)d_keys & 3u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_camera_rays: keys must be 4-byte aligned");
+    if (camera->width == 0 || camera->height == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_camera_rays: empty canvas");
+    if ((uint64_t)y0 + n_rows > camera->height) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_camera_rays: rows [%u, %u + %u) of %u", y0, y0, n_rows, camera->height);
+    if ((uint64_t)n_rows * camera->width > 0xffffffffull) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_camera_rays: %u rows of %u rays are more than 2^32 - 1", n_rows, camera->width);
+    if (!is_affine(camera->inv)) return fail(RTC_ERR_UNSUPPORTED, "camera inverse transform is not affine");
+    if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_camera_rays: ctx is NULL");
+    if (n_rows == 0u || (!d_origins && !d_directions && !d_keys)) return RTC_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    CameraRaysArgs a;
+    std::memset(&a.hdr, 0, sizeof(a.hdr));  // (has_scene_box = 0)
+    // the camera as flatten packs it (rtc_scene_prep.h pack_camera)
+    a.hdr.width = camera->width, a.hdr.height = camera->height;
+    a.hdr.half_w = camera->half_width, a.hdr.half_h = camera->half_height, a.hdr.pixel_size = camera->pixel_size;
+    std::memcpy(a.hdr.cam, camera->inv, sizeof(float) * 12);
+    const float zero[4] = {0.0f, 0.0f, 0.0f, 1.0f};
+    float cam_origin[4];
+    mat_vec4(camera->inv, zero, cam_origin);
+    for (int k = 0; k < 3; k++) a.hdr.cam_origin[k] = cam_origin[k];
+    a.origins = (float4*)d_origins, a.directions = (float4*)d_directions, a.keys = (uint32_t*)d_keys;
+    a.y0 = y0, a.n_rows = n_rows;
+    const uint64_t n = (uint64_t)n_rows * camera->width;
+    hipLaunchKernelGGL(camera_rays_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream_, a);
+    HIP_TRY(hipGetLastError());
+    return RTC_OK;
+}
+
+const char* rtc_ctx_trace_kernel_name(rtc_ctx* c) { return c ? c->trace.name.c_str() : ""; }
+const char* rtc_ctx_trace_kernel_id(rtc_ctx* c) { return c ? c->trace.id.c_str() : ""; }
+
+}  // extern "C"
+// rtc_ctx_stats' read-out, of the renders or of the traces: waits for the device, the last launch's counters (`total`), the mean
+// kernel time of the launches since the last read-out (`events`, which start over)
+static rtc_status read_launch_stats(rtc_ctx* c, const unsigned long long* d_total, const EventPairs& events, size_t& events_used, const std::string& note,
+                                    rtc_stats* out) {
     HIP_TRY(hipSetDevice(c->device));
     unsigned long long total[3] = {0, 0, 0};
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(total, c->d_total, sizeof(total), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(total, d_total, sizeof(total), hipMemcpyDeviceToHost));
     double sum_ms = 0.0;
-    HIP_TRY(sum_event_ms(c, &sum_ms));
+    HIP_TRY(sum_event_ms(events, events_used, &sum_ms));
     out->rays = total[0];
     out->shaded_hits = total[1];
     out->culled_shadow_rays = total[2];
-    out->launches = (uint32_t)c->events_used;
-    out->kernel_ms = c->events_used ? (float)(sum_ms / (double)c->events_used) : 0.0f;
-    out->flags = c->jit_note.empty() ? 0u : RTC_STATS_JIT_FALLBACK;
-    c->events_used = 0;
+    out->launches = (uint32_t)events_used;
+    out->kernel_ms = events_used ? (float)(sum_ms / (double)events_used) : 0.0f;
+    out->flags = note.empty() ? 0u : RTC_STATS_JIT_FALLBACK;
+    events_used = 0;
     return RTC_OK;
+}
+extern "C" {
+rtc_status rtc_ctx_stats(rtc_ctx* c, rtc_stats* out) {
+    if (!c || !out) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_stats: null argument");
+    std::memset(out, 0, sizeof(*out));
+    if (c->trace.last) {  // the last launch was rtc_ctx_trace: its counters, and the traces' own events
+        rtc_ctx::Trace& t = c->trace;
+        out->pixels = t.last_n;
+        return read_launch_stats(c, t.d_total, t.events, t.events_used, t.note, out);
+    }
+    out->rows = c->last_rows;
+    out->pixels = c->last_pixels;
+    if (!c->rendered) return RTC_OK;
+    return read_launch_stats(c, c->d_total, c->events, c->events_used, c->jit_note, out);
 }
 
 const char* rtc_ctx_kernel_name(rtc_ctx* c) {

@@ -1434,6 +1434,9 @@ struct ScenePlan {
     std::vector<std::string> spec_defs;
     std::string spec_name;
     bool compile_now = false;
+    // ... and the policy's two exceptions to "from 2^18 pixels", which rtc_ctx_trace applies to its number of rays: worlds with divided
+    // meshes are compiled whatever the size, a mixed list of many objects (and a world without objects) never
+    bool compile_any_size = false, compile_never = false;
 };
 
 // how many tiles of a mask are set
@@ -1554,8 +1557,13 @@ inline bool like_objects(const std::vector<float4>& soa, const SceneHdr& hdr, ui
         if ((object_bits(soa, hdr, i) & ~(uint32_t)SHAPE_UNIFORM) != *first) return false;
     return n > 0;
 }
-inline bool large_frame(const Policy& P, const SceneHdr& hdr, bool or_else = false) {  // RTC_AMD_SPECIALIZE: 1 always, 2 from 2^18 pixels
-    return P.specialise == 1 || (P.specialise == 2 && ((uint64_t)hdr.width * hdr.height >= (1ull << 18) || or_else));
+// Does the policy want the scene's own kernel for `count` pixels (rtc_ctx_set_scene) or rays (rtc_ctx_trace)?  RTC_AMD_SPECIALIZE: 1
+// always, 2 from 2^18 -- or whatever the count, `any_size` -- and `never` for the scenes that are left to the ahead-of-time loop.
+inline bool wants_scene_kernel(const Policy& P, uint64_t count, bool any_size, bool never) {
+    return !never && (P.specialise == 1 || (P.specialise == 2 && (count >= (1ull << 18) || any_size)));
+}
+inline bool frame_wants_scene_kernel(const Policy& P, const SceneHdr& hdr, const ScenePlan& p) {
+    return wants_scene_kernel(P, (uint64_t)hdr.width * hdr.height, p.compile_any_size, p.compile_never);
 }
 
 // a traversal stream (GroupShapes, or the library's own hierarchy): packet walk, compiled per scene like the flat kernels
@@ -1563,7 +1571,8 @@ inline void plan_tree_kernel(const Policy& P, const SceneHdr& hdr, const std::ve
                              const CommonDefs& d, ScenePlan* p) {
     // (worlds with divided meshes are compiled whatever the frame's size: the ahead-of-time walk has neither the
     // triangle pre-culling specialisation nor the leaf-sharing lanes -- mesh 512 x 384: 7.9 ms)
-    p->compile_now = large_frame(P, hdr, hdr.max_leaf_run >= 16u);
+    p->compile_any_size = hdr.max_leaf_run >= 16u;
+    p->compile_now = frame_wants_scene_kernel(P, hdr, *p);
     // the traversal kernel compiled for this scene's light kind / jitter mode / pattern use and, when every object
     // shares one kind / flags word (a triangle mesh, a grid of spheres), for that word as well
     uint32_t first = 0u;
@@ -1590,7 +1599,7 @@ inline void plan_tree_kernel(const Policy& P, const SceneHdr& hdr, const std::ve
 inline void plan_small_kernel(const Policy& P, const SceneHdr& hdr, const std::vector<float4>& soa, const MaterialFacts& f, const CommonDefs& d, ScenePlan* p) {
     const uint32_t n = hdr.n_objects;
     std::vector<std::string>& defs = p->spec_defs;
-    p->compile_now = large_frame(P, hdr);
+    p->compile_now = frame_wants_scene_kernel(P, hdr, *p);
     std::string list;
     for (uint32_t i = 0; i < n; i++) list += (i ? "," : "") + hex_word(object_bits(soa, hdr, i));
     defs = {"-DRTC_SPEC_LIST=" + list, "-DRTC_SPEC_NOBJ=" + std::to_string(n), std::string("-DRTC_SPEC_SIMPLE=") + (p->simple ? "1" : "0")};
@@ -1644,7 +1653,8 @@ inline void plan_small_kernel(const Policy& P, const SceneHdr& hdr, const std::v
 inline void plan_many_kernel(const Policy& P, const SceneHdr& hdr, const std::vector<float4>& soa, const MaterialFacts& f, const CommonDefs& d, ScenePlan* p) {
     uint32_t first = 0u;
     const bool uniform = like_objects(soa, hdr, &first);
-    p->compile_now = uniform && large_frame(P, hdr);
+    p->compile_never = !uniform;
+    p->compile_now = frame_wants_scene_kernel(P, hdr, *p);
     const std::string b = hex_word(first);
     p->spec_defs = {"-DRTC_SPEC_LIST=" + b, uniform ? "-DRTC_SPEC_UNIFORM_BITS=" + b : std::string("-DRTC_SPEC_RUNTIME_BITS=1"),
                     "-DRTC_SPEC_NOBJ=0", "-DRTC_SPEC_SIMPLE=0"};
@@ -1682,6 +1692,7 @@ inline ScenePlan plan_scene(const Policy& P, const SceneHdr& hdr, const std::vec
     const CommonDefs defs = common_defs(hdr, p, facts);
     const KernelFamily family = aot_family(hdr.n_trav, n, p.simple);
     p.family_name = family.name();
+    p.compile_never = n == 0u;
     if (hdr.n_trav) {
         const std::string how = scene->n_groups ? "tree" : "tree,bvh";
         p.family_name = family.name(how.c_str());

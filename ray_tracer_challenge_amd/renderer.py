@@ -107,6 +107,69 @@ class Renderer:
                                               C.c_void_p(s.cuda_stream)), self._lib)
         return res
 
+    def _ray_tensor(self, t, what, n=None):
+        # (checked, not asserted: the raw pointer goes to a kernel that reads n x 16 bytes through it, 16 at a time)
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 4
+                and t.is_contiguous() and t.data_ptr() % 16 == 0 and (n is None or t.shape[0] == n)):
+            raise ValueError("%s must be a contiguous, 16-byte aligned float32 CUDA tensor (n, 4) on %s" % (what, self.device))
+        return int(t.shape[0])
+
+    def trace(self, origins, directions, depth, keys=None, out=None, stream=None):
+        """World::color_at for the caller's rays against the resident scene (rtc_ctx_trace) on `stream` (default: torch's
+        current stream); asynchronous.  origins, directions: (n, 4) float32 on the renderer's device (x, y, z are read); the
+        direction is used as given.  keys: (n,) int32 / uint32 -- ray i draws its light samples as pixel keys[i] (None: i).
+        -> (n, 3) float32.
+        With `stream` given and no `out`, the result is allocated by torch on its CURRENT stream and written on `stream`: keep it
+        alive until `stream` has been waited for (or pass an `out` made on `stream`, or call out.record_stream(stream)).  One
+        stream at a time per renderer: two traces in flight on different streams race on what stats() reports."""
+        n = self._ray_tensor(origins, "origins")
+        self._ray_tensor(directions, "directions", n)
+        if keys is not None:
+            ok = torch.is_tensor(keys) and keys.is_cuda and keys.device == self.device and keys.dim() == 1 and keys.shape[0] == n and keys.is_contiguous()
+            if not (ok and keys.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and keys.data_ptr() % 4 == 0):
+                raise ValueError("keys must be a contiguous int32 or uint32 CUDA tensor (n,) on %s" % self.device)
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.float32 and out.is_contiguous()
+                and out.numel() == 3 * n):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of %d x 3 on %s" % (n, self.device))
+        if not 0 <= n < 2 ** 32:
+            raise ValueError("at most 2^32 - 1 rays a call")
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        L.check(self._lib.rtc_ctx_trace(self._ctx, int(depth), C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                        C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(s.cuda_stream)), self._lib)
+        return out
+
+    def camera_rays(self, camera=None, y0=0, n_rows=None, stream=None):
+        """ray_for_pixel of `camera` (default: the camera last set) for image rows [y0, y0 + n_rows) (default: to the last),
+        made on the device by the render kernels' own function (rtc_ctx_camera_rays), in image order and in trace()'s
+        layout.  -> (origins (n, 4), directions (n, 4), keys (n,) int32: y * width + x)."""
+        camera = self._keep[1] if camera is None else camera
+        y0 = int(y0)
+        n_rows = camera.height - y0 if n_rows is None else int(n_rows)
+        if y0 < 0 or n_rows < 0 or y0 + n_rows > camera.height:
+            raise ValueError("rows [%d, %d) of a camera of %d" % (y0, y0 + n_rows, camera.height))
+        n = n_rows * camera.width
+        origins = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        directions = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        keys = torch.empty((n,), dtype=torch.int32, device=self.device)
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        L.check(self._lib.rtc_ctx_camera_rays(self._ctx, C.byref(camera._cam), y0, n_rows, C.c_void_p(origins.data_ptr()),
+                                              C.c_void_p(directions.data_ptr()), C.c_void_p(keys.data_ptr()), C.c_void_p(s.cuda_stream)),
+                self._lib)
+        return origins, directions, keys
+
+    @property
+    def trace_kernel_name(self):
+        """The kernel of the last trace() ("" before the first trace of the current scene)."""
+        return self._lib.rtc_ctx_trace_kernel_name(self._ctx).decode()
+
+    @property
+    def trace_kernel_id(self):
+        """Names the code object of the last trace(), as kernel_id does for renders."""
+        return self._lib.rtc_ctx_trace_kernel_id(self._ctx).decode()
+
     @property
     def kernel_name(self):
         return self._lib.rtc_ctx_kernel_name(self._ctx).decode()

@@ -6,9 +6,11 @@
 Per kernel: VGPRs, SGPRs, scratch bytes per lane, LDS bytes (the code object's metadata), instructions and `scratch_`
 instructions (counted in the assembly).  Covered: every kernel of the ahead-of-time library (rtc_device.hip, rtc_oneshot.hip,
 build.py's flags, device only); the scene kernels of the eight profiled workloads (tools/check_profile_ids.sh), their options
-taken from World.scene_plan(camera) and compiled as tools/spec_asm.sh does; and C3's supersampling scene kernel at k = 2
-(the fine camera's options as rtc_ctx_set_scene_ss rewrites them).  With two directories the rows are compared and every
-figure that differs is marked.
+taken from World.scene_plan(camera) and compiled as tools/spec_asm.sh does; C3's supersampling scene kernel at k = 2
+(the fine camera's options as rtc_ctx_set_scene_ss rewrites them); and, where the directory has rtc_trace.h, the same eight
+scenes' ray-stream kernels (the options as rtc_ctx_set_scene rewrites them for rtc_ctx_trace).  With two directories the rows
+are compared and every figure that differs is marked.  --trace-pairs FILE: every ray-stream kernel of the first directory next
+to its render sibling (profiles/trace_codegen.txt).
 
 Build first (python -m ray_tracer_challenge_amd.build --all, in this tree and in the tree of any other directory named): the
 scenes' option lists come from this tree's library, and rtc_device.hip includes the literal the build generates beside it.
@@ -32,14 +34,16 @@ SCENES = [("C3", "soft_shadows", 4096, 4096), ("C4", "glass_and_mirror", 4096, 4
 FIGURES = ("vgpr", "sgpr", "scratch", "lds", "insts", "scratch_insts")
 
 
-def scene_defs(name, w, h, ss=0):
+def scene_defs(name, w, h, ss=0, trace=False):
     kw = {"jitter": ("hashed", scenes.DEFAULT_SEED)} if name == "soft_shadows" else {}
     world, camera, _ = getattr(scenes, name)(w, h, **kw)
     if ss:
         camera = camera.supersampled(ss)
     defs = world.scene_plan(camera)[1]["spec_defs"].split()
-    if ss:
-        defs = [d[:-1] + "0" if d in ("-DRTC_SPEC_BLOCKS_Y=1", "-DRTC_SPEC_RECT=1") else d for d in defs] + ["-DRTC_SPEC_SS=%d" % ss]
+    if ss or trace:
+        off = ("-DRTC_SPEC_BLOCKS_Y=1", "-DRTC_SPEC_RECT=1") + (("-DRTC_SPEC_SHARE=1",) if trace else ())  # (a stream: one lane per ray)
+        defs = [d[:-1] + "0" if d in off else d for d in defs]
+        defs.append("-DRTC_SPEC_SS=%d" % ss if ss else "-DRTC_SPEC_TRACE=1")
     if not any(d.startswith("-DRTC_WAVES_PER_SIMD=") for d in defs):
         defs.append("-DRTC_WAVES_PER_SIMD=7")
     return defs
@@ -83,6 +87,11 @@ def table(csrc, tmp, tag):
     for scene, name, w, h in SCENES:
         jobs.append(("scene " + scene, spec, scene_defs(name, w, h)))
     jobs.append(("scene C3 ss=2", ss, scene_defs("soft_shadows", 4096, 4096, ss=2)))
+    if os.path.exists(os.path.join(csrc, "rtc_trace.h")):
+        trace = os.path.join(tmp, "trace.hip")
+        open(trace, "w").write('#include "rtc_trace.h"\n')
+        for scene, name, w, h in SCENES:
+            jobs.append(("scene %s trace" % scene, trace, scene_defs(name, w, h, trace=True)))
     with ThreadPoolExecutor(8) as ex:
         files = list(ex.map(lambda j: compile_asm(csrc, j[1], j[2], os.path.join(tmp, "%s_%s.s" % (tag, j[0].replace(" ", "_").replace("=", "")))), jobs))
     rows = {}
@@ -90,6 +99,8 @@ def table(csrc, tmp, tag):
         r = read_asm(f)
         pretty = demangle(list(r))
         for k, v in r.items():
+            if kind.endswith(" trace") and not pretty[k].startswith("trace_"):
+                continue  # (the core's render_kernel_spec is in that compile as well: not a kernel anything launches)
             rows["%s: %s" % (kind, pretty[k])] = v
     return rows
 
@@ -98,6 +109,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("csrc", nargs="+")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--trace-pairs", default=None, help="write the ray-stream kernels next to their render siblings here")
     args = ap.parse_args()
     own = os.path.join(ROOT, "ray_tracer_challenge_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
@@ -122,6 +134,17 @@ def main():
     print(text, end="")
     if args.out:
         open(args.out, "w").write(text)
+    if args.trace_pairs:
+        t = tables[0]
+        pairs = ["ray-stream kernels (csrc/rtc_trace.h) next to their render siblings: VGPRs / SGPRs / scratch bytes per lane / LDS bytes / "
+                 "instructions / scratch_ instructions", "%-62s %-36s   |   %-36s %s" % ("kernel", "trace", "render sibling", "scratch, trace - render")]
+        for k in sorted(t):
+            if ": trace_kernel" not in k:
+                continue
+            sib = k.replace(" trace: trace_kernel_spec", ": render_kernel_spec").replace(": trace_kernel<", ": render_kernel<")
+            cells = [" / ".join(str(t[n][f]) for f in FIGURES) if n in t else "-" for n in (k, sib)]
+            pairs.append("%-62s %-36s   |   %-36s %+d B" % (k, cells[0], cells[1], t[k]["scratch"] - t[sib]["scratch"] if sib in t else 0))
+        open(args.trace_pairs, "w").write("\n".join(pairs) + "\n")
 
 
 if __name__ == "__main__":
