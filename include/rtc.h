@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define RTC_ABI_VERSION 8
+#define RTC_ABI_VERSION 8 /* (rtc_ctx_trace_hits and rtc_ctx_is_shadowed were added at 8: two entry points more, no struct and
+                             no existing signature changed, so callers built against the earlier 8 run unchanged) */
 /* reflection_recursion_depth (camera.rs:76: any i16; reference default 5, constants.rs:4; its author renders
  * reflect_refract at 20).  Accepted: 0 .. RTC_MAX_DEPTH.  The kernels keep one frame per suspended shade_hit
  * (world.rs:62-86); up to RTC_STACK_DEPTH_BASE levels every kernel has them, above that the scene's kernel is compiled
@@ -498,6 +499,32 @@ rtc_status rtc_ctx_camera_rays(rtc_ctx* ctx, const rtc_camera* camera, uint32_t 
  * "aot_trace_..." or "spec_..." ids of their own, as rtc_ctx_kernel_name / _id).  "" before the first trace of the current scene. */
 const char* rtc_ctx_trace_kernel_name(rtc_ctx* ctx);
 const char* rtc_ctx_trace_kernel_id(rtc_ctx* ctx);
+/* The first hits (see "First-hit buffers" above) of n caller rays against the context's resident scene: the rays and keys
+ * are rtc_ctx_trace's (DEVICE pointers, x, y, z read, the direction used as given, d_keys NULL: ray i draws as pixel i), the
+ * planes are rtc_ctx_render_hits' (`d_out` a host struct of DEVICE pointers, NULL = not wanted), element i belonging to ray
+ * i.  A miss stores object = -1 and zeros; every requested plane is written for all n elements and nothing behind them; a
+ * plane that is not requested is not touched; w as rtc_ctx_render_hits writes it; `light` is drawn as pixel d_keys[i], path
+ * 1 -- the key a render gives that pixel's primary hit.  Asynchronous on `stream`.
+ * One lane per ray, ray i in thread i, ahead-of-time kernels of rtc_ctx_render_hits' families; every shortcut that acts
+ * inside the scene's intersection and light code applies as in a render.  A supersampled context answers like any other:
+ * the camera is not read.
+ * Like rtc_ctx_render_hits it leaves rtc_ctx_stats, the trace's counters, block lists, measured wave times, warm-up
+ * bookkeeping and rtc_ctx_kernel_name / _id / rtc_ctx_trace_kernel_name / _id alone: a render or a trace after it is
+ * scheduled and reported as if this call had not happened.
+ * RTC_ERR_INVALID_ARG, decided before any device call, in this order, so that each is reported by name whatever else is
+ * wrong: a null ray pointer or a null `d_out` with n > 0; no plane requested; alignment -- origins, directions and the
+ * vector planes 16 bytes, n1n2 8, keys and the scalar planes 4; a null context; no scene set.  n == 0 with these pointer
+ * checks passed: RTC_OK, nothing is launched (the context is not looked at). */
+rtc_status rtc_ctx_trace_hits(rtc_ctx* ctx, const void* d_origins, const void* d_directions, const void* d_keys,
+                              uint32_t n, const rtc_hit_planes* d_out, void* stream);
+/* World::is_shadowed(light_position, point) (world.rs:104-119) for n pairs against the context's resident scene: is the
+ * nearest thing between the two a shadow caster?  Not only for lights: mutual visibility of two points, ambient occlusion.
+ * DEVICE pointers: d_light_positions, d_points n x 4 f32 (16-byte aligned; x, y, z are read); d_out_i32 n x int32, 0 / 1 as
+ * rtc_is_shadowed writes it.  Asynchronous on `stream`; leaves the context alone as rtc_ctx_trace_hits does.
+ * RTC_ERR_INVALID_ARG, decided before any device call, in this order: a null pair or output pointer with n > 0; alignment
+ * (16 bytes for the pairs, 4 for the output); a null context; no scene set.  n == 0 as for rtc_ctx_trace_hits. */
+rtc_status rtc_ctx_is_shadowed(rtc_ctx* ctx, const void* d_light_positions, const void* d_points, uint32_t n,
+                               void* d_out_i32, void* stream);
 
 /* Batched Light::intensity_at (light.rs:10) for n world points (n*4 f32). */
 rtc_status rtc_intensity_at(const rtc_scene* scene, const float* points, uint32_t n, int32_t device,

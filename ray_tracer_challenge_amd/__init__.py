@@ -6,6 +6,9 @@ host-side scene math needed to feed it bit-identical inputs.  This package is
 the Python mirror of the reference's World/Shape/Material/Camera/Canvas API on
 top of that ABI.  The shared library must be built first
 (`python -m ray_tracer_challenge_amd.build`); there is no fallback path.
+
+Device-resident work goes through `renderer.Renderer`: render / render_hits for the camera's pixels, trace / trace_hits /
+is_shadowed for rays and point pairs the caller brings as torch tensors (`rays` makes some, `rays.reflected` the next bounce).
 """
 from ._lib import RtcError, lib  # noqa: F401
 from .api import *  # noqa: F401,F403

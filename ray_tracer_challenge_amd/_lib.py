@@ -175,6 +175,8 @@ SIGNATURES = {
                                       C.c_void_p]),
     "rtc_ctx_trace_kernel_name": (C.c_char_p, [C.c_void_p]),
     "rtc_ctx_trace_kernel_id": (C.c_char_p, [C.c_void_p]),
+    "rtc_ctx_trace_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(rtc_hit_planes), C.c_void_p]),
+    "rtc_ctx_is_shadowed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rtc_intensity_at": (C.c_int, [C.POINTER(rtc_scene), FP, C.c_uint32, C.c_int32, FP]),
     "rtc_is_shadowed": (C.c_int, [C.POINTER(rtc_scene), FP, FP, C.c_uint32, C.c_int32, C.POINTER(C.c_int32)]),
     "rtc_point_on_light": (C.c_int, [C.POINTER(rtc_light), C.POINTER(C.c_int32), C.c_uint32, C.c_int32, FP]),

@@ -1780,6 +1780,74 @@ rtc_status rtc_ctx_camera_rays(rtc_ctx* c, const rtc_camera* camera, uint32_t y0
     return RTC_OK;
 }
 
+// First hits of the caller's rays (rtc_hits.h trace_hits_kernel).  As rtc_ctx_render_hits: the context's scene, none of its
+// render or trace state -- no counters, no events, no warm-up bookkeeping, no names.  The argument checks in the header's
+// order, all on the host.
+rtc_status rtc_ctx_trace_hits(rtc_ctx* c, const void* d_origins, const void* d_directions, const void* d_keys, uint32_t n,
+                              const rtc_hit_planes* d_out, void* stream_) {
+    if (n > 0u && (!d_origins || !d_directions)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: null ray buffer");
+    if (n > 0u && !d_out) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: null output (no rtc_hit_planes)");
+    HitPlanes planes;
+    std::memset(&planes, 0, sizeof(planes));
+    if (d_out && !hit_planes_view(d_out, &planes)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: no plane requested");
+    if (((uintptr_t)d_origins & 15u) || ((uintptr_t)d_directions & 15u))
+        return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: origins and directions must be 16-byte aligned");
+    const void* const vector_planes[] = {planes.point, planes.eye, planes.normal, planes.reflectv, planes.over_point, planes.under_point};
+    for (const void* p : vector_planes)
+        if ((uintptr_t)p & 15u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: the vector planes must be 16-byte aligned");
+    if ((uintptr_t)planes.n1n2 & 7u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: n1n2 must be 8-byte aligned");
+    const void* const scalars[] = {d_keys, planes.object, planes.distance, planes.inside, planes.light};
+    for (const void* p : scalars)
+        if ((uintptr_t)p & 3u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: keys and the scalar planes must be 4-byte aligned");
+    if (n == 0u) return RTC_OK;  // nothing to trace, whatever the context
+    if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: ctx is NULL");
+    if (!c->has_scene) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: no scene set");
+    // (rtc_ctx_set_scene refuses RTC_JITTER_SEQUENCE lights: no resident scene has one)
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    TraceHitsArgs a;
+    a.hdr = c->hdr;
+    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.origins = (const float4*)d_origins, a.directions = (const float4*)d_directions, a.keys = (const uint32_t*)d_keys;
+    a.planes = planes;
+    a.n = n;
+    const bool light = planes.light != nullptr;
+    const dim3 grid((uint32_t)(((uint64_t)n + 255u) / 256u)), block(256);
+    // rtc_ctx_render_hits' families (the geometry-only kernels exist once per object-loop family)
+    dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+        if (light) hipLaunchKernelGGL((trace_hits_kernel<decltype(nobj)::value, decltype(simple)::value, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((trace_hits_kernel<decltype(nobj)::value, false, false>), grid, block, 0, stream, a);
+    });
+    HIP_TRY(hipGetLastError());
+    return RTC_OK;
+}
+
+// World::is_shadowed for the caller's pairs (rtc_hits.h shadowed_kernel); leaves the context as rtc_ctx_trace_hits does.
+rtc_status rtc_ctx_is_shadowed(rtc_ctx* c, const void* d_light_positions, const void* d_points, uint32_t n, void* d_out_i32, void* stream_) {
+    if (n > 0u && (!d_light_positions || !d_points)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: null pair buffer");
+    if (n > 0u && !d_out_i32) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: null output buffer");
+    if (((uintptr_t)d_light_positions & 15u) || ((uintptr_t)d_points & 15u))
+        return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: light positions and points must be 16-byte aligned");
+    if ((uintptr_t)d_out_i32 & 3u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: output must be 4-byte aligned");
+    if (n == 0u) return RTC_OK;  // nothing to answer, whatever the context
+    if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: ctx is NULL");
+    if (!c->has_scene) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: no scene set");
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    ShadowedArgs a;
+    a.hdr = c->hdr;
+    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.light_positions = (const float4*)d_light_positions, a.points = (const float4*)d_points;
+    a.out = (int32_t*)d_out_i32;
+    a.n = n;
+    const dim3 grid((uint32_t)(((uint64_t)n + 255u) / 256u)), block(256);
+    dispatch_family(aot_family(c), [&](auto nobj, auto) {  // (SIMPLE is a property of intensity_at alone)
+        hipLaunchKernelGGL((shadowed_kernel<decltype(nobj)::value>), grid, block, 0, stream, a);
+    });
+    HIP_TRY(hipGetLastError());
+    return RTC_OK;
+}
+
 const char* rtc_ctx_trace_kernel_name(rtc_ctx* c) { return c ? c->trace.name.c_str() : ""; }
 const char* rtc_ctx_trace_kernel_id(rtc_ctx* c) { return c ? c->trace.id.c_str() : ""; }
 

@@ -166,5 +166,49 @@ __global__ __launch_bounds__(256, LIGHT ? RTC_HITS_LIGHT_WAVES : 1) void hits_ke
     first_hit<NOBJ, SIMPLE, LIGHT>(H, A.soa, origin, direction, y * H.width + x, A.planes, idx);
 }
 
+// ---- ray streams: first hits and occlusion for rays the caller brings (rtc_ctx_trace_hits, rtc_ctx_is_shadowed) ----------
+// What rtc_trace.h is to render_body these are to hits_kernel and is_shadowed_kernel: the rays are read from memory instead
+// of made from the camera, one lane per ray, ray i in thread i of a 1-D grid, so a wave is whichever 64 rays the caller put
+// side by side.  Everything behind the loads is first_hit / is_shadowed as the resident scene's SceneHdr switches them.
+// Not here, because a stream has no frame: tiles, the scene-box early-out of primary_ray, block lists, lane sharing.
+struct TraceHitsArgs {
+    SceneHdr hdr;
+    SceneSoA soa;
+    const float4* origins;     // [n] x, y, z read; w ignored (as trace_body)
+    const float4* directions;  // [n] likewise; used as given
+    const uint32_t* keys;      // [n] jitter keys, or nullptr: ray i draws as pixel i (wave-uniform: a kernel argument)
+    HitPlanes planes;          // element i: ray i
+    uint32_t n;
+};
+
+// rtc_ctx_trace_hits.  hits_kernel's launch bounds: behind the loads the two kernels are the same code.
+template <int NOBJ, bool SIMPLE, bool LIGHT>
+__global__ __launch_bounds__(256, LIGHT ? RTC_HITS_LIGHT_WAVES : 1) void trace_hits_kernel(TraceHitsArgs A) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;  // (the host launches ceil(n / 256) workgroups: no wrap below 2^32 rays)
+    if (i >= A.n) return;
+    const float4 o4 = A.origins[i], d4 = A.directions[i];
+    const uint32_t key = A.keys != nullptr ? A.keys[i] : i;
+    first_hit<NOBJ, SIMPLE, LIGHT>(A.hdr, A.soa, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), key, A.planes, i);
+}
+
+struct ShadowedArgs {
+    SceneHdr hdr;
+    SceneSoA soa;
+    const float4* light_positions;  // [n] x, y, z read
+    const float4* points;           // [n] likewise
+    int32_t* out;                   // [n] 0 / 1
+    uint32_t n;
+};
+
+// rtc_ctx_is_shadowed: World::is_shadowed (world.rs:104-119) pair by pair, with the object loop of the scene's family.
+template <int NOBJ>
+__global__ __launch_bounds__(256) void shadowed_kernel(ShadowedArgs A) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= A.n) return;
+    const float4 l = A.light_positions[i], p = A.points[i];
+    Counters cnt = {0u, 0u, 0u, 0u};
+    A.out[i] = is_shadowed<NOBJ>(A.hdr, A.soa, v3(l.x, l.y, l.z), v3(p.x, p.y, p.z), cnt) ? 1 : 0;
+}
+
 }  // namespace rtc
 #endif  // RTC_HITS_H

@@ -1,6 +1,7 @@
-"""Ray generators for Renderer.trace: projections the reference's pinhole camera does not have.
+"""Ray generators for Renderer.trace / trace_hits: projections the reference's pinhole camera does not have, and the
+bounce step from a set of first-hit planes to the next stream (reflected, at the end).
 
-Plain torch, on any device (CPU included).  Each returns (origins, directions): (height * width, 4) float32 in image
+Plain torch, on any device (CPU included).  Each projection returns (origins, directions): (height * width, 4) float32 in image
 order -- ray y * width + x is pixel (x, y) -- origins with w = 1, directions with w = 0 and of unit length to within f32
 rounding.  The angles and offsets are formed in float64 and rounded once; the directions are then normalised in float32
 (three products, two sums, a square root, a division each).
@@ -67,3 +68,22 @@ def equirectangular(width, height, position, device=None):
     directions3 = _normalize(d.reshape(-1, 3).to(torch.float32))
     p = torch.as_tensor([float(c) for c in list(position)[:3]], dtype=torch.float32, device=device)
     return _pack(p[None, :].expand(height * width, 3), directions3)
+
+
+def reflected(hits, directions=None):
+    """The bounce step: from a dict of first-hit planes (Renderer.trace_hits / render_hits, flattened to one element per ray)
+    holding `object`, `over_point` and `reflectv`, the reflection rays of the rays that hit something, compacted in index
+    order.  -> (origins (m, 4): over_point, directions (m, 4): reflectv, index (m,) int64: the ray each came from), on the
+    planes' device, as they were stored (w included; trace() and trace_hits() read x, y, z).
+    `directions` ((n, 4), optional: the directions of the rays that made the hits) is only checked against the planes'
+    length; the reflected direction is the stored `reflectv` (world.rs:220), not recomputed from it."""
+    for k in ("object", "over_point", "reflectv"):
+        if k not in hits:
+            raise ValueError("reflected: the planes need %r" % k)
+    obj = hits["object"].reshape(-1)
+    over, refl = hits["over_point"].reshape(-1, 4), hits["reflectv"].reshape(-1, 4)
+    n = obj.shape[0]
+    if over.shape[0] != n or refl.shape[0] != n or (directions is not None and directions.reshape(-1, 4).shape[0] != n):
+        raise ValueError("reflected: planes and directions of %d rays expected" % n)
+    index = torch.nonzero(obj >= 0).reshape(-1)  # int64, ascending
+    return over[index].contiguous(), refl[index].contiguous(), index

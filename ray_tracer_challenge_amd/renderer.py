@@ -114,6 +114,12 @@ class Renderer:
             raise ValueError("%s must be a contiguous, 16-byte aligned float32 CUDA tensor (n, 4) on %s" % (what, self.device))
         return int(t.shape[0])
 
+    def _key_tensor(self, keys, n):
+        if keys is not None:
+            ok = torch.is_tensor(keys) and keys.is_cuda and keys.device == self.device and keys.dim() == 1 and keys.shape[0] == n and keys.is_contiguous()
+            if not (ok and keys.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and keys.data_ptr() % 4 == 0):
+                raise ValueError("keys must be a contiguous int32 or uint32 CUDA tensor (n,) on %s" % self.device)
+
     def trace(self, origins, directions, depth, keys=None, out=None, stream=None):
         """World::color_at for the caller's rays against the resident scene (rtc_ctx_trace) on `stream` (default: torch's
         current stream); asynchronous.  origins, directions: (n, 4) float32 on the renderer's device (x, y, z are read); the
@@ -124,10 +130,7 @@ class Renderer:
         stream at a time per renderer: two traces in flight on different streams race on what stats() reports."""
         n = self._ray_tensor(origins, "origins")
         self._ray_tensor(directions, "directions", n)
-        if keys is not None:
-            ok = torch.is_tensor(keys) and keys.is_cuda and keys.device == self.device and keys.dim() == 1 and keys.shape[0] == n and keys.is_contiguous()
-            if not (ok and keys.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and keys.data_ptr() % 4 == 0):
-                raise ValueError("keys must be a contiguous int32 or uint32 CUDA tensor (n,) on %s" % self.device)
+        self._key_tensor(keys, n)
         if out is None:
             out = torch.empty((n, 3), dtype=torch.float32, device=self.device)
         if not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.float32 and out.is_contiguous()
@@ -139,6 +142,69 @@ class Renderer:
         L.check(self._lib.rtc_ctx_trace(self._ctx, int(depth), C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
                                         C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.c_void_p(out.data_ptr()),
                                         C.c_void_p(s.cuda_stream)), self._lib)
+        return out
+
+    def trace_hits(self, origins, directions, keys=None, planes=("object", "distance", "normal", "light"), out=None, stream=None):
+        """The first hit of each of the caller's rays against the resident scene (rtc_ctx_trace_hits) on `stream` (default:
+        torch's current stream); asynchronous.  origins, directions, keys: as trace() takes them.  -> {plane: tensor}, element
+        i belonging to ray i: int32 (n,) for object / inside, float32 (n,) for distance / light, float32 (n, 4) for the vector
+        planes, (n, 2) for n1n2; a miss is object -1 and zeros.  `out`: tensors to write into, by plane.
+        With `stream` given, a plane that is not in `out` is allocated by torch on its CURRENT stream and written on `stream`:
+        keep it alive until `stream` has been waited for (or pass an `out` made on `stream`, or call record_stream(stream) on
+        it).  Leaves stats() and the kernel names alone."""
+        n = self._ray_tensor(origins, "origins")
+        self._ray_tensor(directions, "directions", n)
+        self._key_tensor(keys, n)
+        planes = tuple(planes)
+        if not planes:
+            raise ValueError("no plane requested")
+        res, hp = {}, L.rtc_hit_planes()
+        for k in planes:
+            if k not in L.HIT_PLANES:
+                raise ValueError("%r is not a plane (%s)" % (k, ", ".join(L.HIT_PLANES)))
+            is_int, per = L.HIT_PLANES[k]
+            dtype = torch.int32 if is_int else torch.float32
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty((n, per) if per > 1 else (n,), dtype=dtype, device=self.device)
+            # (checked, not asserted: the raw pointer goes to a kernel that writes n elements through it, up to 16 bytes at a time)
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous()
+                    and tuple(t.shape) == ((n, per) if per > 1 else (n,)) and t.data_ptr() % (4 * per) == 0):
+                raise ValueError("out[%r] must be a contiguous, %d-byte aligned %s CUDA tensor of %d%s on %s"
+                                 % (k, 4 * per, "int32" if is_int else "float32", n, " x %d" % per if per > 1 else "", self.device))
+            res[k] = t
+            setattr(hp, k, t.data_ptr())
+        if not 0 <= n < 2 ** 32:
+            raise ValueError("at most 2^32 - 1 rays a call")
+        if n == 0:  # (an empty tensor has no address to give: nothing to trace, no call)
+            return res
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        L.check(self._lib.rtc_ctx_trace_hits(self._ctx, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                                             C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.byref(hp),
+                                             C.c_void_p(s.cuda_stream)), self._lib)
+        return res
+
+    def is_shadowed(self, light_positions, points, out=None, stream=None):
+        """World::is_shadowed(light_position, point) pair by pair against the resident scene (rtc_ctx_is_shadowed) on `stream`
+        (default: torch's current stream); asynchronous.  light_positions, points: (n, 4) float32 on the renderer's device (x,
+        y, z are read).  -> (n,) int32, 1: the nearest thing between the two is a shadow caster.
+        With `stream` given and no `out`, the result is allocated by torch on its CURRENT stream and written on `stream`: keep
+        it alive until `stream` has been waited for (or pass an `out` made on `stream`, or call out.record_stream(stream)).
+        Leaves stats() and the kernel names alone."""
+        n = self._ray_tensor(light_positions, "light_positions")
+        self._ray_tensor(points, "points", n)
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int32, device=self.device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.int32 and out.is_contiguous()
+                and tuple(out.shape) == (n,) and out.data_ptr() % 4 == 0):
+            raise ValueError("out must be a contiguous int32 CUDA tensor (%d,) on %s" % (n, self.device))
+        if not 0 <= n < 2 ** 32:
+            raise ValueError("at most 2^32 - 1 pairs a call")
+        if n == 0:
+            return out
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        L.check(self._lib.rtc_ctx_is_shadowed(self._ctx, C.c_void_p(light_positions.data_ptr()), C.c_void_p(points.data_ptr()), n,
+                                              C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)), self._lib)
         return out
 
     def camera_rays(self, camera=None, y0=0, n_rows=None, stream=None):

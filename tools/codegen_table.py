@@ -10,7 +10,9 @@ taken from World.scene_plan(camera) and compiled as tools/spec_asm.sh does; C3's
 (the fine camera's options as rtc_ctx_set_scene_ss rewrites them); and, where the directory has rtc_trace.h, the same eight
 scenes' ray-stream kernels (the options as rtc_ctx_set_scene rewrites them for rtc_ctx_trace).  With two directories the rows
 are compared and every figure that differs is marked.  --trace-pairs FILE: every ray-stream kernel of the first directory next
-to its render sibling (profiles/trace_codegen.txt).
+to its render sibling (profiles/trace_codegen.txt).  --hits-pairs FILE: every ray-stream first-hit and occlusion kernel
+(csrc/rtc_hits.h: trace_hits_kernel, shadowed_kernel) next to its sibling, hits_kernel of the same instantiation or the batched
+is_shadowed_kernel (profiles/trace_hits_codegen.txt); given alone, only rtc_device.hip is compiled.
 
 Build first (python -m ray_tracer_challenge_amd.build --all, in this tree and in the tree of any other directory named): the
 scenes' option lists come from this tree's library, and rtc_device.hip includes the literal the build generates beside it.
@@ -79,15 +81,16 @@ def demangle(names):
     return {n: re.sub(r"^void rtc::|\(rtc::\w+\)$|\(.*\)$", "", d) for n, d in zip(names, out)}
 
 
-def table(csrc, tmp, tag):
-    jobs = [("aot " + s, os.path.join(csrc, s), []) for s in ("rtc_device.hip", "rtc_oneshot.hip")]
+def table(csrc, tmp, tag, device_only=False):
+    jobs = [("aot " + s, os.path.join(csrc, s), []) for s in ("rtc_device.hip", "rtc_oneshot.hip")[:1 if device_only else 2]]
     spec, ss = os.path.join(tmp, "spec.hip"), os.path.join(tmp, "ss.hip")
     open(spec, "w").write('#include "rtc_kernel_core.h"\n')
     open(ss, "w").write('#include "rtc_supersample.h"\n')
-    for scene, name, w, h in SCENES:
+    for scene, name, w, h in ([] if device_only else SCENES):
         jobs.append(("scene " + scene, spec, scene_defs(name, w, h)))
-    jobs.append(("scene C3 ss=2", ss, scene_defs("soft_shadows", 4096, 4096, ss=2)))
-    if os.path.exists(os.path.join(csrc, "rtc_trace.h")):
+    if not device_only:
+        jobs.append(("scene C3 ss=2", ss, scene_defs("soft_shadows", 4096, 4096, ss=2)))
+    if os.path.exists(os.path.join(csrc, "rtc_trace.h")) and not device_only:
         trace = os.path.join(tmp, "trace.hip")
         open(trace, "w").write('#include "rtc_trace.h"\n')
         for scene, name, w, h in SCENES:
@@ -110,10 +113,12 @@ def main():
     ap.add_argument("csrc", nargs="+")
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-pairs", default=None, help="write the ray-stream kernels next to their render siblings here")
+    ap.add_argument("--hits-pairs", default=None, help="write the ray-stream first-hit and occlusion kernels next to their siblings here")
     args = ap.parse_args()
+    device_only = bool(args.hits_pairs) and not args.out and not args.trace_pairs and len(args.csrc) == 1
     own = os.path.join(ROOT, "ray_tracer_challenge_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
-        tables = [table(os.path.abspath(c), tmp, "t%d" % i) for i, c in enumerate(args.csrc)]
+        tables = [table(os.path.abspath(c), tmp, "t%d" % i, device_only) for i, c in enumerate(args.csrc)]
     lines = ["figures per kernel: VGPRs / SGPRs / scratch bytes per lane / LDS bytes / instructions / scratch_ instructions"]
     if len(tables) == 2:
         lines.append("first: %s   second: %s   (* a figure that differs)" % tuple(os.path.relpath(os.path.abspath(c), ROOT) if os.path.abspath(c) == own else "the parent's csrc" for c in args.csrc))
@@ -145,6 +150,20 @@ def main():
             cells = [" / ".join(str(t[n][f]) for f in FIGURES) if n in t else "-" for n in (k, sib)]
             pairs.append("%-62s %-36s   |   %-36s %+d B" % (k, cells[0], cells[1], t[k]["scratch"] - t[sib]["scratch"] if sib in t else 0))
         open(args.trace_pairs, "w").write("\n".join(pairs) + "\n")
+    if args.hits_pairs:
+        t = tables[0]
+        pairs = ["ray-stream first-hit and occlusion kernels (csrc/rtc_hits.h) next to their siblings: VGPRs / SGPRs / scratch bytes per lane / "
+                 "LDS bytes / instructions / scratch_ instructions", "%-58s %-32s   |   %-32s %-32s %s" % ("kernel", "stream", "sibling", "", "scratch, stream - sibling")]
+        for k in sorted(t):
+            if ": trace_hits_kernel<" in k:
+                sib = k.replace(": trace_hits_kernel<", ": hits_kernel<")
+            elif ": shadowed_kernel<" in k:
+                sib = k[:k.index(": ")] + ": rtc::is_shadowed_kernel"  # (not a template: the mangled name carries no return type)
+            else:
+                continue
+            cells = [" / ".join(str(t[n][f]) for f in FIGURES) if n in t else "-" for n in (k, sib)]
+            pairs.append("%-58s %-32s   |   %-32s %-32s %+d B" % (k, cells[0], sib.split(": ")[1].replace("rtc::", ""), cells[1], t[k]["scratch"] - t[sib]["scratch"] if sib in t else 0))
+        open(args.hits_pairs, "w").write("\n".join(pairs) + "\n")
 
 
 if __name__ == "__main__":
