@@ -507,7 +507,8 @@ struct SceneHdr {
     // on): bit 0 -- cull at all; bit 1 -- the `dark` shortcut (every sample blocked on the far side of a casting sphere),
     // the one decision that asserts hits instead of removing tests; bit 2 -- shadow_fast (RTC_AMD_FAST_SHADOW), the
     // margin-guarded decision of a sample without normalising its ray; bit 3 -- block cones (RTC_AMD_CELL_CULL,
-    // blocks_usable): 2 x 2 blocks of the light's cells called lit by the wave before any sample is drawn.  Off, every shadow ray is tested against every
+    // blocks_usable): 2 x 2 blocks of the light's cells called lit by the wave before any sample is drawn; bit 4 -- own-sphere blocks
+    // (RTC_AMD_OWN_BLOCKS, intensity_at): the same blocks called lit against the sphere the lane sits on.  Off, every shadow ray is tested against every
     // object the exact way: the image and the ray counts must not change (tests/test_gpu_fullsize.py, whole frames).
     uint32_t cull_flags;
     uint32_t max_leaf_run;  // the longest run of consecutive leaf entries in SceneSoA::trav (host: lanes per pixel, for_each_leaf_shared)
@@ -519,7 +520,7 @@ struct SceneHdr {
     // sample's own position (8 u x the light's largest coordinate); 0: not available (jitter outside [0, 1], ...)
     float cell_hd;
 };
-constexpr uint32_t CULL_ENABLED = 1u, CULL_DARK = 2u, CULL_FAST_SHADOW = 4u, CULL_CELLS = 8u;
+constexpr uint32_t CULL_ENABLED = 1u, CULL_DARK = 2u, CULL_FAST_SHADOW = 4u, CULL_CELLS = 8u, CULL_OWN_BLOCKS = 16u;
 constexpr uint32_t RTC_MAX_GATES = 8;
 
 // Structure-of-arrays scene records in HBM: 4 float4 of geometry (64 B) and
@@ -2228,12 +2229,24 @@ DI float intensity_at(const SceneHdr& H, const SceneSoA& S, V3 p, uint32_t pixel
             // hd R, with the largest R any lane may use: 1.03 sqrt(1 + 32 u oo) at oo = 2.5e5 (500 radii; beyond, a lane calls nothing lit).
             // The same for every lane and sphere -- a scalar, where the exact product would be a register per sphere.
             const float T_lit = hd * 1.2535f;
+            // Own-sphere blocks (ERROR_BUDGET.md B11, RTC_AMD_OWN_BLOCKS).  A lane that SITS ON casting sphere i -- 1e-4 < c_own, oo <= 1.21:
+            // B2's own bounds -- is where the cone above is mute (oo <= 1.001 R^2), and where the sphere's tangent plane at the shade point
+            // cuts the light B2 does not speak for the whole light.  Per block it does.  Every sample direction is v = c + delta,
+            // |delta| <= hd, so sign(g) (v . o) >= -d - hd |o| and |v| <= sq + 2 hd:
+            //     d < -|o| (0.05 sq + 1.1 hd)  =>  every sample 2.9 degrees above the tangent plane: b > 0, both roots negative.
+            // It is the compare the loop already makes, with S_lit[i] = -0.05 |o| (1 + 1e-4); T_lit stays the scalar it is, since
+            // 1.1 hd |o| (1 + 1e-4) <= 1.2102 hd < T_lit for |o| <= 1.1 (a per-lane product would be a register per sphere): the loop
+            // gains no instruction.  NaN sq (a shade point inside the block cone's base) holds in no comparison, as before.
+            // (oo <= 1.21 is implied by the mute zone, oo <= 1.001 R^2 ~ 1.062: it is written out because it is the bound B2's
+            // argument and the T_lit inequality above are stated for.)
+            const bool own = (H.cull_flags & CULL_OWN_BLOCKS) != 0u;  // wave-uniform
 #pragma unroll
             for (int i = 0; i < N; i++) {
                 const uint32_t bits = spec_bits(i, __float_as_uint(S.geo[i].w));
                 if ((bits & SHAPE_KIND_MASK) != RTC_SPHERE || !(bits & SHAPE_CASTS) || ((skip >> i) & 1u)) continue;  // wave-uniform
-                const float oo = pre[i].c + 1.0f, R2 = 1.0609f * (1.0f + 1.9073486e-6f * oo);
+                const float c_own = pre[i].c, oo = c_own + 1.0f, R2 = 1.0609f * (1.0f + 1.9073486e-6f * oo);
                 S_lit[i] = (oo > 1.001f * R2 && oo < 2.5e5f) ? __builtin_amdgcn_sqrtf(oo - R2) : RTC_NAN;  // (NaN: no comparison holds -- this lane calls nothing lit)
+                if (own && c_own > 1e-4f && oo <= 1.21f && !(oo > 1.001f * R2)) S_lit[i] = -0.05f * (1.0001f * __builtin_amdgcn_sqrtf(oo));
             }
             for (int vb = 0; vb < H.v_steps; vb += 2) {
                 for (int ub = 0; ub < H.u_steps; ub += 2) {

@@ -234,7 +234,7 @@ inline void triangle_box(const rtc_object& o, const float4 tri[3], double d_worl
 #endif
 struct Policy {
     int specialise = 2;  // RTC_AMD_SPECIALIZE: 0 never, 1 always (a failed compile is an error), 2 by frame size
-    bool light_cull = true, dark = true, fast_shadow = true, cell_cull = true;  // RTC_AMD_LIGHT_CULL / _DARK / _FAST_SHADOW / _CELL_CULL (SceneHdr::cull_flags)
+    bool light_cull = true, dark = true, fast_shadow = true, cell_cull = true, own_blocks = true;  // RTC_AMD_LIGHT_CULL / _DARK / _FAST_SHADOW / _CELL_CULL / _OWN_BLOCKS (SceneHdr::cull_flags)
     bool bvh = true, scene_box = true, gates = true, tri_precull = true, block_list = true, quiet = false;
     bool scene_tiles = true;  // RTC_AMD_SCENE_TILES: a sparse bounded scene's frames as zero-fill + its own tiles (rtc_ctx::scene_tile_mask)
     bool prune = true;    // RTC_AMD_PRUNE: groups / nodes a ray enters beyond what it still wants are left closed (for_each_object, ERROR_BUDGET.md B6)
@@ -263,6 +263,7 @@ struct Policy {
         p.dark = flag(std::getenv("RTC_AMD_DARK"), true);
         p.fast_shadow = flag(std::getenv("RTC_AMD_FAST_SHADOW"), true);
         p.cell_cull = flag(std::getenv("RTC_AMD_CELL_CULL"), true);
+        p.own_blocks = flag(std::getenv("RTC_AMD_OWN_BLOCKS"), true);
         p.bvh = flag(std::getenv("RTC_AMD_BVH"), true);
         p.scene_box = flag(std::getenv("RTC_AMD_SCENE_BOX"), true);
         p.gates = flag(std::getenv("RTC_AMD_GATES"), true);
@@ -1208,7 +1209,7 @@ struct Flatten {
         hdr->all_cast = 1;
         for (uint32_t i = 0; i < n; i++)
             if (!scene->objects[i].casts_shadow) hdr->all_cast = 0;
-        hdr->cull_flags = (P.light_cull ? CULL_ENABLED : 0u) | (P.dark ? CULL_DARK : 0u) | (P.fast_shadow ? CULL_FAST_SHADOW : 0u) | (P.cell_cull ? CULL_CELLS : 0u);
+        hdr->cull_flags = (P.light_cull ? CULL_ENABLED : 0u) | (P.dark ? CULL_DARK : 0u) | (P.fast_shadow ? CULL_FAST_SHADOW : 0u) | (P.cell_cull ? CULL_CELLS : 0u) | (P.own_blocks ? CULL_OWN_BLOCKS : 0u);
         return RTC_OK;
     }
     // One object's light-cone record (light_cull_mask): the area light's corners `cw` in the object's space, and in trn.w / off2.w
