@@ -31,7 +31,9 @@ extern "C" {
 #endif
 
 #define RTC_ABI_VERSION 8 /* (rtc_ctx_trace_hits and rtc_ctx_is_shadowed were added at 8: two entry points more, no struct and
-                             no existing signature changed, so callers built against the earlier 8 run unchanged) */
+                             no existing signature changed, so callers built against the earlier 8 run unchanged; likewise
+                             adaptive supersampling: rtc_ctx_render_adaptive, rtc_ctx_adaptive_stats, rtc_ctx_adaptive_kernel_name
+                             / _id and the struct rtc_adaptive_stats are additions, nothing that existed has moved) */
 /* reflection_recursion_depth (camera.rs:76: any i16; reference default 5, constants.rs:4; its author renders
  * reflect_refract at 20).  Accepted: 0 .. RTC_MAX_DEPTH.  The kernels keep one frame per suspended shade_hit
  * (world.rs:62-86); up to RTC_STACK_DEPTH_BASE levels every kernel has them, above that the scene's kernel is compiled
@@ -499,6 +501,52 @@ rtc_status rtc_ctx_camera_rays(rtc_ctx* ctx, const rtc_camera* camera, uint32_t 
  * "aot_trace_..." or "spec_..." ids of their own, as rtc_ctx_kernel_name / _id).  "" before the first trace of the current scene. */
 const char* rtc_ctx_trace_kernel_name(rtc_ctx* ctx);
 const char* rtc_ctx_trace_kernel_id(rtc_ctx* ctx);
+/* ------------------------------------------------------------------------
+ * Adaptive supersampling: k x k rays only where neighbouring pixels of the rendered frame differ.
+ * For the context's resident scene and camera (W x H), k = 2 or 4 and an f32 threshold:
+ *  (1) B is exactly what rtc_ctx_render writes for the whole frame at `depth`, its black last row and column included.
+ *  (2) Pixel p is flagged when, for any of its up to four neighbours n (x +- 1, y +- 1, inside the frame) and any channel c,
+ *      fabsf(B[p][c] - B[n][c]) > threshold: f32 subtraction and fabsf, a strict compare, so a NaN difference (inf - inf) never
+ *      flags; the rule is symmetric, both pixels of a contrasting pair are flagged; the last row and column take part like
+ *      any pixel (their neighbours are flagged wherever the scene is lit there).
+ *  (3) S is rtc_ctx_set_scene_ss's frame for the same camera and k: the fine camera rtc_camera_supersampled(camera, k), jitter
+ *      keys from the fine pixel index y_f * k W + x_f, the fine frame's last row and column black, the pairwise f32 tree along
+ *      x first, then along y, times 0.25f or 0.0625f, nothing fused (see rtc_ctx_set_scene_ss).
+ *  (4) The output O[p] = S[p] where p is flagged, B[p] elsewhere; S is never computed where p is not flagged.  With a
+ *      threshold so large that nothing is flagged O is rtc_ctx_render's frame bit for bit.  The picture does not depend on
+ *      the order in which flagged pixels are processed.
+ * d_out_rgb: DEVICE pointer to H x W x 3 f32.  d_mask_u8: DEVICE pointer to H x W bytes, 1 = refined, 0 = not; may be NULL.
+ * The whole frame only: the mask needs neighbours across band edges, so there is no partition; the f32 canvas only.
+ * Asynchronous on `stream`; nothing comes back to the host between the three passes, the number of flagged pixels included.
+ * The base pass IS rtc_ctx_render -- tiles, rectangle, block lists, feedback and its occasional read-back of measurements --
+ * so rtc_ctx_stats and rtc_ctx_kernel_name / _id afterwards report it as after rtc_ctx_render, and the schedule moves as a
+ * render moves it.  The refinement leaves all of that alone, as a trace does, and the trace's own state as well.  Its kernel
+ * is one lane per fine sample, the ahead-of-time family or -- where rtc_ctx_set_scene's specialisation policy asks for it
+ * for a frame of W x H pixels; RTC_AMD_SPECIALIZE=0|1 as there -- the scene's own, compiled by the first adaptive call that
+ * wants it and cached like every scene kernel; depth above 8 takes the deep-stack variant.
+ * Rejected, decided before any device call, in this order, the context's checks last: a threshold that is not finite or is
+ * negative, a k other than 2 or 4, a null or misaligned output pointer, a depth out of range, a null context, no scene set
+ * (all RTC_ERR_INVALID_ARG); a supersampled context (RTC_ERR_UNSUPPORTED); a fine frame beyond rtc_camera_supersampled's
+ * limits, 2^32 pixels or 2^17 rows (RTC_ERR_INVALID_ARG).
+ * One stream at a time, as for the whole context. */
+typedef struct rtc_adaptive_stats {
+    uint64_t refined_pixels;     /* flagged pixels of the last rtc_ctx_render_adaptive                                  */
+    uint64_t rays;               /* of the refinement pass, counted as rtc_ctx_trace counts them                        */
+    uint64_t shaded_hits;
+    uint64_t culled_shadow_rays; /* voted by whichever lanes share a wave: <= rays, otherwise not comparable            */
+    float mask_ms;               /* HIP-event time of the mask and list kernel                                          */
+    float refine_ms;             /* ... and of the refinement kernel                                                    */
+} rtc_adaptive_stats;
+rtc_status rtc_ctx_render_adaptive(rtc_ctx* ctx, int32_t depth, uint32_t k, float threshold, void* d_out_rgb,
+                                   void* d_mask_u8, void* stream);
+/* Waits for the device as rtc_ctx_stats does; all zero before the first rtc_ctx_render_adaptive. */
+rtc_status rtc_ctx_adaptive_stats(rtc_ctx* ctx, rtc_adaptive_stats* out);
+/* The refinement kernel of the context's last rtc_ctx_render_adaptive and the code it names
+ * ("adaptive_refine_kernel<...;ss=k>" / "adaptive_refine_kernel_spec[...;ss=k]"; "aot_adaptive<k>_..." or "spec_..." ids),
+ * as rtc_ctx_trace_kernel_name / _id.  "" before the first adaptive call of the current scene. */
+const char* rtc_ctx_adaptive_kernel_name(rtc_ctx* ctx);
+const char* rtc_ctx_adaptive_kernel_id(rtc_ctx* ctx);
+
 /* The first hits (see "First-hit buffers" above) of n caller rays against the context's resident scene: the rays and keys
  * are rtc_ctx_trace's (DEVICE pointers, x, y, z read, the direction used as given, d_keys NULL: ray i draws as pixel i), the
  * planes are rtc_ctx_render_hits' (`d_out` a host struct of DEVICE pointers, NULL = not wanted), element i belonging to ray

@@ -86,6 +86,11 @@ class rtc_stats(C.Structure):
 RTC_STATS_JIT_FALLBACK = 1
 
 
+class rtc_adaptive_stats(C.Structure):
+    _fields_ = [("refined_pixels", C.c_uint64), ("rays", C.c_uint64), ("shaded_hits", C.c_uint64), ("culled_shadow_rays", C.c_uint64),
+                ("mask_ms", C.c_float), ("refine_ms", C.c_float)]
+
+
 class rtc_opts(C.Structure):
     _fields_ = [("devices", C.POINTER(C.c_int32)), ("n_devices", C.c_uint32), ("band_rows", C.c_uint32),
                 ("quantize", C.c_int32), ("out_on_device", C.c_int32)]
@@ -177,6 +182,10 @@ SIGNATURES = {
     "rtc_ctx_trace_kernel_id": (C.c_char_p, [C.c_void_p]),
     "rtc_ctx_trace_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(rtc_hit_planes), C.c_void_p]),
     "rtc_ctx_is_shadowed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtc_ctx_render_adaptive": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtc_ctx_adaptive_stats": (C.c_int, [C.c_void_p, C.POINTER(rtc_adaptive_stats)]),
+    "rtc_ctx_adaptive_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "rtc_ctx_adaptive_kernel_id": (C.c_char_p, [C.c_void_p]),
     "rtc_intensity_at": (C.c_int, [C.POINTER(rtc_scene), FP, C.c_uint32, C.c_int32, FP]),
     "rtc_is_shadowed": (C.c_int, [C.POINTER(rtc_scene), FP, FP, C.c_uint32, C.c_int32, C.POINTER(C.c_int32)]),
     "rtc_point_on_light": (C.c_int, [C.POINTER(rtc_light), C.POINTER(C.c_int32), C.c_uint32, C.c_int32, FP]),
@@ -219,6 +228,9 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
          "rtc_diag_ss_plan": (C.c_uint32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32,
                                            C.c_double, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
          "rtc_diag_ctx_share_log2": (C.c_uint32, [C.c_void_p]),
+         # adaptive supersampling: the refinement's slot -> (entry, sx, sy, lane) mapping and its grid (tests/test_adaptive_boundary.py)
+         "rtc_diag_adaptive_plan": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
          # rtc_scene_prep.h on the host: digests of what flatten packs and the text of plan_scene's choice (tests/test_scene_prep.py)
          "rtc_diag_scene_plan": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)])}
 

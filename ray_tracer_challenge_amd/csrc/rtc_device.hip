@@ -38,6 +38,7 @@
 #include "rtc_hits.h"
 #include "rtc_supersample.h"
 #include "rtc_trace.h"
+#include "rtc_adaptive.h"
 #include "rtc_wavefront.h"
 #include "rtc_scene_prep.h"
 
@@ -224,6 +225,27 @@ struct rtc_ctx {
         uint64_t last_n = 0;
         bool last = false;                // the context's last launch was a trace: rtc_ctx_stats reports it
     } trace;
+    // Adaptive supersampling (rtc_ctx_render_adaptive; rtc_adaptive.h).  The base frame is the context's normal render; the mask
+    // and the refinement have everything of their own, as a trace has, so that the frame schedule and rtc_ctx_stats never see them.
+    struct Adaptive {
+        struct PerK {                     // k = 2, 4
+            std::vector<std::string> defs;   // the ray stream's options with -DRTC_SPEC_ADAPTIVE=k in the place of -DRTC_SPEC_TRACE=1
+            hipFunction_t fn = nullptr;      // the scene's refinement kernel, compiled by the first call that asks for it
+            std::string fn_id;
+            DeepKernels deep;
+        } per_k[2];
+        bool failed = false;              // hiprtc did not deliver: the ahead-of-time kernel from then on (note says why)
+        std::string note;
+        std::string name, id;             // of the last call's refinement kernel ("" before the first of the current scene)
+        uint32_t* d_list = nullptr;       // flagged pixel indices: width * height words, allocated by the first call
+        size_t list_cap = 0;
+        AdaptiveQueue* d_queue = nullptr; // the list's length and the last refinement's {rays, shaded hits, culled shadow rays}
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // before the mask kernel, between the two, after the refinement
+        bool ran = false;                 // the events have been recorded
+        std::set<std::pair<const void*, const void*>> warmed;  // (kernel, stream) pairs launched once
+        std::map<const void*, int> wgs_per_cu;  // occupancy of a refinement kernel, asked once
+    } adaptive;
+    rtc_camera camera;             // the camera of the resident scene as rtc_ctx_set_scene took it (has_scene)
     uint32_t last_rows = 0;
     uint32_t last_share_log2 = 0;  // lanes per pixel (log2) the last launch was planned with (rtc_diag_ctx_share_log2)
     uint64_t last_pixels = 0;
@@ -372,7 +394,10 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
     // -DRTC_SPEC_TRACE=1: the scene's ray-stream kernel -- rtc_trace.h beside the core, likewise (never both)
     bool trace = false;
     for (const auto& d : defines) trace = trace || d.rfind("-DRTC_SPEC_TRACE=", 0) == 0;
-    const char* const entry = ss ? "ss_render_kernel_spec" : trace ? "trace_kernel_spec" : "render_kernel_spec";
+    // -DRTC_SPEC_ADAPTIVE=k: the scene's refinement kernel of adaptive supersampling -- rtc_adaptive.h beside the core, likewise
+    bool adaptive = false;
+    for (const auto& d : defines) adaptive = adaptive || d.rfind("-DRTC_SPEC_ADAPTIVE=", 0) == 0;
+    const char* const entry = ss ? "ss_render_kernel_spec" : trace ? "trace_kernel_spec" : adaptive ? "adaptive_refine_kernel_spec" : "render_kernel_spec";
     std::string core_file;
     const char* core = k_core_src;
     if (!P.jit_source.empty()) {  // development builds only (Policy)
@@ -381,9 +406,9 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
     }
     // (... and rtc_supersample.h / rtc_trace.h from the same directory, when it is there: an experiment in either header needs no rebuild)
     std::string beside_file;
-    const char* beside_src = trace ? k_trace_src : k_ss_src;  // the header beside the core, whichever it is
-    const char* const beside_name = trace ? "rtc_trace.h" : "rtc_supersample.h";
-    if ((ss || trace) && !P.jit_source.empty()) {
+    const char* beside_src = trace ? k_trace_src : adaptive ? k_adaptive_src : k_ss_src;  // the header beside the core, whichever it is
+    const char* const beside_name = trace ? "rtc_trace.h" : adaptive ? "rtc_adaptive.h" : "rtc_supersample.h";
+    if ((ss || trace || adaptive) && !P.jit_source.empty()) {
         const size_t slash = P.jit_source.find_last_of('/');
         const std::string beside = (slash == std::string::npos ? std::string() : P.jit_source.substr(0, slash + 1)) + beside_name;
         if (read_file(beside, &beside_file)) beside_src = beside_file.c_str();
@@ -414,6 +439,7 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
                 " args " + std::to_string(sizeof(RenderArgs)) + "\n";
     // (a ray-stream kernel takes TraceArgs: its layout is rtc_trace.h's text, hashed below, and its size is in the key as well)
     if (trace) opt_text += "trace args " + std::to_string(sizeof(TraceArgs)) + "\n";
+    if (adaptive) opt_text += "adaptive args " + std::to_string(sizeof(AdaptiveRefineArgs)) + "\n";
     // (Not in the key: WHICH libhiprtc this process holds.  A Python process that imported torch first compiles with the wheel's
     // bundled compiler, the same script under rocprofv3 -- which puts /opt/rocm/lib first in LD_LIBRARY_PATH -- with the system's;
     // both report one hiprtcVersion and emit different, equally valid code for these kernels (same images, same speed:
@@ -421,15 +447,15 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
     // compiled -- profiles/run_profile.sh compiles first, plainly -- and the id below says which binary it was.)
     char name[64];
     uint64_t source_hash = fnv1a(opt_text, fnv1a(core));
-    if (ss || trace) source_hash = fnv1a(beside_src, source_hash);  // (the plain kernels' names do not move)
+    if (ss || trace || adaptive) source_hash = fnv1a(beside_src, source_hash);  // (the plain kernels' names do not move)
     snprintf(name, sizeof(name), "spec_%016llx.hsaco", (unsigned long long)source_hash);
     const std::string cache_dir = jit_cache_dir(P), cache_path = cache_dir + "/" + name;
     auto compile = [&](std::string* code) -> rtc_status {
         hiprtcProgram prog;
-        const char* src = ss ? "#include \"rtc_supersample.h\"\n" : trace ? "#include \"rtc_trace.h\"\n" : "#include \"rtc_kernel_core.h\"\n";
+        const char* src = ss ? "#include \"rtc_supersample.h\"\n" : trace ? "#include \"rtc_trace.h\"\n" : adaptive ? "#include \"rtc_adaptive.h\"\n" : "#include \"rtc_kernel_core.h\"\n";
         const char* headers[] = {core, beside_src};
         const char* header_names[] = {"rtc_kernel_core.h", beside_name};
-        if (hiprtcCreateProgram(&prog, src, "rtc_scene_spec.hip", (ss || trace) ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
+        if (hiprtcCreateProgram(&prog, src, "rtc_scene_spec.hip", (ss || trace || adaptive) ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
             return fail(RTC_ERR_DEVICE, "hiprtcCreateProgram failed");
         std::vector<const char*> copts;
         for (const auto& o : opts) copts.push_back(o.c_str());
@@ -526,6 +552,13 @@ std::string aot_ss_kernel_id(uint32_t k) {
 std::string aot_trace_kernel_id() {
     char b[48];
     snprintf(b, sizeof(b), "aot_trace_%016llx", (unsigned long long)fnv1a(k_trace_src, fnv1a(k_core_src)));
+    return b;
+}
+
+// ... and its refinement kernels of adaptive supersampling: the core's text and rtc_adaptive.h's
+std::string aot_adaptive_kernel_id(uint32_t k) {
+    char b[56];
+    snprintf(b, sizeof(b), "aot_adaptive%u_%016llx", k, (unsigned long long)fnv1a(k_adaptive_src, fnv1a(k_core_src)));
     return b;
 }
 
@@ -641,6 +674,10 @@ void rtc_ctx_destroy(rtc_ctx* c) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
     }
+    if (c->adaptive.d_list) (void)hipFree(c->adaptive.d_list);
+    if (c->adaptive.d_queue) (void)hipFree(c->adaptive.d_queue);
+    for (hipEvent_t e : c->adaptive.ev)
+        if (e) (void)hipEventDestroy(e);
     delete c;
 }
 
@@ -904,6 +941,7 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     }
     ScenePlan plan = plan_scene(P, hdr, soa, scene, camera, heavy_boxes, region);  // which kernel will render this scene
     c->hdr = hdr;
+    c->camera = *camera;
     c->ss_k = k;
     c->n_objects = hdr.n_objects;
     c->has_scene = true;
@@ -945,6 +983,16 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
         t.fn = nullptr, t.failed = false, t.last = false;
         t.fn_id.clear(), t.note.clear(), t.name.clear(), t.id.clear();
         t.deep.clear();
+        // ... and the refinement of an adaptive frame: a ray stream's options, an entry of its own per factor
+        rtc_ctx::Adaptive& ad = c->adaptive;
+        for (uint32_t i = 0; i < 2u; i++) {
+            rtc_ctx::Adaptive::PerK& pk = ad.per_k[i];
+            pk.defs.clear();
+            for (const auto& d : t.defs) pk.defs.push_back(d == "-DRTC_SPEC_TRACE=1" ? std::string("-DRTC_SPEC_ADAPTIVE=") + (i ? "4" : "2") : d);
+            pk.fn = nullptr, pk.fn_id.clear(), pk.deep.clear();
+        }
+        ad.failed = false;
+        ad.note.clear(), ad.name.clear(), ad.id.clear();
     }
     if (k != 1u) {
         // Scene tiles, the scene rectangle and several blocks per workgroup address the canvas by fine pixels and are not carried
@@ -1850,6 +1898,181 @@ rtc_status rtc_ctx_is_shadowed(rtc_ctx* c, const void* d_light_positions, const 
 
 const char* rtc_ctx_trace_kernel_name(rtc_ctx* c) { return c ? c->trace.name.c_str() : ""; }
 const char* rtc_ctx_trace_kernel_id(rtc_ctx* c) { return c ? c->trace.id.c_str() : ""; }
+
+}  // extern "C"
+
+// ---- adaptive supersampling (rtc_adaptive.h) ---------------------------------------
+static_assert(ADAPTIVE_STEP == ADAPTIVE_STEP_SLOTS, "the kernel's step is the plan's");
+// trace_kernel_for for the refinement kernel of factor k: the scene's own where the policy asks for it, always deeper than the
+// ahead-of-time stack, compiled on first use; null: the ahead-of-time family.
+static rtc_status adaptive_kernel_for(rtc_ctx* c, int32_t depth, uint32_t k, bool want, hipFunction_t* fn, std::string* id) {
+    rtc_ctx::Adaptive& ad = c->adaptive;
+    rtc_ctx::Adaptive::PerK& pk = ad.per_k[k == 4u ? 1 : 0];
+    *fn = nullptr;
+    if (depth > RTC_STACK_DEPTH_BASE) return deep_kernel(c, depth, pk.defs, pk.deep, fn, id);
+    if (!want || ad.failed) return RTC_OK;
+    if (pk.fn == nullptr) {
+        const rtc_status jst = jit_get(c->policy, c->device, pk.defs, &pk.fn, &pk.fn_id);
+        if (jst != RTC_OK) {  // as trace_kernel_for: RTC_AMD_SPECIALIZE=1 an error, else the ahead-of-time kernel, and say so
+            pk.fn = nullptr;
+            ad.failed = true;
+            ad.note = rtc_last_error();
+            if (c->policy.specialise == 1) return jst;
+            static bool warned = false;
+            if (!warned && !c->policy.quiet) {
+                warned = true;
+                std::fprintf(stderr, "librtc_amd: scene specialisation unavailable, refining with the slower ahead-of-time kernel: %.300s\n", ad.note.c_str());
+            }
+            return RTC_OK;
+        }
+    }
+    *fn = pk.fn, *id = pk.fn_id;
+    return RTC_OK;
+}
+
+// f(the ahead-of-time refinement kernel of the context's family and factor k)
+template <class F>
+static void dispatch_adaptive(rtc_ctx* c, uint32_t k, F&& f) {
+    dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+        if (k == 4u) f(adaptive_refine_kernel<decltype(nobj)::value, decltype(simple)::value, 4>);
+        else f(adaptive_refine_kernel<decltype(nobj)::value, decltype(simple)::value, 2>);
+    });
+}
+static hipError_t launch_adaptive(rtc_ctx* c, hipFunction_t fn, uint32_t k, uint32_t n_workgroups, hipStream_t stream, AdaptiveRefineArgs& a) {
+    if (fn) {
+        void* params[] = {&a};
+        return hipModuleLaunchKernel(fn, n_workgroups, 1, 1, 256, 1, 1, 0, stream, params, nullptr);
+    }
+    dispatch_adaptive(c, k, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_workgroups), dim3(256), 0, stream, a); });
+    return hipGetLastError();
+}
+// workgroups of the refinement kernel a compute unit holds at once (asked once per kernel; 0 from the runtime: one)
+static int adaptive_wgs_per_cu(rtc_ctx* c, hipFunction_t fn, uint32_t k, const void* key) {
+    auto it = c->adaptive.wgs_per_cu.find(key);
+    if (it != c->adaptive.wgs_per_cu.end()) return it->second;
+    int n = 0;
+    hipError_t e = hipSuccess;
+    if (fn) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, 0);
+    else dispatch_adaptive(c, k, [&](auto kernel) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0); });
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || n < 1) n = 1;
+    if (n > 8) n = 8;  // (a compute unit holds 32 waves)
+    c->adaptive.wgs_per_cu[key] = n;
+    return n;
+}
+
+extern "C" {
+
+// The argument checks come first, the context's last among them: all are decided on the host, before any device call.  Between
+// the three passes -- the base frame, the mask, the refinement -- nothing comes back to the host: the mask kernel is ordered
+// behind the base pass by being launched on `stream` (ctx_render_slot has joined its zero-fill stream back), the refinement's
+// grid does not depend on how many pixels were flagged.
+rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float threshold, void* d_out_rgb, void* d_mask_u8, void* stream_) {
+    if (!(threshold >= 0.0f) || !std::isfinite(threshold)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: the threshold must be finite and >= 0");
+    if (k != 2u && k != 4u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: supersampling factor %u: 2 or 4 rays per pixel side", k);
+    if (!d_out_rgb) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: null output buffer");
+    if ((uintptr_t)d_out_rgb & 3u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: the output must be 4-byte aligned");
+    if (depth < 0 || depth > RTC_MAX_DEPTH) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: depth %d outside [0, %d]", depth, RTC_MAX_DEPTH);
+    if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: ctx is NULL");
+    if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: no scene/camera set");
+    if (c->ss_k != 1u) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_adaptive: a supersampled context renders every pixel with k x k rays already");
+    rtc_camera fine;
+    RTC_TRY(rtc_camera_supersampled(&c->camera, k, &fine));  // (the fine frame's limits: 2^32 pixels, 2^17 rows)
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    rtc_ctx::Adaptive& ad = c->adaptive;
+    const Policy& P = c->policy;
+    const uint32_t width = c->hdr.width, height = c->hdr.height;
+    const size_t n_pixels = (size_t)width * height;
+    // ---- the refinement kernel: the policy's question is asked with the frame's pixels, as the base pass asks it
+    int32_t refine_depth = depth;
+    if (refine_depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) refine_depth = RTC_STACK_DEPTH_BASE;  // (as rtc_ctx_render)
+    const rtc_ctx::Adaptive::PerK& pk = ad.per_k[k == 4u ? 1 : 0];
+    const bool want = !pk.defs.empty() && wants_scene_kernel(P, n_pixels, c->trace.compile_any_size, c->trace.compile_never);
+    hipFunction_t fn = nullptr;
+    std::string id;
+    RTC_TRY(adaptive_kernel_for(c, refine_depth, k, want, &fn, &id));
+    auto renamed = [&](const std::string& name) {  // trace_kernel<...> -> adaptive_refine_kernel<...;ss=k>
+        std::string out = name.rfind("trace_", 0) == 0 ? "adaptive_refine_" + name.substr(6) : name;
+        if (!out.empty()) out.insert(out.size() - 1, ";ss=" + std::to_string(k));
+        return out;
+    };
+    // ---- workspaces (the list: first use / a larger frame only)
+    HIP_TRY(grow(&ad.d_list, &ad.list_cap, n_pixels));
+    if (!ad.d_queue) HIP_TRY(hipMalloc((void**)&ad.d_queue, sizeof(AdaptiveQueue)));
+    for (hipEvent_t& e : ad.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const void* const kernel_key = fn ? (const void*)fn : aot_family(c).key(k);
+    const uint32_t n_workgroups = adaptive_grid((uint32_t)compute_units(c), (uint32_t)adaptive_wgs_per_cu(c, fn, k, kernel_key), width, height, k);
+    AdaptiveRefineArgs a;
+    a.hdr = c->hdr;
+    a.hdr.width = fine.width, a.hdr.height = fine.height, a.hdr.pixel_size = fine.pixel_size;  // (half extents and transform: the same, checked)
+    a.hdr.has_scene_box = 0u;  // (rtc_adaptive.h)
+    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.list = ad.d_list, a.queue = ad.d_queue;
+    a.out = (float*)d_out_rgb;
+    a.out_width = width;
+    a.depth = refine_depth;
+    a.warm = 0u;
+    // ---- the base frame B: the context's normal render, with its tiles, lists, feedback and stats
+    RTC_TRY(rtc_ctx_render(c, depth, nullptr, d_out_rgb, stream_));
+    // ---- warm up (in front of the events), mask, refinement, sum
+    if (ad.warmed.insert(std::make_pair(kernel_key, (const void*)stream)).second) {
+        AdaptiveRefineArgs w = a;
+        w.warm = 1u;
+        HIP_TRY(launch_adaptive(c, fn, k, 1u, stream, w));
+    }
+    HIP_TRY(hipMemsetAsync(ad.d_queue, 0, sizeof(AdaptiveQueue), stream));
+    HIP_TRY(hipEventRecord(ad.ev[0], stream));
+    AdaptiveMaskArgs m;
+    m.frame = (const float*)d_out_rgb, m.mask = (uint8_t*)d_mask_u8, m.list = ad.d_list, m.queue = ad.d_queue;
+    m.width = width, m.height = height, m.threshold = threshold;
+    m.blocks_x = (width + 15u) / 16u, m.n_blocks = m.blocks_x * ((height + 15u) / 16u);
+    hipLaunchKernelGGL(adaptive_mask_kernel, dim3(adaptive_mask_grid((uint32_t)compute_units(c), m.n_blocks)), dim3(256), 0, stream, m);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ad.ev[1], stream));
+    HIP_TRY(launch_adaptive(c, fn, k, n_workgroups, stream, a));
+    HIP_TRY(hipEventRecord(ad.ev[2], stream));
+    // (named once it has been launched: a call that failed on the way names no kernel it did not run)
+    ad.name = renamed(fn ? c->trace.spec_name : c->trace.family_name);
+    ad.id = fn ? id : aot_adaptive_kernel_id(k);
+    ad.ran = true;
+    return RTC_OK;
+}
+
+// Waits for the device, as rtc_ctx_stats does.
+rtc_status rtc_ctx_adaptive_stats(rtc_ctx* c, rtc_adaptive_stats* out) {
+    if (!c || !out) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_adaptive_stats: null argument");
+    std::memset(out, 0, sizeof(*out));
+    const rtc_ctx::Adaptive& ad = c->adaptive;
+    if (!ad.ran) return RTC_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    AdaptiveQueue q;
+    HIP_TRY(hipMemcpy(&q, ad.d_queue, sizeof(q), hipMemcpyDeviceToHost));
+    out->refined_pixels = q.n_flagged;
+    out->rays = q.total[0], out->shaded_hits = q.total[1], out->culled_shadow_rays = q.total[2];
+    HIP_TRY(hipEventElapsedTime(&out->mask_ms, ad.ev[0], ad.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&out->refine_ms, ad.ev[1], ad.ev[2]));
+    return RTC_OK;
+}
+
+const char* rtc_ctx_adaptive_kernel_name(rtc_ctx* c) { return c ? c->adaptive.name.c_str() : ""; }
+const char* rtc_ctx_adaptive_kernel_id(rtc_ctx* c) { return c ? c->adaptive.id.c_str() : ""; }
+
+// Diagnostic (not in rtc.h; tests/test_adaptive_boundary.py, no device needed): rtc_adaptive.h's adaptive_slot -- the function the
+// refinement kernel calls -- for slots [first_slot, first_slot + n), {entry, sx, sy, lane} per slot into `out`, and
+// rtc_launch_plan.h's adaptive_grid into *grid.  -> a wave's step, in slots; 0: k is neither 2 nor 4.
+uint32_t rtc_diag_adaptive_plan(uint32_t k, uint32_t width, uint32_t height, uint32_t n_cus, uint32_t wgs_per_cu, uint64_t first_slot, uint32_t n,
+                                uint32_t* out, uint32_t* grid) {
+    if (k != 2u && k != 4u) return 0u;
+    for (uint32_t i = 0; out && i < n; i++) {
+        const AdaptiveSlot s = k == 4u ? adaptive_slot<4>(first_slot + i) : adaptive_slot<2>(first_slot + i);
+        out[4 * i] = s.entry, out[4 * i + 1] = s.sx, out[4 * i + 2] = s.sy, out[4 * i + 3] = s.lane;
+    }
+    if (grid) *grid = adaptive_grid(n_cus, wgs_per_cu, width, height, k);
+    return ADAPTIVE_STEP_SLOTS;
+}
 
 }  // extern "C"
 // rtc_ctx_stats' read-out, of the renders or of the traces: waits for the device, the last launch's counters (`total`), the mean

@@ -32,6 +32,18 @@ inline uint32_t tile_y0(uint32_t t) { return (t & 0x7fffu) << 2; }
 // pixel (log2), at origins that are multiples of their size: any s serves k = 2, k = 4 needs s <= 2.  (Block origins are
 // multiples of 4 pixels: groups never straddle blocks.)  k = 1: no cap.
 inline uint32_t ss_max_share_log2(uint32_t k) { return k == 4u ? 2u : 4u; }
+// Adaptive supersampling (rtc_adaptive.h; the slot -> (entry, sx, sy) mapping is that header's adaptive_slot).  The refinement's
+// grid: how many workgroups of four waves the device holds at once (the kernel's occupancy), and no more than a fully flagged
+// frame could give one step of ADAPTIVE_STEP_SLOTS slots per wave -- never a function of how many pixels ARE flagged, which the
+// host does not know.  The waves stride through the list's steps.
+constexpr uint32_t ADAPTIVE_STEP_SLOTS = 64u;
+inline uint32_t adaptive_grid(uint32_t n_cus, uint32_t wgs_per_cu, uint32_t width, uint32_t height, uint32_t k) {
+    const uint64_t slots = (uint64_t)width * height * k * k, per_wg = 4ull * ADAPTIVE_STEP_SLOTS;
+    const uint64_t resident = (uint64_t)std::max(1u, n_cus) * std::max(1u, wgs_per_cu);
+    return (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(resident, (slots + per_wg - 1u) / per_wg));
+}
+// ... and the mask kernel's: workgroups striding through the frame's 16 x 16 blocks, eight per compute unit at the most
+inline uint32_t adaptive_mask_grid(uint32_t n_cus, uint32_t n_blocks) { return std::max(1u, std::min(n_blocks, std::max(1u, n_cus) * 8u)); }
 // the blocks of the 16 x 16 tile at (x0, y0) at 2^s lanes per pixel, clipped to the partition
 inline void push_tile_blocks(std::vector<uint32_t>* out, uint32_t s, uint32_t x0, uint32_t y0, uint32_t width, uint32_t rows) {
     const uint32_t hbw = 16u >> (s >> 1), hbh = 16u >> ((s + 1u) >> 1);

@@ -80,6 +80,47 @@ class Renderer:
                                        C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
         return out
 
+    def render_adaptive(self, depth, k=2, threshold=0.1, out=None, mask=None, stream=None):
+        """Adaptive supersampling (rtc_ctx_render_adaptive) on `stream` (default: torch's current stream); asynchronous.  The
+        frame is render()'s, except that every pixel one of whose four neighbours differs from it by more than `threshold` in
+        some channel holds the k x k supersampled value instead (k = 2 or 4).  mask: None -> the frame; True -> (frame, mask)
+        with a fresh (height, width) uint8 tensor, 1 = refined; a tensor -> written and returned likewise."""
+        if out is None:
+            out = self.alloc()
+        # (checked, not asserted: the raw pointers go to kernels that write height x width x 3 floats / height x width bytes through them)
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.float32 and out.is_contiguous()
+                and out.numel() == self.height * self.width * 3):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of %d x %d x 3 on %s" % (self.height, self.width, self.device))
+        if mask is True:
+            mask = torch.empty((self.height, self.width), dtype=torch.uint8, device=self.device)
+        elif mask is False:
+            mask = None
+        if mask is not None and not (torch.is_tensor(mask) and mask.is_cuda and mask.device == self.device and mask.dtype == torch.uint8
+                                     and mask.is_contiguous() and mask.numel() == self.height * self.width):
+            raise ValueError("mask must be a contiguous uint8 CUDA tensor of %d x %d on %s" % (self.height, self.width, self.device))
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        L.check(self._lib.rtc_ctx_render_adaptive(self._ctx, int(depth), int(k), float(threshold), C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(mask.data_ptr()) if mask is not None else None, C.c_void_p(s.cuda_stream)),
+                self._lib)
+        return out if mask is None else (out, mask)
+
+    def adaptive_stats(self):
+        """Synchronises with the last render_adaptive() and returns what its mask and refinement passes did."""
+        st = L.rtc_adaptive_stats()
+        L.check(self._lib.rtc_ctx_adaptive_stats(self._ctx, C.byref(st)), self._lib)
+        return {"refined_pixels": int(st.refined_pixels), "rays": int(st.rays), "shaded_hits": int(st.shaded_hits),
+                "culled_shadow_rays": int(st.culled_shadow_rays), "mask_ms": float(st.mask_ms), "refine_ms": float(st.refine_ms)}
+
+    @property
+    def adaptive_kernel_name(self):
+        """The refinement kernel of the last render_adaptive() ("" before the first of the current scene)."""
+        return self._lib.rtc_ctx_adaptive_kernel_name(self._ctx).decode()
+
+    @property
+    def adaptive_kernel_id(self):
+        """Names the code object of the last render_adaptive()'s refinement, as kernel_id does for renders."""
+        return self._lib.rtc_ctx_adaptive_kernel_id(self._ctx).decode()
+
     def render_hits(self, planes=("object", "distance", "normal", "light"), out=None, part=None, stream=None):
         """The first hit of every pixel's ray (rtc_ctx_render_hits) on `stream` (default: torch's current stream);
         asynchronous.  -> {plane: tensor}: int32 (rows, w) for object / inside, float32 (rows, w) for distance / light,
