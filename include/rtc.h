@@ -33,7 +33,9 @@ extern "C" {
 #define RTC_ABI_VERSION 8 /* (rtc_ctx_trace_hits and rtc_ctx_is_shadowed were added at 8: two entry points more, no struct and
                              no existing signature changed, so callers built against the earlier 8 run unchanged; likewise
                              adaptive supersampling: rtc_ctx_render_adaptive, rtc_ctx_adaptive_stats, rtc_ctx_adaptive_kernel_name
-                             / _id and the struct rtc_adaptive_stats are additions, nothing that existed has moved) */
+                             / _id and the struct rtc_adaptive_stats are additions, nothing that existed has moved;
+                             ray reordering: rtc_ctx_ray_order, rtc_ctx_trace_reordered, rtc_ctx_reorder_stats and the struct
+                             rtc_reorder_stats, additions likewise) */
 /* reflection_recursion_depth (camera.rs:76: any i16; reference default 5, constants.rs:4; its author renders
  * reflect_refract at 20).  Accepted: 0 .. RTC_MAX_DEPTH.  The kernels keep one frame per suspended shade_hit
  * (world.rs:62-86); up to RTC_STACK_DEPTH_BASE levels every kernel has them, above that the scene's kernel is compiled
@@ -501,6 +503,58 @@ rtc_status rtc_ctx_camera_rays(rtc_ctx* ctx, const rtc_camera* camera, uint32_t 
  * "aot_trace_..." or "spec_..." ids of their own, as rtc_ctx_kernel_name / _id).  "" before the first trace of the current scene. */
 const char* rtc_ctx_trace_kernel_name(rtc_ctx* ctx);
 const char* rtc_ctx_trace_kernel_id(rtc_ctx* ctx);
+/* ------------------------------------------------------------------------
+ * Ray reordering: an incoherent stream sorted on the device, traced in sorted order, answered in the caller's.
+ * rtc_ctx_trace gives ray i to thread i, and a wave's time is that of its 64 rays together: a stream in random order costs
+ * several times a coherent one.  Every colour is exact whatever a ray's neighbours are, so the library may reorder.
+ *
+ * The coherence key of a ray: a 32-bit unsigned integer, a function of the stream alone (neither scene nor camera), computed
+ * with f32 + - * /, compares and float-to-int conversions only, nothing fused, no library function: the same bits on the host.
+ *  Stream box: per axis a, lo[a] and hi[a] are the minimum and maximum over the rays' origin components that are finite
+ *   (|x| <= FLT_MAX; +inf and -inf where there is none).  Signed zeros are equivalent below.
+ *  Origin cell of a component x with its axis' lo, hi: 0 if x is not finite or not hi > lo (a camera's rays all leave one
+ *   point); else t = (x - lo) * (16.0f / (hi - lo)) and the cell is 15 if t >= 16.0f, (int)t if t > 0.0f, else 0 (a NaN t: 0).
+ *   The three 4-bit cells are interleaved to 12 bits, x lowest: bit k of cell x, y, z is bit 3k, 3k + 1, 3k + 2.
+ *  Direction cell, the octahedral map on a 1024 x 1024 grid: |a| is a < 0.0f ? -a : a, sign(a) is a >= 0.0f ? 1.0f : -1.0f;
+ *   s = (|dx| + |dy|) + |dz|; if not s > 0.0f or s is not finite, u = v = 0; else px = dx / s, py = dy / s, and where
+ *   dz < 0.0f the fold (px, py) <- ((1.0f - |py|) * sign(px), (1.0f - |px|) * sign(py)), both from the unfolded values;
+ *   u = cell((px * 0.5f + 0.5f) * 1024.0f), v likewise from py, cell(t) = 1023 if t >= 1024.0f, (int)t if t > 0.0f, else 0.
+ *   u and v are interleaved to 20 bits, u lowest: bit k of u, v is bit 2k, 2k + 1.
+ *  key = origin << 20 | direction: bits [31:20] the origin, bits [19:0] the direction.
+ * The order of a stream: order[j] is the index of the ray that comes j-th by key, ties by index -- a stable sort, the same
+ * permutation on every run (a least-significant-digit radix sort on the device, no float arithmetic, no atomics on positions). */
+/* The order of n caller rays.  DEVICE pointers: d_origins, d_directions as rtc_ctx_trace takes them; d_order_u32 n x u32.
+ * Needs a context (its device, its scratch memory) but no scene.  Asynchronous on `stream`; nothing is read by the host.
+ * RTC_ERR_INVALID_ARG, decided before any device call, in this order: a null ray or output pointer with n > 0; origins /
+ * directions not 16-byte aligned, the output not 4-byte aligned; a null context.  n == 0 with the pointer checks passed:
+ * RTC_OK, nothing is launched (the context is not looked at).  Scratch memory that cannot be had: RTC_ERR_DEVICE, the context
+ * stays usable. */
+rtc_status rtc_ctx_ray_order(rtc_ctx* ctx, const void* d_origins, const void* d_directions, uint32_t n, void* d_order_u32,
+                             void* stream);
+/* rtc_ctx_trace with the stream sorted first: its arguments, its checks in its order, and the same bits in d_out_rgb, element i
+ * belonging to the caller's ray i.  The rays are ordered (as rtc_ctx_ray_order), gathered into the context's own buffers with
+ * their keys -- d_keys[i], or i where d_keys is NULL: a ray draws its light samples as in the caller's order -- traced there by
+ * rtc_ctx_trace's launch, and the colours stored back at out[order[j]].
+ * Afterwards the context is as after rtc_ctx_trace of the same stream: rtc_ctx_stats reports the trace (rays and shaded_hits
+ * equal the plain trace's; culled_shadow_rays is voted by whichever lanes share a wave, so it is not comparable), and
+ * rtc_ctx_trace_kernel_name / _id are those the plain trace of the same n would report.  Everything a trace leaves alone
+ * stays alone.  The scratch memory -- 52 bytes a ray: 16 for the sort's two (key, index) buffers, 12 of which later hold the
+ * colours, 36 for the gathered rays and keys -- is allocated by the first call that needs it, grows on demand (which waits for
+ * the device) and is released by rtc_ctx_destroy; if it cannot be had: RTC_ERR_DEVICE, the context stays usable.
+ * One stream at a time, as for the whole context.  Off by default for a reason: a stream that is coherent already pays the
+ * sort for nothing (DESIGN.md 8f says where the crossover lies). */
+rtc_status rtc_ctx_trace_reordered(rtc_ctx* ctx, int32_t depth, const void* d_origins, const void* d_directions,
+                                   const void* d_keys, uint32_t n, void* d_out_rgb, void* stream);
+typedef struct rtc_reorder_stats {
+    uint64_t n;        /* rays of the last rtc_ctx_trace_reordered                                                        */
+    float keys_ms;     /* HIP-event time of the stream box and the keys                                                   */
+    float sort_ms;     /* ... of the sort's four passes                                                                   */
+    float gather_ms;   /* ... of the gather into sorted order                                                             */
+    float trace_ms;    /* ... of the trace: the kernel rtc_ctx_stats times, its counter sum and any first-launch warm-up  */
+    float scatter_ms;  /* ... of the colours' way back                                                                    */
+} rtc_reorder_stats;
+/* Waits for the device as rtc_ctx_stats does; all zero before the first rtc_ctx_trace_reordered. */
+rtc_status rtc_ctx_reorder_stats(rtc_ctx* ctx, rtc_reorder_stats* out);
 /* ------------------------------------------------------------------------
  * Adaptive supersampling: k x k rays only where neighbouring pixels of the rendered frame differ.
  * For the context's resident scene and camera (W x H), k = 2 or 4 and an f32 threshold:

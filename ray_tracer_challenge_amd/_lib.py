@@ -91,6 +91,11 @@ class rtc_adaptive_stats(C.Structure):
                 ("mask_ms", C.c_float), ("refine_ms", C.c_float)]
 
 
+class rtc_reorder_stats(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("keys_ms", C.c_float), ("sort_ms", C.c_float), ("gather_ms", C.c_float), ("trace_ms", C.c_float),
+                ("scatter_ms", C.c_float)]
+
+
 class rtc_opts(C.Structure):
     _fields_ = [("devices", C.POINTER(C.c_int32)), ("n_devices", C.c_uint32), ("band_rows", C.c_uint32),
                 ("quantize", C.c_int32), ("out_on_device", C.c_int32)]
@@ -186,6 +191,9 @@ SIGNATURES = {
     "rtc_ctx_adaptive_stats": (C.c_int, [C.c_void_p, C.POINTER(rtc_adaptive_stats)]),
     "rtc_ctx_adaptive_kernel_name": (C.c_char_p, [C.c_void_p]),
     "rtc_ctx_adaptive_kernel_id": (C.c_char_p, [C.c_void_p]),
+    "rtc_ctx_ray_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtc_ctx_trace_reordered": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtc_ctx_reorder_stats": (C.c_int, [C.c_void_p, C.POINTER(rtc_reorder_stats)]),
     "rtc_intensity_at": (C.c_int, [C.POINTER(rtc_scene), FP, C.c_uint32, C.c_int32, FP]),
     "rtc_is_shadowed": (C.c_int, [C.POINTER(rtc_scene), FP, FP, C.c_uint32, C.c_int32, C.POINTER(C.c_int32)]),
     "rtc_point_on_light": (C.c_int, [C.POINTER(rtc_light), C.POINTER(C.c_int32), C.c_uint32, C.c_int32, FP]),
@@ -231,6 +239,9 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
          # adaptive supersampling: the refinement's slot -> (entry, sx, sy, lane) mapping and its grid (tests/test_adaptive_boundary.py)
          "rtc_diag_adaptive_plan": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+         # ray reordering: rtc_reorder.h's key function on host buffers, and the sort's plan {grid, segment, sub-tile} (tests/test_reorder_boundary.py)
+         "rtc_diag_ray_keys": (None, [FP, FP, C.c_uint32, FP, C.POINTER(C.c_uint32)]),
+         "rtc_diag_reorder_plan": (C.c_uint32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
          # rtc_scene_prep.h on the host: digests of what flatten packs and the text of plan_scene's choice (tests/test_scene_prep.py)
          "rtc_diag_scene_plan": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)])}
 

@@ -39,6 +39,7 @@
 #include "rtc_supersample.h"
 #include "rtc_trace.h"
 #include "rtc_adaptive.h"
+#include "rtc_reorder.h"
 #include "rtc_wavefront.h"
 #include "rtc_scene_prep.h"
 
@@ -245,6 +246,17 @@ struct rtc_ctx {
         std::set<std::pair<const void*, const void*>> warmed;  // (kernel, stream) pairs launched once
         std::map<const void*, int> wgs_per_cu;  // occupancy of a refinement kernel, asked once
     } adaptive;
+    // Ray reordering (rtc_ctx_ray_order, rtc_ctx_trace_reordered; rtc_reorder.h).  The sort's and the gather's buffers, events of
+    // its own; the trace in the middle is rtc_ctx_trace's and is reported as one.
+    struct Reorder {
+        bool dir_major = !REORDER_ORIGIN_MAJOR;  // RTC_AMD_REORDER_DIR_MAJOR (development): the direction in the key's top bits
+        uint8_t* d_scratch = nullptr;    // sort ping-pong (16 B a ray; the colours reuse 12 of them) + gathered rays and keys (36 B a ray)
+        size_t scratch_cap = 0;          // bytes
+        uint32_t* d_table = nullptr;     // the sort's [digit][workgroup] table, then the stream box (REORDER_TABLE_WORDS, allocated once)
+        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // around keys + box, sort, gather, trace, scatter
+        bool ran = false;                // the events have been recorded (by a reordered trace)
+        uint64_t last_n = 0;
+    } reorder;
     rtc_camera camera;             // the camera of the resident scene as rtc_ctx_set_scene took it (has_scene)
     uint32_t last_rows = 0;
     uint32_t last_share_log2 = 0;  // lanes per pixel (log2) the last launch was planned with (rtc_diag_ctx_share_log2)
@@ -638,6 +650,7 @@ rtc_status rtc_ctx_create(int32_t device, rtc_ctx** out) {
     rtc_ctx* c = new rtc_ctx();
     c->device = device;
     c->policy = Policy::from_env();  // the one place a context looks at the environment
+    if (const char* e = RTC_DEV_ENV("RTC_AMD_REORDER_DIR_MAJOR")) c->reorder.dir_major = *e && e[0] != '0';
     HIP_TRY(hipMalloc(&c->d_total, 3 * CTX_TOTAL_SLOTS * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(c->d_total, 0, 3 * CTX_TOTAL_SLOTS * sizeof(unsigned long long)));
     *out = c;
@@ -677,6 +690,10 @@ void rtc_ctx_destroy(rtc_ctx* c) {
     if (c->adaptive.d_list) (void)hipFree(c->adaptive.d_list);
     if (c->adaptive.d_queue) (void)hipFree(c->adaptive.d_queue);
     for (hipEvent_t e : c->adaptive.ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->reorder.d_scratch) (void)hipFree(c->reorder.d_scratch);
+    if (c->reorder.d_table) (void)hipFree(c->reorder.d_table);
+    for (hipEvent_t e : c->reorder.ev)
         if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -1737,23 +1754,26 @@ static hipError_t launch_trace(rtc_ctx* c, hipFunction_t fn, uint32_t n_workgrou
     return hipGetLastError();
 }
 
-extern "C" {
-
-// The argument checks come first, the context's last among them: all are decided on the host, before any device call.
-rtc_status rtc_ctx_trace(rtc_ctx* c, int32_t depth, const void* d_origins, const void* d_directions, const void* d_keys, uint32_t n,
-                         void* d_out_rgb, void* stream_) {
-    if (n > 0u && (!d_origins || !d_directions)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: null ray buffer");
-    if (n > 0u && !d_out_rgb) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: null output buffer");
+// rtc_ctx_trace's and rtc_ctx_trace_reordered's argument checks, the context's last among them: all are decided on the host, before
+// any device call.
+static rtc_status trace_args_ok(const char* who, const rtc_ctx* c, int32_t depth, const void* d_origins, const void* d_directions, const void* d_keys,
+                                uint32_t n, const void* d_out_rgb) {
+    if (n > 0u && (!d_origins || !d_directions)) return fail(RTC_ERR_INVALID_ARG, "%s: null ray buffer", who);
+    if (n > 0u && !d_out_rgb) return fail(RTC_ERR_INVALID_ARG, "%s: null output buffer", who);
     if (((uintptr_t)d_origins & 15u) || ((uintptr_t)d_directions & 15u))
-        return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: origins and directions must be 16-byte aligned");
-    if (((uintptr_t)d_keys & 3u) || ((uintptr_t)d_out_rgb & 3u)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: keys and output must be 4-byte aligned");
-    if (depth < 0 || depth > RTC_MAX_DEPTH) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: depth %d outside [0, %d]", depth, RTC_MAX_DEPTH);
-    if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: ctx is NULL");
-    if (!c->has_scene) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace: no scene set");
-    if (n == 0u) return RTC_OK;
+        return fail(RTC_ERR_INVALID_ARG, "%s: origins and directions must be 16-byte aligned", who);
+    if (((uintptr_t)d_keys & 3u) || ((uintptr_t)d_out_rgb & 3u)) return fail(RTC_ERR_INVALID_ARG, "%s: keys and output must be 4-byte aligned", who);
+    if (depth < 0 || depth > RTC_MAX_DEPTH) return fail(RTC_ERR_INVALID_ARG, "%s: depth %d outside [0, %d]", who, depth, RTC_MAX_DEPTH);
+    if (!c) return fail(RTC_ERR_INVALID_ARG, "%s: ctx is NULL", who);
+    if (!c->has_scene) return fail(RTC_ERR_INVALID_ARG, "%s: no scene set", who);
+    return RTC_OK;
+}
+
+// The trace itself, n > 0 rays whose arguments have been checked: the kernel's choice, its workspaces, the launch between the
+// trace's events, the counters.  (The device is the context's already.)
+static rtc_status trace_launch(rtc_ctx* c, int32_t depth, const void* d_origins, const void* d_directions, const void* d_keys, uint32_t n,
+                               void* d_out_rgb, hipStream_t stream) {
     // (rtc_ctx_set_scene refuses RTC_JITTER_SEQUENCE lights: no resident scene has one)
-    hipStream_t stream = (hipStream_t)stream_;
-    HIP_TRY(hipSetDevice(c->device));
     rtc_ctx::Trace& t = c->trace;
     const Policy& P = c->policy;
     if (depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) depth = RTC_STACK_DEPTH_BASE;  // (as rtc_ctx_render)
@@ -1795,6 +1815,161 @@ rtc_status rtc_ctx_trace(rtc_ctx* c, int32_t depth, const void* d_origins, const
     t.last_n = n;
     t.last = true;
     return RTC_OK;
+}
+
+// ---- ray reordering (rtc_reorder.h) ------------------------------------------------
+constexpr size_t REORDER_TABLE_WORDS = (size_t)REORDER_DIGITS * REORDER_MAX_GRID + 6u;
+constexpr size_t REORDER_SORT_BYTES = 16u, REORDER_GATHER_BYTES = 36u;  // per ray: DESIGN.md 8f
+struct ReorderBuffers {  // the scratch block of a stream of n rays
+    uint32_t *idx_a, *keys_a, *keys_b, *idx_b;  // the sort's ping-pong: the last pass leaves keys in keys_a (and the order where it is told to)
+    float* colours;                             // n x 3 f32 over keys_a, keys_b, idx_b: free once the order stands in idx_a
+    float4 *origins, *directions;               // gathered
+    uint32_t* keys;
+};
+static ReorderBuffers reorder_buffers(uint8_t* base, uint32_t n) {
+    ReorderBuffers b;
+    b.idx_a = (uint32_t*)base, b.keys_a = b.idx_a + n, b.keys_b = b.keys_a + n, b.idx_b = b.keys_b + n;
+    b.colours = (float*)b.keys_a;
+    b.origins = (float4*)(base + REORDER_SORT_BYTES * n), b.directions = b.origins + n;  // (16 n bytes in: 16-byte aligned)
+    b.keys = (uint32_t*)(b.directions + n);
+    return b;
+}
+// The scratch block (grow-only; a call in flight on this stream may still be using the old one: grow frees, which waits) and the table.
+static rtc_status reorder_room(rtc_ctx* c, uint32_t n, bool gathered) {
+    rtc_ctx::Reorder& r = c->reorder;
+    if (!r.d_table) HIP_TRY(hipMalloc((void**)&r.d_table, REORDER_TABLE_WORDS * sizeof(uint32_t)));
+    const hipError_t e = grow(&r.d_scratch, &r.scratch_cap, (size_t)n * (REORDER_SORT_BYTES + (gathered ? REORDER_GATHER_BYTES : 0u)));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // (the context stays usable: the next call allocates again)
+        return fail(RTC_ERR_DEVICE, "ray reordering: %zu bytes of scratch for %u rays: %s", (size_t)n * (REORDER_SORT_BYTES + REORDER_GATHER_BYTES), n,
+                    hipGetErrorString(e));
+    }
+    return RTC_OK;
+}
+// Keys of the stream (box, then keys: after_keys is recorded behind them if given), then the sort: d_order[j] = the ray that comes
+// j-th by key, ties by index.  Everything on `stream`, nothing read by the host.
+static rtc_status reorder_sort(rtc_ctx* c, const void* d_origins, const void* d_directions, uint32_t n, const ReorderBuffers& b, uint32_t* d_order,
+                               hipStream_t stream, hipEvent_t after_keys) {
+    rtc_ctx::Reorder& r = c->reorder;
+    uint32_t* const box = r.d_table + (size_t)REORDER_DIGITS * REORDER_MAX_GRID;
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)n + 255u) / 256u);
+    hipLaunchKernelGGL(reorder_box_init_kernel, dim3(1), dim3(64), 0, stream, box);
+    hipLaunchKernelGGL(reorder_box_kernel, dim3(std::min<uint32_t>(n_tiles, 2048u)), dim3(256), 0, stream, (const float4*)d_origins, n, box);
+    hipLaunchKernelGGL(reorder_keys_kernel, dim3(n_tiles), dim3(256), 0, stream, (const float4*)d_origins, (const float4*)d_directions, n, box, b.keys_a,
+                       r.dir_major);
+    HIP_TRY(hipGetLastError());
+    if (after_keys) HIP_TRY(hipEventRecord(after_keys, stream));
+    const ReorderPlan plan = reorder_plan(n, (uint32_t)compute_units(c));
+    const uint32_t* keys_in = b.keys_a;
+    const uint32_t* idx_in = nullptr;  // (the first pass: element i is ray i)
+    for (uint32_t pass = 0; pass < REORDER_PASSES; pass++) {
+        const bool to_b = (pass & 1u) == 0u;
+        uint32_t* const keys_out = to_b ? b.keys_b : b.keys_a;
+        uint32_t* const idx_out = pass + 1u == REORDER_PASSES ? d_order : to_b ? b.idx_b : b.idx_a;
+        hipLaunchKernelGGL(reorder_count_kernel, dim3(plan.grid), dim3(256), 0, stream, keys_in, n, plan.segment, 8u * pass, r.d_table);
+        hipLaunchKernelGGL(reorder_scan_kernel, dim3(1), dim3(1024), 0, stream, r.d_table, REORDER_DIGITS * plan.grid);
+        hipLaunchKernelGGL(reorder_scatter_kernel, dim3(plan.grid), dim3(256), 0, stream, keys_in, idx_in, n, plan.segment, 8u * pass,
+                           (const uint32_t*)r.d_table, keys_out, idx_out);
+        keys_in = keys_out, idx_in = idx_out;
+    }
+    HIP_TRY(hipGetLastError());
+    return RTC_OK;
+}
+
+extern "C" {
+
+rtc_status rtc_ctx_trace(rtc_ctx* c, int32_t depth, const void* d_origins, const void* d_directions, const void* d_keys, uint32_t n,
+                         void* d_out_rgb, void* stream_) {
+    RTC_TRY(trace_args_ok("rtc_ctx_trace", c, depth, d_origins, d_directions, d_keys, n, d_out_rgb));
+    if (n == 0u) return RTC_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return trace_launch(c, depth, d_origins, d_directions, d_keys, n, d_out_rgb, (hipStream_t)stream_);
+}
+
+rtc_status rtc_ctx_ray_order(rtc_ctx* c, const void* d_origins, const void* d_directions, uint32_t n, void* d_order_u32, void* stream_) {
+    if (n > 0u && (!d_origins || !d_directions)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_ray_order: null ray buffer");
+    if (n > 0u && !d_order_u32) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_ray_order: null output buffer");
+    if (((uintptr_t)d_origins & 15u) || ((uintptr_t)d_directions & 15u))
+        return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_ray_order: origins and directions must be 16-byte aligned");
+    if ((uintptr_t)d_order_u32 & 3u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_ray_order: output must be 4-byte aligned");
+    if (n == 0u) return RTC_OK;  // nothing to order, whatever the context
+    if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_ray_order: ctx is NULL");
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    RTC_TRY(reorder_room(c, n, false));
+    return reorder_sort(c, d_origins, d_directions, n, reorder_buffers(c->reorder.d_scratch, n), (uint32_t*)d_order_u32, stream, nullptr);
+}
+
+rtc_status rtc_ctx_trace_reordered(rtc_ctx* c, int32_t depth, const void* d_origins, const void* d_directions, const void* d_keys, uint32_t n,
+                                   void* d_out_rgb, void* stream_) {
+    RTC_TRY(trace_args_ok("rtc_ctx_trace_reordered", c, depth, d_origins, d_directions, d_keys, n, d_out_rgb));
+    if (n == 0u) return RTC_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    rtc_ctx::Reorder& r = c->reorder;
+    RTC_TRY(reorder_room(c, n, true));
+    for (hipEvent_t& e : r.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const ReorderBuffers b = reorder_buffers(r.d_scratch, n);
+    const dim3 grid((uint32_t)(((uint64_t)n + 255u) / 256u)), block(256);
+    HIP_TRY(hipEventRecord(r.ev[0], stream));
+    RTC_TRY(reorder_sort(c, d_origins, d_directions, n, b, b.idx_a, stream, r.ev[1]));
+    HIP_TRY(hipEventRecord(r.ev[2], stream));
+    hipLaunchKernelGGL(reorder_gather_kernel, grid, block, 0, stream, (const float4*)d_origins, (const float4*)d_directions, (const uint32_t*)d_keys,
+                       (const uint32_t*)b.idx_a, n, b.origins, b.directions, b.keys);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(r.ev[3], stream));
+    RTC_TRY(trace_launch(c, depth, b.origins, b.directions, b.keys, n, b.colours, stream));
+    HIP_TRY(hipEventRecord(r.ev[4], stream));
+    hipLaunchKernelGGL(reorder_scatter_colours_kernel, grid, block, 0, stream, (const float*)b.colours, (const uint32_t*)b.idx_a, n, (float*)d_out_rgb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(r.ev[5], stream));
+    r.last_n = n;
+    r.ran = true;
+    return RTC_OK;
+}
+
+// Waits for the device, as rtc_ctx_stats does.
+rtc_status rtc_ctx_reorder_stats(rtc_ctx* c, rtc_reorder_stats* out) {
+    if (!c || !out) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_reorder_stats: null argument");
+    std::memset(out, 0, sizeof(*out));
+    const rtc_ctx::Reorder& r = c->reorder;
+    if (!r.ran) return RTC_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    out->n = r.last_n;
+    float* const ms[5] = {&out->keys_ms, &out->sort_ms, &out->gather_ms, &out->trace_ms, &out->scatter_ms};
+    for (int k = 0; k < 5; k++) HIP_TRY(hipEventElapsedTime(ms[k], r.ev[k], r.ev[k + 1]));
+    return RTC_OK;
+}
+
+// Diagnostic (not in rtc.h; tests/test_reorder_boundary.py, no device needed): rtc_reorder.h's reorder_key -- the function the key
+// kernel calls -- on host buffers in rtc_ctx_trace's layout (n x 4 f32), with the stream box it is taken against in box_out
+// {lo x, y, z, hi x, y, z}.  Either output may be NULL.
+void rtc_diag_ray_keys(const float* origins, const float* directions, uint32_t n, float* box_out, uint32_t* keys_out) {
+    const float inf = REORDER_FLT_MAX * 2.0f;
+    ReorderBox box = {{inf, inf, inf}, {-inf, -inf, -inf}};
+    for (uint64_t i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++) {
+            const float x = origins[4u * i + a];
+            if (!reorder_finite(x)) continue;
+            if (x < box.lo[a]) box.lo[a] = x;
+            if (x > box.hi[a]) box.hi[a] = x;
+        }
+    for (int a = 0; box_out && a < 3; a++) box_out[a] = box.lo[a], box_out[3 + a] = box.hi[a];
+    bool dir_major = !REORDER_ORIGIN_MAJOR;
+    if (const char* e = RTC_DEV_ENV("RTC_AMD_REORDER_DIR_MAJOR")) dir_major = *e && e[0] != '0';
+    for (uint64_t i = 0; keys_out && i < n; i++)
+        keys_out[i] = reorder_key(box, origins[4u * i], origins[4u * i + 1u], origins[4u * i + 2u], directions[4u * i], directions[4u * i + 1u],
+                                  directions[4u * i + 2u], dir_major);
+}
+
+// Diagnostic (not in rtc.h): the sort's plan for n rays on a device of n_cus compute units, out = {grid, segment, sub-tile}: workgroup
+// w of `grid` owns elements [w * segment, min(n, (w + 1) * segment)) and walks them `sub-tile` at a time.  -> grid.
+uint32_t rtc_diag_reorder_plan(uint32_t n, uint32_t n_cus, uint32_t* out) {
+    const ReorderPlan p = reorder_plan(n, n_cus);
+    if (out) out[0] = p.grid, out[1] = p.segment, out[2] = REORDER_TILE;
+    return p.grid;
 }
 
 rtc_status rtc_ctx_camera_rays(rtc_ctx* c, const rtc_camera* camera, uint32_t y0, uint32_t n_rows, void* d_origins, void* d_directions, void* d_keys,

@@ -161,14 +161,19 @@ class Renderer:
             if not (ok and keys.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and keys.data_ptr() % 4 == 0):
                 raise ValueError("keys must be a contiguous int32 or uint32 CUDA tensor (n,) on %s" % self.device)
 
-    def trace(self, origins, directions, depth, keys=None, out=None, stream=None):
+    def trace(self, origins, directions, depth, keys=None, out=None, stream=None, reorder=False):
         """World::color_at for the caller's rays against the resident scene (rtc_ctx_trace) on `stream` (default: torch's
         current stream); asynchronous.  origins, directions: (n, 4) float32 on the renderer's device (x, y, z are read); the
         direction is used as given.  keys: (n,) int32 / uint32 -- ray i draws its light samples as pixel keys[i] (None: i).
         -> (n, 3) float32.
         With `stream` given and no `out`, the result is allocated by torch on its CURRENT stream and written on `stream`: keep it
         alive until `stream` has been waited for (or pass an `out` made on `stream`, or call out.record_stream(stream)).  One
-        stream at a time per renderer: two traces in flight on different streams race on what stats() reports."""
+        stream at a time per renderer: two traces in flight on different streams race on what stats() reports.
+        reorder=True (rtc_ctx_trace_reordered): the stream is sorted by a coherence key on the device, traced in that order and
+        answered in the caller's -- the same bits, element i still ray i's, keys=None still drawing as pixel i.  For streams whose
+        neighbours in memory are not neighbours in space (second bounces, shuffled or gathered rays); a coherent stream only pays
+        for the sort.  trace_hits() and is_shadowed() do not take the flag: compose them from ray_order() and
+        index_select."""
         n = self._ray_tensor(origins, "origins")
         self._ray_tensor(directions, "directions", n)
         self._key_tensor(keys, n)
@@ -180,10 +185,40 @@ class Renderer:
         if not 0 <= n < 2 ** 32:
             raise ValueError("at most 2^32 - 1 rays a call")
         s = torch.cuda.current_stream(self.device) if stream is None else stream
-        L.check(self._lib.rtc_ctx_trace(self._ctx, int(depth), C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
-                                        C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(s.cuda_stream)), self._lib)
+        entry = self._lib.rtc_ctx_trace_reordered if reorder else self._lib.rtc_ctx_trace
+        L.check(entry(self._ctx, int(depth), C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()),
+                      C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)),
+                self._lib)
         return out
+
+    def ray_order(self, origins, directions, out=None, stream=None):
+        """The coherence order of the caller's rays (rtc_ctx_ray_order) on `stream` (default: torch's current stream);
+        asynchronous.  origins, directions: as trace() takes them.  -> (n,) int32: out[j] is the index of the ray that comes j-th
+        by key (include/rtc.h spells the key out), ties by index -- origins.index_select(0, order) is the stream trace(reorder=True)
+        traces, and what trace_hits() / is_shadowed(), which have no flag of their own, can be given.  No scene is read.
+        With `stream` given and no `out`, keep the result alive as for trace()."""
+        n = self._ray_tensor(origins, "origins")
+        self._ray_tensor(directions, "directions", n)
+        if n > 2 ** 31 - 1:
+            raise ValueError("at most 2^31 - 1 rays a call (the order is int32)")
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int32, device=self.device)
+        if not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype == torch.int32 and out.is_contiguous()
+                and tuple(out.shape) == (n,) and out.data_ptr() % 4 == 0):
+            raise ValueError("out must be a contiguous int32 CUDA tensor (%d,) on %s" % (n, self.device))
+        if n == 0:  # (an empty tensor has no address to give)
+            return out
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        L.check(self._lib.rtc_ctx_ray_order(self._ctx, C.c_void_p(origins.data_ptr()), C.c_void_p(directions.data_ptr()), n,
+                                            C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)), self._lib)
+        return out
+
+    def reorder_stats(self):
+        """Synchronises with the last trace(reorder=True) and returns its phases' HIP-event times (all zero before the first)."""
+        st = L.rtc_reorder_stats()
+        L.check(self._lib.rtc_ctx_reorder_stats(self._ctx, C.byref(st)), self._lib)
+        return {"n": int(st.n), "keys_ms": float(st.keys_ms), "sort_ms": float(st.sort_ms), "gather_ms": float(st.gather_ms),
+                "trace_ms": float(st.trace_ms), "scatter_ms": float(st.scatter_ms)}
 
     def trace_hits(self, origins, directions, keys=None, planes=("object", "distance", "normal", "light"), out=None, stream=None):
         """The first hit of each of the caller's rays against the resident scene (rtc_ctx_trace_hits) on `stream` (default:
