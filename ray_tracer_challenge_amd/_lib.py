@@ -243,7 +243,15 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
          "rtc_diag_ray_keys": (None, [FP, FP, C.c_uint32, FP, C.POINTER(C.c_uint32)]),
          "rtc_diag_reorder_plan": (C.c_uint32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
          # rtc_scene_prep.h on the host: digests of what flatten packs and the text of plan_scene's choice (tests/test_scene_prep.py)
-         "rtc_diag_scene_plan": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)])}
+         "rtc_diag_scene_plan": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]),
+         # scene-tile lists: their two orders, the feedback's cost of a wave and its rule, the mask of a scene and camera, and what a
+         # context's last frame listed (tests/test_plane_tiles_plan.py, tests/test_gpu_plane_tiles.py)
+         "rtc_diag_tile_order": (C.c_uint32, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]),
+         "rtc_diag_wave_work": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
+         "rtc_diag_longest_first_pays": (C.c_int32, [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]),
+         "rtc_diag_scene_tile_mask": (C.c_uint32, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]),
+         "rtc_diag_ctx_scene_tiles": (None, [C.c_void_p, C.POINTER(rtc_partition), C.POINTER(C.c_uint32)]),
+         "rtc_diag_seam_ctx": (C.c_void_p, [C.c_uint32])}
 
 _lib = None
 _loaded = {}  # path -> CDLL
@@ -291,7 +299,15 @@ def load(path):
         _preload_torch_hip_runtime()
         L = C.CDLL(path)
         for name, (res, args) in list(SIGNATURES.items()) + list(EXTRA.items()):
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                # (a diagnostic that a library named by RTC_AMD_LIB lacks -- the parent commit's, loaded for an A/B by tools/ab_env.py:
+                # calling it there raises this same error.  The package's own libraries, and the ABI proper, must be complete.)
+                named = os.environ.get("RTC_AMD_LIB")
+                if name.startswith("rtc_diag_") and named and os.path.abspath(named) == path:
+                    continue
+                raise
             fn.restype = res
             fn.argtypes = args
         _loaded[path] = L

@@ -832,6 +832,19 @@ class World:
         L.check(L.lib().rtc_diag_scene_plan(C.byref(cs.scene), C.byref(camera._cam) if camera is not None else None, text, len(text), digests))
         return tuple(digests), dict(line.split("=", 1) for line in text.value.decode().splitlines())
 
+    def scene_tile_mask(self, camera):
+        """rtc_diag_scene_tile_mask: the 16 x 16 tiles of `camera`'s frame in which a primary ray can see anything of this world, as
+        rtc_ctx_set_scene would decide under the current environment, without a GPU -> a bool array (tile rows, tile columns), or
+        None where the scene gets no mask (not known, or RTC_AMD_SCENE_TILES does not want one)."""
+        cs = self._c()
+        tw, th = (camera.width + 15) // 16, (camera.height + 15) // 16
+        mask, dims = np.zeros(tw * th, dtype=np.uint8), (C.c_uint32 * 2)()
+        n = L.lib().rtc_diag_scene_tile_mask(C.byref(cs.scene), C.byref(camera._cam), mask.ctypes.data_as(C.POINTER(C.c_uint8)), mask.size, dims)
+        if n == 0:
+            return None
+        assert (dims[0], dims[1]) == (tw, th) and n == tw * th
+        return mask.reshape(th, tw) != 0
+
     def color_at(self, origins, directions, depth, device=0):
         """World::color_at for a batch of rays (world.rs:88-101); (n,4),(n,4) -> (n,3)."""
         o = np.ascontiguousarray(np.asarray(origins, dtype=f32).reshape(-1, 4))

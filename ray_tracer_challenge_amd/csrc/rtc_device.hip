@@ -159,17 +159,26 @@ struct rtc_ctx {
     std::map<std::array<uint32_t, 5>, BlockList> block_lists;
     float scene_box_coverage = 1.0f;  // share of the image the scene's box projects to (1: unknown / all of it)
     uint32_t scene_rect[4] = {0u, 0u, 0u, 0u};  // the 16 x 16 tiles outside which no primary ray sees anything: [x0, x1) x [y0, y1); empty: unknown
-    // Scene tiles: of a bounded world whose entries project to a small part of the frame (C5: 64 spheres, 7 % of 8192^2), the 16 x 16
-    // tiles some entry's padded box projects to.  Frames of such a scene are a zero-fill of the canvas and one workgroup per
-    // listed tile (ctx_render_slot), instead of the bounding rectangle of them all.  Empty: not known / not worth it.
+    // Scene tiles: the 16 x 16 tiles in which a primary ray can see anything -- those some bounded entry's padded box projects to (C5:
+    // 64 spheres, 7 % of 8192^2) and the near side of every top-level plane's horizon (C3: two thirds of the frame).  Frames of such a
+    // scene are a zero-fill of the other tiles and one workgroup per listed tile (ctx_render_slot).  Empty: not known / not worth it.
     std::vector<uint8_t> scene_tile_mask;
     uint32_t scene_tiles_w = 0u, scene_tiles_h = 0u;
+    bool scene_tiles_sparse = false;  // ScenePlan's: the list also serves frames whose rows are reported chunk by chunk
     struct SceneTileList {
         uint32_t* d = nullptr;
         size_t n = 0;
         unsigned long long traced_pixels = 0ull;  // traced pixels (x < w - 1, y < h - 1) inside the listed tiles
         uint2* d_fill = nullptr;  // the runs of tiles that are NOT listed, at most 64 tiles each: {x0 | n << 16, local row} (fill_tiles_kernel)
         size_t n_fill = 0;
+        // feedback (order_scene_tiles): the list as launched, and where its first frame leaves its waves' work counts ([4 n] uint4, a
+        // copy of block_counts).  IDLE: a scene's first frame -- as for a regular grid, nothing is measured (or allocated) before a
+        // second frame of the same scene shows that frames repeat; FRESH: the next frame leaves its counts; TIMED: they are on the
+        // device; SETTLED: ordered, or left as it is
+        std::vector<uint32_t> host;
+        uint4* d_counts = nullptr;
+        enum { IDLE, FRESH, TIMED, SETTLED } state = IDLE;
+        bool ordered = false;  // SETTLED, and the list was re-ordered
     };
     hipStream_t fill_stream = nullptr;  // the zero-fill of a tile launch runs beside the render kernel (fork / join by events)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -310,6 +319,7 @@ static void drop_scene_tile_lists(rtc_ctx* c) {
     for (auto& tl : c->scene_tile_lists) {
         if (tl.second.d) (void)hipFree(tl.second.d);
         if (tl.second.d_fill) (void)hipFree(tl.second.d_fill);
+        if (tl.second.d_counts) (void)hipFree(tl.second.d_counts);
     }
     c->scene_tile_lists.clear();
 }
@@ -808,7 +818,7 @@ static rtc_status order_grid(rtc_ctx* c, BlockList& bl, uint32_t gx, uint32_t gy
         HIP_TRY(hipMemcpy(staging, bl.d_ticks, 4u * nt * sizeof(uint4), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < 4u * nt; i++) {  // (in place: ticks[i] overwrites a word of counts[i / 4], which has been read)
             const uint4 n = counts[i];
-            ticks[i] = (n.x - std::min(n.x, n.z)) + 16u * n.y + n.z / 8u;
+            ticks[i] = wave_work(n.x, n.y, n.z);
         }
     } else {
         HIP_TRY(hipMemcpy(staging, bl.d_ticks, 4u * nt * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -827,14 +837,10 @@ static rtc_status order_grid(rtc_ctx* c, BlockList& bl, uint32_t gx, uint32_t gy
     bl.state = BlockList::REFINED;
     bl.listed = false;
     {
-        std::vector<uint32_t> block_cost(nt), sorted_cost;
-        for (size_t b = 0; b < nt; b++) block_cost[b] = std::max(std::max(ticks[4 * b], ticks[4 * b + 1]), std::max(ticks[4 * b + 2], ticks[4 * b + 3]));
-        sorted_cost = block_cost;
-        std::sort(sorted_cost.begin(), sorted_cost.end(), std::greater<uint32_t>());
-        const size_t wg_slots = (size_t)(wave_slots / 4.0);
-        const double in_order = simulate_dispatch(block_cost, wg_slots), longest_first = simulate_dispatch(sorted_cost, wg_slots);
+        double in_order = 0.0, longest_first = 0.0;
+        const bool pays = longest_first_pays(ticks, nt, (size_t)(wave_slots / 4.0), &in_order, &longest_first);
         if (P.jit_print) std::fprintf(stderr, "librtc_amd: grid of %zu blocks: modelled frame %.4g in image order, %.4g longest first\n", nt, in_order, longest_first);
-        if (!(longest_first < 0.97 * in_order)) return RTC_OK;  // (the grid stays)
+        if (!pays) return RTC_OK;  // (the grid stays)
     }
     refine_block_list(launched, ticks, c->hdr.width, rows, wave_slots, INFINITY, 0.0, &ordered);
     if (ordered.empty() || ordered.size() > bl.n) return RTC_OK;
@@ -977,6 +983,7 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     c->scene_rect_coverage = plan.scene_rect_coverage;
     c->scene_tile_mask.swap(plan.scene_tile_mask);
     if (!c->scene_tile_mask.empty()) c->scene_tiles_w = plan.scene_tiles_w, c->scene_tiles_h = plan.scene_tiles_h;
+    c->scene_tiles_sparse = plan.scene_tiles_sparse;
     c->spec_shares = plan.spec_shares, c->spec_blocks_y = plan.spec_blocks_y, c->spec_rect = plan.spec_rect;
     if (plan.tree_waves) c->tree_waves = plan.tree_waves;
     c->wf_pays = plan.wf_pays;
@@ -1186,7 +1193,7 @@ struct LaunchLists {
     uint32_t* d_ticks = nullptr;        // RenderArgs::wave_ticks
     BlockList* timed_list = nullptr;    // a list whose own events bracket this launch
     void* copy_counts_to = nullptr;     // where the launch's wave counts go afterwards, on its stream
-    const rtc_ctx::SceneTileList* scene_tiles = nullptr;
+    rtc_ctx::SceneTileList* scene_tiles = nullptr;
 };
 
 // (a world in which nothing reflects or transmits -- an empty world among them, which the reference renders black at any
@@ -1262,16 +1269,58 @@ static rtc_status use_block_list(rtc_ctx* c, const Partition& q, uint32_t rows, 
     return RTC_OK;
 }
 
+// A scene-tile list's second frame has left what its waves counted (SceneTileList::TIMED): as order_grid, for a list -- the same
+// cost of a wave, the same model of the dispatcher, the same 3 %.  The tiles stay whole and the fill runs as they are.
+static rtc_status order_scene_tiles(rtc_ctx* c, rtc_ctx::SceneTileList& tl, uint32_t rows) {
+    HIP_TRY(hipDeviceSynchronize());  // (once per scene and partition)
+    tl.state = rtc_ctx::SceneTileList::SETTLED;
+    void* staging = nullptr;
+    HIP_TRY(feedback_staging(c, 4u * tl.n * sizeof(uint4), &staging));
+    HIP_TRY(hipMemcpy(staging, tl.d_counts, 4u * tl.n * sizeof(uint4), hipMemcpyDeviceToHost));
+    const uint4* counts = (const uint4*)staging;
+    uint32_t* ticks = (uint32_t*)staging;
+    for (size_t i = 0; i < 4u * tl.n; i++) {  // (in place: ticks[i] overwrites a word of counts[i / 4], which has been read)
+        const uint4 n = counts[i];
+        ticks[i] = wave_work(n.x, n.y, n.z);
+    }
+    double in_order = 0.0, longest_first = 0.0;
+    const bool pays = longest_first_pays(ticks, tl.n, (size_t)(0.85 * compute_units(c) * 6.0), &in_order, &longest_first);
+    if (c->policy.jit_print)
+        std::fprintf(stderr, "librtc_amd: scene tiles: list of %zu: modelled frame %.4g in list order, %.4g longest first\n", tl.n, in_order, longest_first);
+    if (!pays) return RTC_OK;  // (the list stays)
+    std::vector<uint32_t> ordered;
+    order_tile_list(tl.host, ticks, c->hdr.width, rows, &ordered);
+    if (ordered.size() != tl.n) return RTC_OK;
+    HIP_TRY(hipMemcpy(tl.d, ordered.data(), tl.n * sizeof(uint32_t), hipMemcpyHostToDevice));  // (nothing is in flight: the synchronisation above)
+    tl.host.swap(ordered);
+    tl.ordered = true;
+    return RTC_OK;
+}
+
 // Scene tiles (rtc_ctx::scene_tile_mask): the canvas is zero-filled at memory speed (805 MB of an 8192^2 frame: 0.12 ms) and
 // only the tiles some entry of the world projects to get a workgroup -- C5: 18 k of 262 k, where the bounding rectangle of
 // them all has 60 k, and a frame of such short waves costs what starting them costs (0.78 waves per ns).  The partition's
 // list, built and uploaded on first use (an empty one: nothing of the scene in this partition's rows).
-static rtc_status use_scene_tile_list(rtc_ctx* c, const Partition& q, hipStream_t stream, const rtc_ctx::SceneTileList** out) {
+// The list's first frame starts its tiles in the grid's permuted order (swizzle_tile_list); the second of the same scene leaves its
+// waves' work counts, and the frames after it start the tiles longest first where the grid feedback's model says that pays
+// (order_scene_tiles).
+static rtc_status use_scene_tile_list(rtc_ctx* c, const Partition& q, uint32_t rows, bool feedback, hipStream_t stream, LaunchLists* L) {
+    const Policy& P = c->policy;
     const std::array<uint32_t, 3> key = {q.band_rows, q.n_parts, q.part};
     auto it = c->scene_tile_lists.find(key);
     if (it == c->scene_tile_lists.end()) {
+        // (a caller cycling through partitions without end: start over -- nothing may be in flight)
+        if (c->scene_tile_lists.size() >= 256u) {
+            HIP_TRY(hipDeviceSynchronize());
+            drop_scene_tile_lists(c);
+        }
         SceneTilePlan host;
         plan_scene_tiles(TileMask{c->scene_tile_mask.data(), c->scene_tiles_w, c->scene_tiles_h}, c->hdr.width, c->hdr.height, q, &host);
+        if (P.swizzle) {
+            std::vector<uint32_t> permuted;
+            swizzle_tile_list(host.tiles, c->hdr.width, rows, &permuted);
+            host.tiles.swap(permuted);
+        }
         static_assert(sizeof(FillRun) == sizeof(uint2), "fill_tiles_kernel reads the runs as uint2");
         rtc_ctx::SceneTileList tl;
         tl.n = host.tiles.size();
@@ -1286,21 +1335,33 @@ static rtc_status use_scene_tile_list(rtc_ctx* c, const Partition& q, hipStream_
             }
             HIP_TRY(hipStreamSynchronize(stream));  // (the host vectors go out of scope)
         }
+        tl.host.swap(host.tiles);
         it = c->scene_tile_lists.emplace(key, tl).first;
+    }
+    rtc_ctx::SceneTileList& tl = it->second;
+    if (tl.n && feedback) {
+        if (tl.state == rtc_ctx::SceneTileList::TIMED) RTC_TRY(order_scene_tiles(c, tl, rows));
+        if (tl.state == rtc_ctx::SceneTileList::IDLE) {
+            tl.state = rtc_ctx::SceneTileList::FRESH;
+        } else if (tl.state == rtc_ctx::SceneTileList::FRESH) {
+            if (!tl.d_counts) HIP_TRY(hipMalloc((void**)&tl.d_counts, 4u * tl.n * sizeof(uint4)));
+            L->copy_counts_to = tl.d_counts;
+            tl.state = rtc_ctx::SceneTileList::TIMED;
+        }
     }
     if (it->second.n && !c->fill_stream) {  // the zero-fill runs beside the render kernel (fork / join by events)
         HIP_TRY(hipStreamCreateWithFlags(&c->fill_stream, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     }
-    *out = &it->second;
+    L->scene_tiles = &it->second;
     return RTC_OK;
 }
 
 // A regular grid's frames after the first: the same 16 x 16 blocks, started in the order of their longest wave in the frame
 // before (refine_block_list: a list of one lane per pixel throughout).  Where the grid is the plain one -- one block per
 // workgroup, no scene rectangle, nobody waiting for rows in image order (rtc_render_ex's progress words) -- and the frame
-// has a tail worth the list: its longest wave is a tenth of its throughput time or more.
+// has a tail worth the list: a model of the dispatcher ends it at least 3 % earlier longest first (order_grid).
 // timed_waves: the kernel leaves its waves' times (else their work counts are taken).
 static rtc_status use_grid_feedback(rtc_ctx* c, const Partition& q, uint32_t rows, int32_t depth, bool timed_waves, hipStream_t stream, LaunchPlan* lp,
                                     LaunchLists* L) {
@@ -1411,8 +1472,10 @@ static rtc_status settle_shape(rtc_ctx* c, const Partition& q, uint32_t rows, in
                                bool out_u8, const ProgressPlan* progress, hipStream_t stream, LaunchPlan* lp, LaunchLists* L) {
     const Policy& P = c->policy;
     const bool list_words_fit = c->hdr.width <= 65532u && rows <= 131068u;  // (tile_word)
-    if (lp->shape == LaunchPlan::GRID && share_log2 == 0u && !c->scene_tile_mask.empty() && (q.band_rows & 15u) == 0u && list_words_fit) {
-        RTC_TRY(use_scene_tile_list(c, q, stream, &L->scene_tiles));
+    if (lp->shape == LaunchPlan::GRID && share_log2 == 0u && !c->scene_tile_mask.empty() && (q.band_rows & 15u) == 0u && list_words_fit &&
+        (progress == nullptr || c->scene_tiles_sparse)) {
+        // (the feedback: as for the grid, not where rows are reported chunk by chunk -- the seam's frames pay no wait for it)
+        RTC_TRY(use_scene_tile_list(c, q, rows, P.block_feedback && P.grid_feedback && progress == nullptr, stream, L));
         if (L->scene_tiles->n) {
             lp->run_scene_tiles(L->scene_tiles->n, c->last_pixels - L->scene_tiles->traced_pixels);
             L->d_tiles = L->scene_tiles->d;
@@ -1599,6 +1662,49 @@ uint64_t rtc_diag_scene_tiles(const uint8_t* mask, uint32_t mask_w, uint32_t mas
     for (size_t i = 0; i < plan.fill.size() && i < cap; i++) fill[2 * i] = plan.fill[i].x0_n, fill[2 * i + 1] = plan.fill[i].row;
     counts[0] = (uint32_t)plan.tiles.size(), counts[1] = (uint32_t)plan.fill.size();
     return plan.traced_pixels;
+}
+// A scene-tile list's orders (tests/test_plane_tiles_plan.py): ticks == NULL: the first frame's (swizzle_tile_list); else the
+// feedback's from four wave costs per tile (order_tile_list).  -> the new list's length (its first min(that, cap) words in `out`).
+uint32_t rtc_diag_tile_order(const uint32_t* list, const uint32_t* ticks, uint32_t n, uint32_t width, uint32_t rows, uint32_t* out, uint32_t cap) {
+    std::vector<uint32_t> l(list, list + n), made;
+    if (ticks) order_tile_list(l, ticks, width, rows, &made);
+    else swizzle_tile_list(l, width, rows, &made);
+    for (size_t i = 0; i < made.size() && i < cap; i++) out[i] = made[i];
+    return (uint32_t)made.size();
+}
+// ... and the cost of a wave that counted {rays, shade points, culled shadow rays}, and whether longest first is worth a list
+uint32_t rtc_diag_wave_work(uint32_t rays, uint32_t shade_points, uint32_t culled) { return wave_work(rays, shade_points, culled); }
+int32_t rtc_diag_longest_first_pays(const uint32_t* ticks, uint32_t n_blocks, uint32_t wg_slots) { return longest_first_pays(ticks, n_blocks, wg_slots) ? 1 : 0; }
+// The scene-tile mask of a scene and camera under the environment's policy: -> the number of tiles written (w * h; 0: the scene has
+// no mask -- not known, or the policy does not want it), dims = {w, h}.
+uint32_t rtc_diag_scene_tile_mask(const rtc_scene* scene, const rtc_camera* camera, uint8_t* mask, uint32_t cap, uint32_t dims[2]) {
+    dims[0] = dims[1] = 0u;
+    if (!scene || !camera) return 0u;
+    const Policy P = Policy::from_env();
+    SceneHdr hdr;
+    std::vector<float4> soa;
+    std::vector<float> texels, heavy_boxes;
+    SceneRegion region;
+    if (flatten(P, scene, camera, &hdr, &soa, &texels, &heavy_boxes, &region) != RTC_OK) return 0u;
+    ScenePlan p;
+    plan_coverage(P, hdr, camera, region, &p);
+    if (p.scene_tile_mask.empty() || p.scene_tile_mask.size() > cap) return 0u;
+    std::memcpy(mask, p.scene_tile_mask.data(), p.scene_tile_mask.size());
+    dims[0] = p.scene_tiles_w, dims[1] = p.scene_tiles_h;
+    return (uint32_t)p.scene_tile_mask.size();
+}
+// What the context's last rtc_ctx_render left out: {tiles listed, fill runs, feedback} of the partition's scene-tile list (0, 0: the
+// frame was not drawn from one); feedback: 0 the list has not been launched with feedback, 1 its counts are on the device, 2 they
+// have been judged and the list stays, 3 ... and the list was re-ordered.
+void rtc_diag_ctx_scene_tiles(rtc_ctx* c, const rtc_partition* part, uint32_t out[3]) {
+    out[0] = out[1] = out[2] = 0u;
+    if (!c) return;
+    const Partition q = resolve(part);
+    auto it = c->scene_tile_lists.find({q.band_rows, q.n_parts, q.part});
+    if (it == c->scene_tile_lists.end()) return;
+    const rtc_ctx::SceneTileList& tl = it->second;
+    out[0] = (uint32_t)tl.n, out[1] = (uint32_t)tl.n_fill;
+    out[2] = tl.state <= rtc_ctx::SceneTileList::FRESH ? 0u : tl.state == rtc_ctx::SceneTileList::TIMED ? 1u : tl.ordered ? 3u : 2u;
 }
 // A scene-rectangle launch of a partition: out = {grid_x, grid_y, blocks_y, block_x0, block_y0, fill_wg_rows, fill_rows, fill_period,
 // fill_rect[4]}; -> extra_rays.

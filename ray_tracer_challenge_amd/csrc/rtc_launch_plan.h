@@ -6,6 +6,7 @@
 #define RTC_LAUNCH_PLAN_H
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -229,6 +230,49 @@ inline void plan_scene_tiles(const TileMask& mask, uint32_t width, uint32_t heig
             close_run();
         }
     });
+}
+
+// Scheduling for scene-tile lists: what the regular grid has (RenderArgs::swizzle for a first frame, the grid feedback's order for
+// the later ones), as arithmetic on the list.
+// What a wave cost, from what it counted (RenderArgs::block_counts: rays, shade points, shadow rays the light-cone cull resolved):
+// rays that met objects, and shade points (each a light-cone cull, a Phong evaluation, a push or pop of the recursion) at sixteen
+// rays apiece.
+inline uint32_t wave_work(uint32_t rays, uint32_t shade_points, uint32_t culled) { return (rays - std::min(rays, culled)) + 16u * shade_points + culled / 8u; }
+// Is the longest-first order worth a list?  Both orders go through a model of the dispatcher with the blocks' costs (ticks: four
+// waves per block): yes when it ends the frame at least 3 % earlier.
+inline bool longest_first_pays(const uint32_t* ticks, size_t n_blocks, size_t wg_slots, double* in_order = nullptr, double* longest_first = nullptr) {
+    std::vector<uint32_t> block_cost(n_blocks), sorted_cost;
+    for (size_t b = 0; b < n_blocks; b++) block_cost[b] = std::max(std::max(ticks[4 * b], ticks[4 * b + 1]), std::max(ticks[4 * b + 2], ticks[4 * b + 3]));
+    sorted_cost = block_cost;
+    std::sort(sorted_cost.begin(), sorted_cost.end(), std::greater<uint32_t>());
+    const double a = simulate_dispatch(block_cost, wg_slots), b = simulate_dispatch(sorted_cost, wg_slots);
+    if (in_order) *in_order = a;
+    if (longest_first) *longest_first = b;
+    return b < 0.97 * a;
+}
+// A scene-tile list's first frame: the list is in image order (plan_scene_tiles); the regular grid starts its blocks permuted within
+// four block rows -- workgroup j of such a group renders block (2 (j >> 3) + (j & 1), (j & 7) >> 1) of it -- and so does the list:
+// its tiles in the order in which that walk meets them.  (Tiles are whole, one lane per pixel: `list` holds one word per tile.)
+inline void swizzle_tile_list(const std::vector<uint32_t>& list, uint32_t width, uint32_t rows, std::vector<uint32_t>* out) {
+    const uint32_t tw = (width + 15u) / 16u, th = (rows + 15u) / 16u, gx = (tw + 1u) & ~1u;
+    std::vector<int32_t> index((size_t)tw * th, -1);
+    out->clear();
+    for (size_t i = 0; i < list.size(); i++) {
+        const uint32_t tx = tile_x0(list[i]) / 16u, ty = tile_y0(list[i]) / 16u;
+        if (tx >= tw || ty >= th || index[(size_t)ty * tw + tx] >= 0) return (void)(*out = list);  // (not a tile list of this frame: as it is)
+        index[(size_t)ty * tw + tx] = (int32_t)i;
+    }
+    out->reserve(list.size());
+    for (uint32_t ty0 = 0; ty0 < th; ty0 += 4u)
+        for (uint32_t j = 0; j < 4u * gx; j++) {
+            const uint32_t tx = 2u * (j >> 3) + (j & 1u), ty = ty0 + ((j & 7u) >> 1);
+            if (tx < tw && ty < th && index[(size_t)ty * tw + tx] >= 0) out->push_back(list[(size_t)index[(size_t)ty * tw + tx]]);
+        }
+}
+// ... and its later frames: the tiles by the longest of their four waves' costs in the frame before (ticks: [4 list.size()], in
+// the order of `list`), longest first, equal ones in list order.
+inline void order_tile_list(const std::vector<uint32_t>& list, const uint32_t* ticks, uint32_t width, uint32_t rows, std::vector<uint32_t>* out) {
+    refine_block_list(list, ticks, width, rows, 1.0, INFINITY, 0.0, out);
 }
 
 // What RenderArgs and the launch need to know of a frame's geometry.  `shape` says which of the mutually exclusive ways

@@ -228,6 +228,13 @@ void rtc_render_release(void) {
     g_state.clear();
 }
 
+// Diagnostics (not in rtc.h; tests/test_gpu_plane_tiles.py): the context rtc_render_ex keeps for entry k of opts->devices, for the
+// rtc_diag_ctx_* questions about its last frame (NULL: none; it lives until rtc_render_release).
+rtc_ctx* rtc_diag_seam_ctx(uint32_t k) {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    return k < g_state.size() ? g_state[k].ctx : nullptr;
+}
+
 rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, const rtc_opts* opts, void* out,
                          rtc_stats* stats) {
     if (!out || !camera) return fail(RTC_ERR_INVALID_ARG, "rtc_render: null argument");

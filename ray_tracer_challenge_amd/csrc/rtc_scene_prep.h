@@ -232,11 +232,17 @@ inline void triangle_box(const rtc_object& o, const float4 tri[3], double d_worl
 #else
 #define RTC_DEV_ENV(name) ((const char*)nullptr)
 #endif
+// Scene tiles (plan_coverage): the share of the 16 x 16 tiles of a frame of a world with planes, in percent, that must be unseen for
+// the frame to be drawn from a tile list instead of the regular grid or the scene's rectangle (profiles/plane_tiles_ab.txt has the sweep).
+constexpr uint32_t SCENE_TILES_UNSEEN_PCT = 20u;
 struct Policy {
     int specialise = 2;  // RTC_AMD_SPECIALIZE: 0 never, 1 always (a failed compile is an error), 2 by frame size
     bool light_cull = true, dark = true, fast_shadow = true, cell_cull = true, own_blocks = true;  // RTC_AMD_LIGHT_CULL / _DARK / _FAST_SHADOW / _CELL_CULL / _OWN_BLOCKS (SceneHdr::cull_flags)
     bool bvh = true, scene_box = true, gates = true, tri_precull = true, block_list = true, quiet = false;
-    bool scene_tiles = true;  // RTC_AMD_SCENE_TILES: a sparse bounded scene's frames as zero-fill + its own tiles (rtc_ctx::scene_tile_mask)
+    // RTC_AMD_SCENE_TILES: frames as a zero-fill of the tiles nothing can be seen in + one workgroup for each of the others
+    // (rtc_ctx::scene_tile_mask): 0 never, 1 where it pays (plan_coverage: SCENE_TILES_UNSEEN_PCT; sparse bounded worlds), 2 whenever any
+    // tile is unseen
+    int scene_tiles = 1;
     bool prune = true;    // RTC_AMD_PRUNE: groups / nodes a ray enters beyond what it still wants are left closed (for_each_object, ERROR_BUDGET.md B6)
     int clusters = -1;    // RTC_AMD_CLUSTERS: nodes over long triangle runs -- 0 never, 1 always, -1 by frame size
     int share_log2 = -1;  // RTC_AMD_SHARE_LOG2 = 0..3: lanes per pixel (log2) pinned for every frame; -1: by frame size
@@ -269,7 +275,7 @@ struct Policy {
         p.gates = flag(std::getenv("RTC_AMD_GATES"), true);
         p.tri_precull = flag(std::getenv("RTC_AMD_TRI_PRECULL"), true);
         p.prune = flag(std::getenv("RTC_AMD_PRUNE"), true);
-        p.scene_tiles = flag(std::getenv("RTC_AMD_SCENE_TILES"), true);
+        if (const char* e = std::getenv("RTC_AMD_SCENE_TILES")) p.scene_tiles = e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;
         p.block_list = flag(std::getenv("RTC_AMD_BLOCK_LIST"), true);
         p.block_feedback = flag(std::getenv("RTC_AMD_BLOCK_FEEDBACK"), true);
         p.grid_feedback = flag(std::getenv("RTC_AMD_GRID_FEEDBACK"), true);
@@ -1415,6 +1421,30 @@ inline void mark_plane_side(const std::array<double, 4>& row, const rtc_camera* 
         for (long tx = tx0; tx <= tx1; tx++) (*tiles)[(size_t)ty * tw + tx] = 1;
 }
 
+// ... and tile by tile, for the scene-tile mask: g is linear in (px, py), so over a tile's square it takes its least value at a
+// corner -- a tile none of whose four corners has g < 0 holds no pixel that can see the plane (the same g, the same 8 pixels of
+// margin, the same "everything" for a camera in the plane or values that are not finite).  A tile's square is taken from its
+// first pixel to its neighbour's, [16 tx, 16 tx + 16]: every pixel centre of the tile lies inside.
+inline void mark_plane_tiles(const std::array<double, 4>& row, const rtc_camera* cam, std::vector<uint8_t>* tiles, uint32_t tw, uint32_t th) {
+    const float* m = cam->inv;
+    const double y_o = row[0] * m[3] + row[1] * m[7] + row[2] * m[11] + row[3];
+    double col[3];
+    for (int k = 0; k < 3; k++) col[k] = row[0] * m[k] + row[1] * m[4 + k] + row[2] * m[8 + k];
+    const double sz = cam->pixel_size, a = -col[0] * sz, b = -col[1] * sz;
+    const double c0 = col[0] * (cam->half_width - 0.5 * sz) + col[1] * (cam->half_height - 0.5 * sz) - col[2];
+    if (!std::isfinite(y_o) || !std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c0) || y_o == 0.0) {
+        std::fill(tiles->begin(), tiles->end(), (uint8_t)1);
+        return;
+    }
+    const double sgn = y_o > 0.0 ? 1.0 : -1.0, margin = 8.0 * (std::fabs(a) + std::fabs(b));
+    auto g = [&](double px, double py) { return sgn * (a * px + b * py + c0) - margin; };
+    for (uint32_t ty = 0; ty < th; ty++)
+        for (uint32_t tx = 0; tx < tw; tx++) {
+            const double x0 = 16.0 * tx, y0 = 16.0 * ty;
+            if (g(x0, y0) < 0.0 || g(x0 + 16.0, y0) < 0.0 || g(x0, y0 + 16.0) < 0.0 || g(x0 + 16.0, y0 + 16.0) < 0.0) (*tiles)[(size_t)ty * tw + tx] = 1;
+        }
+}
+
 // What rtc_ctx_set_scene keeps of a scene beside its records: which tiles of the frame matter, and which kernel renders it.
 struct ScenePlan {
     bool simple = false;  // every object scale+translate-only, no cylinder / cone / triangle, no patterns
@@ -1426,6 +1456,9 @@ struct ScenePlan {
     std::vector<uint8_t> scene_rect_tiles;      // the tiles scene_rect bounds: the region's box projected, the planes' visible sides
     std::vector<uint8_t> scene_tile_mask;       // the tiles some top-level entry projects to; empty: not known / not worth it
     uint32_t scene_tiles_w = 0u, scene_tiles_h = 0u;
+    // ... of a bounded world, under a third of the frame and under two thirds of the rectangle: a frame whose rows leave chunk by
+    // chunk (rtc_render_ex) is drawn from the list only then -- a list cannot report rows, and only there it gains more than that costs
+    bool scene_tiles_sparse = false;
     bool spec_shares = false, spec_blocks_y = false, spec_rect = false;  // the scene's kernel takes -DRTC_SPEC_SHARE / _BLOCKS_Y / _RECT = 1
     int tree_waves = 0;    // waves per SIMD of the scene's tree kernel (0: the scene has no traversal stream)
     bool wf_pays = false;  // a tree world with long leaf runs whose materials both reflect and transmit
@@ -1482,18 +1515,28 @@ inline void plan_coverage(const Policy& P, const SceneHdr& hdr, const rtc_camera
     if (P.jit_print)
         std::fprintf(stderr, "librtc_amd: scene rectangle tiles [%u, %u) x [%u, %u) of %u x %u: %.3f of the frame\n", x0, x1, y0, y1, tw, th,
                      p->scene_rect_coverage);
-    // ... and entry by entry (ERROR_BUDGET.md B8 holds for each padded box as it does for their union): where the entries
-    // together cover under a third of the frame and under two thirds of their bounding rectangle, frames are drawn tile by tile
-    if (P.scene_tiles && region.planes.empty() && !region.entry_boxes.empty() && x0 < x1 && y0 < y1) {
+    // ... and tile by tile: the tiles some entry's padded box projects to (ERROR_BUDGET.md B8 holds for each padded box as it does
+    // for their union) and those that can see a top-level plane (mark_plane_tiles).  Frames are drawn from the list of those tiles, and
+    // the rest is zero-filled, where that was measured to pay: a bounded world whose entries cover under a third of the frame and
+    // under two thirds of their rectangle (C5), a world with planes a fifth of whose tiles or more are in neither (C3's sky).
+    if (P.scene_tiles != 0 && (!region.entry_boxes.empty() || !region.planes.empty()) && x0 < x1 && y0 < y1) {
         std::vector<uint8_t> each;
-        uint32_t ew = 0, eh = 0;
-        project_heavy_boxes(P, region.entry_boxes, camera, &each, &ew, &eh);
-        const size_t n_each = count_tiles(each);
-        if (ew == tw && eh == th && n_each > 0 && 3u * n_each < (size_t)tw * th && 3u * n_each < 2u * (size_t)(x1 - x0) * (y1 - y0)) {
-            p->scene_tile_mask = each;
-            p->scene_tiles_w = tw, p->scene_tiles_h = th;
+        uint32_t ew = tw, eh = th;
+        if (!region.entry_boxes.empty()) project_heavy_boxes(P, region.entry_boxes, camera, &each, &ew, &eh);
+        else each.assign((size_t)tw * th, 0);
+        if (ew == tw && eh == th && each.size() == (size_t)tw * th) {
+            for (uint8_t& b : each) b = b ? 1 : 0;
+            for (const auto& pl : region.planes) mark_plane_tiles(pl, camera, &each, tw, th);
+            const size_t n_each = count_tiles(each), n_all = (size_t)tw * th, unseen = n_all - n_each;
+            const bool sparse = region.planes.empty() && 3u * n_each < n_all && 3u * n_each < 2u * (size_t)(x1 - x0) * (y1 - y0);
+            const bool wanted = P.scene_tiles == 2 || (region.planes.empty() ? sparse : 100u * unseen >= (size_t)SCENE_TILES_UNSEEN_PCT * n_all);
+            if (n_each > 0 && unseen > 0 && wanted) {
+                p->scene_tile_mask = each;
+                p->scene_tiles_w = tw, p->scene_tiles_h = th;
+                p->scene_tiles_sparse = sparse;
+            }
+            if (P.jit_print) std::fprintf(stderr, "librtc_amd: scene tiles: %zu of %u x %u%s\n", n_each, tw, th, p->scene_tile_mask.empty() ? " (not used)" : "");
         }
-        if (P.jit_print) std::fprintf(stderr, "librtc_amd: scene tiles: %zu of %u x %u%s\n", n_each, tw, th, p->scene_tile_mask.empty() ? " (not used)" : "");
     }
     p->scene_rect_tiles.swap(covered);
 }
