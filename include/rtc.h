@@ -81,6 +81,12 @@ enum { RTC_JITTER_CONSTANT = 0, RTC_JITTER_HASHED = 2,
         * rectangle_light.rs:76-88's order) and rtc_point_on_light; rtc_render / rtc_ctx_set_scene / rtc_color_at refuse. */
        RTC_JITTER_SEQUENCE = 3 };
 #define RTC_JITTER_SEQUENCE_MAX 16
+/* The most cells, u_steps x v_steps, a rectangle light may have: 2^24.  rectangle_light.rs:76-88 adds 1.0 per lit sample in
+ * f32, and an f32 sum of ones stops growing at 2^24: with more cells the reference answers a fully lit point with
+ * 2^24 / cells, not 1.0, and none of the library's ways to answer samples without tracing them reproduces that.
+ * rtc_rectangle_light, rtc_scene_validate and every call that takes a scene refuse such a light with RTC_ERR_UNSUPPORTED
+ * (the product is formed in 64 bits: 65 536 x 65 536 is refused, not wrapped). */
+#define RTC_LIGHT_CELLS_MAX 16777216
 
 /* A boxed Pattern (pattern/pattern.rs:8-26) flattened: the two colours every pattern is built from and
  * BasePattern.t_inverse (pattern.rs:33,52-54).  Gradient and Sine2D keep `distance = b - a`

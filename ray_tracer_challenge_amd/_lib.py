@@ -21,6 +21,8 @@ RTC_UV_CHECKERS, RTC_UV_ALIGN_CHECK, RTC_UV_IMAGE = 1, 2, 3
 RTC_MAP_SPHERICAL, RTC_MAP_PLANAR, RTC_MAP_CYLINDRICAL = 1, 2, 3
 RTC_LIGHT_POINT, RTC_LIGHT_RECT = 0, 1
 RTC_JITTER_CONSTANT, RTC_JITTER_HASHED, RTC_JITTER_SEQUENCE = 0, 2, 3
+RTC_JITTER_SEQUENCE_MAX = 16
+RTC_LIGHT_CELLS_MAX = 1 << 24  # u_steps x v_steps of a rectangle light: more is refused with RTC_ERR_UNSUPPORTED
 RTC_MAX_DEPTH = 255        # accepted by rtc_render / rtc_ctx_render (above RTC_STACK_DEPTH_BASE: a scene kernel with a longer stack)
 RTC_STACK_DEPTH_BASE = 8   # ... and by rtc_color_at
 
@@ -251,7 +253,9 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
          "rtc_diag_longest_first_pays": (C.c_int32, [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]),
          "rtc_diag_scene_tile_mask": (C.c_uint32, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]),
          "rtc_diag_ctx_scene_tiles": (None, [C.c_void_p, C.POINTER(rtc_partition), C.POINTER(C.c_uint32)]),
-         "rtc_diag_seam_ctx": (C.c_void_p, [C.c_uint32])}
+         "rtc_diag_seam_ctx": (C.c_void_p, [C.c_uint32]),
+         # the packed work counter's capacity: does a launch count a light's culled shadow rays, or run with the culls off (tests/test_light_grid_limits.py)
+         "rtc_diag_culled_count_fits": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32])}
 
 _lib = None
 _loaded = {}  # path -> CDLL

@@ -1095,6 +1095,26 @@ static rtc_status deep_kernel(rtc_ctx* c, int32_t depth, const std::vector<std::
     return RTC_OK;
 }
 
+// The scene's header as a launch of up to RTC_STACK_DEPTH_BASE levels takes it: where the packed counter of such a kernel cannot hold
+// the culled shadow rays one lane may answer (rtc_launch_plan.h culled_count_fits), the whole-light cull and the block cones are off
+// in the launch's copy -- the only two places that count one (Counters::add_culled).  `rays_per_lane`: the rays a lane traces into one
+// counter; 0: unknown (the level-by-level renderer's lanes draw rays from a queue), every shade point the word can count.
+// (Lights of up to 256 cells, the usual ones, fit whatever the launch is and are not looked at further.)
+static SceneHdr launch_hdr(const rtc_ctx* c, int32_t depth, uint32_t rays_per_lane) {
+    SceneHdr h = c->hdr;
+    const int64_t cells = (int64_t)h.u_steps * (int64_t)h.v_steps;
+    if (h.light_kind != RTC_LIGHT_RECT || depth > RTC_STACK_DEPTH_BASE || cells * (int64_t)SHADED_COUNT_MAX <= (int64_t)CULLED_COUNT_MAX) return h;
+    bool any_refl = rays_per_lane == 0u, any_refr = rays_per_lane == 0u;
+    const uint32_t stride = padded_count(h.n_objects);
+    for (uint32_t i = 0; i < h.n_objects && !(any_refl && any_refr); i++) {  // (as scene_recurses; NaN: recurses)
+        any_refl = any_refl || !(c->soa_host[soa_index(COL_MAT_B, stride, i)].w == 0.0f);
+        any_refr = any_refr || !(c->soa_host[soa_index(COL_MAT_C, stride, i)].x == 0.0f);
+    }
+    if (!culled_count_fits(cells, depth, any_refl, any_refr, rays_per_lane == 0u ? (uint32_t)SHADED_COUNT_MAX : rays_per_lane))
+        h.cull_flags &= ~(CULL_ENABLED | CULL_CELLS);
+    return h;
+}
+
 // The frame level by level (rtc_wavefront.h): one lane per ray, suspended shade_hits as nodes in HBM.  *used: false when the
 // frame was not rendered this way (pools could not be allocated, or ran full: the caller renders it with the per-pixel kernel).
 static rtc_status render_wavefront(rtc_ctx* c, int32_t depth, const Partition& q, uint32_t rows, void* d_out, bool out_u8, hipStream_t stream,
@@ -1129,7 +1149,7 @@ static rtc_status render_wavefront(rtc_ctx* c, int32_t depth, const Partition& q
         c->wf_cap_rays = cap_rays, c->wf_cap_nodes = cap_nodes;
     }
     WfArgs a;
-    a.hdr = c->hdr;
+    a.hdr = launch_hdr(c, depth, 0u);
     a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
     a.out = out_u8 ? nullptr : (float*)d_out;
     a.out_u8 = out_u8 ? (uint8_t*)d_out : nullptr;
@@ -1430,7 +1450,7 @@ static rtc_status fork_tile_fill(rtc_ctx* c, const rtc_ctx::SceneTileList& tl, v
 static RenderArgs render_args(const rtc_ctx* c, const Partition& q, uint32_t rows, int32_t depth, uint32_t share_log2, void* d_out_rgb, bool out_u8,
                               unsigned long long* total, const ProgressPlan* progress, const LaunchPlan& lp, const LaunchLists& L) {
     RenderArgs a;
-    a.hdr = c->hdr;
+    a.hdr = launch_hdr(c, depth, lp.blocks_y);
     a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
     a.out = out_u8 ? nullptr : (float*)d_out_rgb;
     a.out_u8 = out_u8 ? (uint8_t*)d_out_rgb : nullptr;
@@ -1718,6 +1738,11 @@ uint64_t rtc_diag_rect_launch(uint32_t width, uint32_t height, const rtc_partiti
     std::memcpy(out, v, sizeof(v));
     return lp.extra_rays;
 }
+// The packed counter's capacity (tests/test_light_grid_limits.py): does a launch of `depth` levels whose lanes trace `rays_per_lane` rays
+// each count the culled shadow rays of a light of u_steps x v_steps cells exactly (1), or does it run with the culls off (0)?
+int32_t rtc_diag_culled_count_fits(int32_t u_steps, int32_t v_steps, int32_t depth, int32_t any_refl, int32_t any_refr, uint32_t rays_per_lane) {
+    return culled_count_fits((int64_t)u_steps * (int64_t)v_steps, depth, any_refl != 0, any_refr != 0, rays_per_lane) ? 1 : 0;
+}
 
 // The lanes per pixel (log2) the context's last rtc_ctx_render was planned with -- a block list's entries may differ per tile, under
 // the same cap (tests/test_gpu_supersample.py: the cap in effect under a pinned RTC_AMD_SHARE_LOG2).
@@ -1895,7 +1920,7 @@ static rtc_status trace_launch(rtc_ctx* c, int32_t depth, const void* d_origins,
     HIP_TRY(grow(&t.d_counts, &t.counts_cap, n_counts));
     if (!t.d_total) HIP_TRY(hipMalloc((void**)&t.d_total, 3 * sizeof(unsigned long long)));
     TraceArgs a;
-    a.hdr = c->hdr;
+    a.hdr = launch_hdr(c, depth, 1u);
     a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
     a.origins = (const float4*)d_origins, a.directions = (const float4*)d_directions, a.keys = (const uint32_t*)d_keys;
     a.out = (float*)d_out_rgb;
@@ -2286,7 +2311,7 @@ rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float 
     const void* const kernel_key = fn ? (const void*)fn : aot_family(c).key(k);
     const uint32_t n_workgroups = adaptive_grid((uint32_t)compute_units(c), (uint32_t)adaptive_wgs_per_cu(c, fn, k, kernel_key), width, height, k);
     AdaptiveRefineArgs a;
-    a.hdr = c->hdr;
+    a.hdr = launch_hdr(c, refine_depth, 1u);  // (a step's counters are unpacked before the next: one ray per lane and counter)
     a.hdr.width = fine.width, a.hdr.height = fine.height, a.hdr.pixel_size = fine.pixel_size;  // (half extents and transform: the same, checked)
     a.hdr.has_scene_box = 0u;  // (rtc_adaptive.h)
     a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);

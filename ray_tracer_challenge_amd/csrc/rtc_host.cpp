@@ -511,6 +511,9 @@ rtc_status rtc_rectangle_light(const float intensity[3], const float corner[4], 
                                uint32_t jitter_seed, rtc_light* out) {
     if (!out || !intensity || !corner || !u_vec || !v_vec) return fail(RTC_ERR_INVALID_ARG, "rtc_rectangle_light: null argument");
     if (u_steps <= 0 || v_steps <= 0) return fail(RTC_ERR_INVALID_ARG, "rtc_rectangle_light: steps must be positive");
+    if ((int64_t)u_steps * (int64_t)v_steps > (int64_t)RTC_LIGHT_CELLS_MAX)
+        return fail(RTC_ERR_UNSUPPORTED, "rtc_rectangle_light: %d x %d steps are more than RTC_LIGHT_CELLS_MAX = %d cells (2^24)", u_steps, v_steps,
+                    RTC_LIGHT_CELLS_MAX);
     if (jitter_mode != RTC_JITTER_CONSTANT && jitter_mode != RTC_JITTER_HASHED && jitter_mode != RTC_JITTER_SEQUENCE)
         return fail(RTC_ERR_UNSUPPORTED, "rtc_rectangle_light: jitter mode %d cannot run on the device", jitter_mode);
     std::memset(out, 0, sizeof(*out));

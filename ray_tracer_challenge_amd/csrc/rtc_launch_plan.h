@@ -275,6 +275,34 @@ inline void order_tile_list(const std::vector<uint32_t>& list, const uint32_t* t
     refine_block_list(list, ticks, width, rows, 1.0, INFINITY, 0.0, out);
 }
 
+// The packed work counter's capacity (rtc_kernel_core.h Counters).  A kernel of up to RTC_STACK_DEPTH_BASE levels counts, per lane,
+// its shade points in bits 0..11 of one word and the shadow rays it answered without a test in bits 12..31: 2^20 - 1 of them at the
+// most, one more carries out of the word and the frame's culled_shadow_rays loses 2^20.  A lane adds at most the light's cell
+// count per shade point, so the count is exact while cells x (shade points a lane can make in the launch) <= 2^20 - 1.  A launch
+// for which that does not hold runs with the whole-light cull and the block cones switched off in its copy of the scene's
+// header (rtc_device.hip launch_hdr): every sample is traced, the image is the same (each switch has its on / off tests) and
+// culled_shadow_rays is honestly 0.  Kernels with a longer stack count in a word of their own and are never limited.
+// (This rule is what holds.  The comment at Counters still speaks of "<= 255 shade points, <= 255 x 128 cells", which nothing ever
+// enforced and which is wrong twice -- depth 8 shades up to 511 points a ray, 8 blocks per workgroup make that 4 088 a lane.  It
+// is left as it is for now: the compiled kernel depends on the TEXT of rtc_kernel_core.h, comments included, so touching it would
+// change every scene kernel's id for no change in code.  LABNOTES.md "Light grids".)
+constexpr uint64_t CULLED_COUNT_MAX = (1ull << 20) - 1ull;
+constexpr uint64_t SHADED_COUNT_MAX = (1ull << 12) - 1ull;  // what bits 0..11 hold: no launch lets a lane make more shade points
+// The shade points of one ray traced at `depth` (world.rs:121-162: a child is traced while remaining >= 1, so levels depth, depth - 1,
+// ... 0 shade): one where no material reflects or transmits, a chain where only one of the two occurs in the scene, a full binary tree
+// otherwise.
+inline uint64_t shade_points_per_ray(int32_t depth, bool any_refl, bool any_refr) {
+    const uint32_t levels = (uint32_t)std::min(std::max(depth, 0), RTC_STACK_DEPTH_BASE) + 1u;
+    if (!any_refl && !any_refr) return 1ull;
+    if (any_refl != any_refr) return levels;
+    return (1ull << levels) - 1ull;
+}
+// `rays_per_lane`: how many rays a lane of the launch traces into one counter (blocks per workgroup; 1 for ray streams)
+inline bool culled_count_fits(int64_t cells, int32_t depth, bool any_refl, bool any_refr, uint32_t rays_per_lane) {
+    const uint64_t points = std::min(SHADED_COUNT_MAX, shade_points_per_ray(depth, any_refl, any_refr) * std::max(1u, rays_per_lane));
+    return cells >= 0 && (uint64_t)cells <= CULLED_COUNT_MAX / points;
+}
+
 // What RenderArgs and the launch need to know of a frame's geometry.  `shape` says which of the mutually exclusive ways
 // of launching was chosen; the regular grid alone can be swizzled, re-ordered by the grid feedback or cut into progress
 // chunks, and only while it is the plain one (plain_grid()).

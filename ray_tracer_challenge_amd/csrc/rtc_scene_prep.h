@@ -1156,6 +1156,10 @@ struct Flatten {
             RTC_TRY(check_tuple(l.u_vec, 0.0f, "light.u_vec"));
             RTC_TRY(check_tuple(l.v_vec, 0.0f, "light.v_vec"));
             if (l.u_steps <= 0 || l.v_steps <= 0) return fail(RTC_ERR_INVALID_ARG, "light steps must be positive");
+            // (include/rtc.h RTC_LIGHT_CELLS_MAX: above 2^24 cells the reference's own f32 sum of ones saturates; in 64 bits, an int product wraps from 46 341^2)
+            const int64_t cells = (int64_t)l.u_steps * (int64_t)l.v_steps;
+            if (cells > (int64_t)RTC_LIGHT_CELLS_MAX)
+                return fail(RTC_ERR_UNSUPPORTED, "light of %d x %d steps: more than RTC_LIGHT_CELLS_MAX = %d cells (2^24)", l.u_steps, l.v_steps, RTC_LIGHT_CELLS_MAX);
             if (l.jitter_mode != RTC_JITTER_CONSTANT && l.jitter_mode != RTC_JITTER_HASHED && l.jitter_mode != RTC_JITTER_SEQUENCE)
                 return fail(RTC_ERR_UNSUPPORTED, "jitter mode %d cannot run on the device (closures are host-only)", l.jitter_mode);
             if (l.jitter_mode == RTC_JITTER_SEQUENCE) {
