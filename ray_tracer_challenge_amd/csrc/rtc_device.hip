@@ -136,17 +136,29 @@ struct rtc_ctx {
     uint32_t* d_ppm_bits = nullptr;
     size_t ppm_rows_cap = 0, ppm_bits_cap = 0;
     int n_cus = 0;                    // compute_units()
-    bool spec_shares = false;         // spec_fn was compiled with -DRTC_SPEC_SHARE=1
+    bool spec_shares = false;         // render.fn was compiled with -DRTC_SPEC_SHARE=1
     bool spec_blocks_y = false;       // ... with -DRTC_SPEC_BLOCKS_Y=1 (several blocks per workgroup)
     bool spec_rect = false;           // ... with -DRTC_SPEC_RECT=1 (scene rectangle launches: block offsets, zero-filling workgroups)
-    hipFunction_t spec_fn = nullptr;  // scene-specialised kernel (hiprtc), or null: ahead-of-time kernels
-    // Recursion deeper than RTC_AOT_MAX_DEPTH (ctx_render_slot): the scene's kernel compiled once more with a longer frame
-    // stack (-DRTC_SPEC_MAX_DEPTH=16 / 32 / ...), on first use; spec_defs: the options of this scene's kernel (empty when
-    // the policy left the scene to the ahead-of-time kernels -- deep_defs() then writes the options from scratch)
-    std::vector<std::string> spec_defs;
-    std::string spec_name;
-    typedef std::map<int, std::pair<hipFunction_t, std::string>> DeepKernels;  // by stack depth: the kernel and its id
-    DeepKernels deep_fn;
+    // One kernel of the resident scene as the context keeps it -- the frame's, the ray streams', the refinement's of one factor:
+    // what rtc_scene_prep.h planned for it, the scene-compiled kernel (scene_kernel_for) and, for recursion deeper than
+    // RTC_STACK_DEPTH_BASE, the same kernel compiled once more with a longer frame stack on first use (deep_kernel).
+    struct SceneKernel {
+        KernelVariant variant;        // options (written down whatever the policy says: deep_kernel may need them) and the two names
+        hipFunction_t fn = nullptr;   // scene-specialised kernel (hiprtc), or null: the ahead-of-time family
+        std::string fn_id;
+        std::map<int, std::pair<hipFunction_t, std::string>> deep;  // by stack depth: the kernel and its id
+        bool failed = false;          // hiprtc did not deliver fn: the ahead-of-time family from then on (note says why)
+        std::string note;
+        // (kernel, stream) pairs launched once (warm_up).  One set per slot: KernelFamily::key() is one value for the render and the
+        // ray-stream kernel of a family.  It outlives the scene.
+        std::set<std::pair<const void*, const void*>> warmed;
+        void reset(const KernelVariant& v) {  // another scene
+            variant = v;
+            fn = nullptr, failed = false;
+            fn_id.clear(), note.clear(), deep.clear();
+        }
+    };
+    SceneKernel render;               // compiled by rtc_ctx_set_scene (or deferred: lazy_jit); note: rtc_ctx_jit_status
     std::string kernel_name;          // what rtc_ctx_render launches, for rtc_ctx_kernel_name()
     // Block list of the current scene (RenderArgs::tiles): which 16 x 16 pixel tiles of the image a mesh projects to
     // (row-major bitmap, empty: no block list), and the list last built -- for the partition it was built for
@@ -185,10 +197,8 @@ struct rtc_ctx {
     std::map<std::array<uint32_t, 3>, SceneTileList> scene_tile_lists;  // per partition {band_rows, n_parts, part}
     float scene_rect_coverage = 1.0f;           // ... and its share of the frame
     std::string kernel_id;            // rtc_ctx_kernel_id(): names the code object (source + options + compiler), not the scene
-    std::string jit_note;             // why spec_fn is null although the policy wanted one (rtc_ctx_jit_status)
     // the scene as last uploaded: an identical one (rtc_render_ex called again for the next frame) is not uploaded twice
     std::vector<float4> soa_host;
-    std::set<std::pair<const void*, const void*>> warmed;  // (kernel, stream) pairs that have been launched once (ctx_render_slot)
     std::vector<float> texels_host;
     uint4* d_block_counts = nullptr;
     size_t block_cap = 0;
@@ -217,34 +227,22 @@ struct rtc_ctx {
     // Ray streams (rtc_ctx_trace; rtc_trace.h).  Everything a trace needs it has of its own -- kernel, names, counters, events,
     // warm-up bookkeeping -- so that the frame schedule and what rtc_ctx_render reports never see it.
     struct Trace {
-        std::vector<std::string> defs;    // the scene's kernel options as a ray stream takes them (-DRTC_SPEC_TRACE=1); empty: a world without objects
-        std::string family_name, spec_name;  // "trace_kernel<...>", "trace_kernel_spec[...]"
+        SceneKernel kernel;               // trace_variant's, compiled by the first trace that asks for it
         bool compile_any_size = false, compile_never = false;  // ScenePlan's: what wants_scene_kernel takes beside the number of rays
-        hipFunction_t fn = nullptr;       // the scene's ray-stream kernel, compiled by the first trace that asks for it
-        std::string fn_id;
-        bool failed = false;              // ... or hiprtc did not deliver it: the ahead-of-time kernel from then on (note says why)
-        std::string note;
-        DeepKernels deep;                 // as rtc_ctx::deep_fn
         std::string name, id;             // of the last trace's kernel ("" before the first trace of the current scene)
         uint4* d_counts = nullptr;        // one partial per wave
         size_t counts_cap = 0;
         unsigned long long* d_total = nullptr;  // {rays, shaded hits, culled shadow rays} of the last trace
         std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // around the trace kernels since the last rtc_ctx_stats that reported a trace
         size_t events_used = 0;
-        std::set<std::pair<const void*, const void*>> warmed;  // (kernel, stream) pairs launched once
         uint64_t last_n = 0;
         bool last = false;                // the context's last launch was a trace: rtc_ctx_stats reports it
     } trace;
     // Adaptive supersampling (rtc_ctx_render_adaptive; rtc_adaptive.h).  The base frame is the context's normal render; the mask
     // and the refinement have everything of their own, as a trace has, so that the frame schedule and rtc_ctx_stats never see them.
     struct Adaptive {
-        struct PerK {                     // k = 2, 4
-            std::vector<std::string> defs;   // the ray stream's options with -DRTC_SPEC_ADAPTIVE=k in the place of -DRTC_SPEC_TRACE=1
-            hipFunction_t fn = nullptr;      // the scene's refinement kernel, compiled by the first call that asks for it
-            std::string fn_id;
-            DeepKernels deep;
-        } per_k[2];
-        bool failed = false;              // hiprtc did not deliver: the ahead-of-time kernel from then on (note says why)
+        SceneKernel kernel[2];            // refine_variant's of k = 2, 4, compiled by the first call that asks for it
+        bool failed = false;              // hiprtc did not deliver one of them: the ahead-of-time kernels from then on, for both (note says why)
         std::string note;
         std::string name, id;             // of the last call's refinement kernel ("" before the first of the current scene)
         uint32_t* d_list = nullptr;       // flagged pixel indices: width * height words, allocated by the first call
@@ -252,7 +250,6 @@ struct rtc_ctx {
         AdaptiveQueue* d_queue = nullptr; // the list's length and the last refinement's {rays, shaded hits, culled shadow rays}
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // before the mask kernel, between the two, after the refinement
         bool ran = false;                 // the events have been recorded
-        std::set<std::pair<const void*, const void*>> warmed;  // (kernel, stream) pairs launched once
         std::map<const void*, int> wgs_per_cu;  // occupancy of a refinement kernel, asked once
     } adaptive;
     // Ray reordering (rtc_ctx_ray_order, rtc_ctx_trace_reordered; rtc_reorder.h).  The sort's and the gather's buffers, events of
@@ -619,6 +616,17 @@ static void dispatch_family(KernelFamily k, F&& f) {
     else if (k.nobj == 8) f(std::integral_constant<int, 8>(), std::false_type());
     else f(std::integral_constant<int, 0>(), std::false_type());
 }
+// One launch of a slot's kernel (rtc_ctx::SceneKernel): `fn`, the scene-compiled one, takes `args` as its one parameter; null: `aot`
+// dispatches to the ahead-of-time family.
+template <class Args, class Aot>
+static hipError_t launch_scene_kernel(hipFunction_t fn, dim3 grid, hipStream_t stream, Args& args, Aot&& aot) {
+    if (fn) {
+        void* params[] = {&args};
+        return hipModuleLaunchKernel(fn, grid.x, grid.y, 1, 256, 1, 1, 0, stream, params, nullptr);
+    }
+    aot();
+    return hipGetLastError();
+}
 
 extern "C" {
 
@@ -858,47 +866,92 @@ static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hi
         SsRenderArgs sa;
         sa.fine = a;
         sa.out_width = a.hdr.width / c->ss_k, sa.out_rows = a.rows / c->ss_k;
-        if (spec_fn) {
-            void* params[] = {&sa};
-            return hipModuleLaunchKernel(spec_fn, grid.x, grid.y, 1, 256, 1, 1, 0, stream, params, nullptr);
-        }
-        dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
-            if (c->ss_k == 2u) hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
-            else hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, sa);
+        return launch_scene_kernel(spec_fn, grid, stream, sa, [&] {
+            dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+                if (c->ss_k == 2u) hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
+                else hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, sa);
+            });
         });
-        return hipGetLastError();
     }
-    if (spec_fn) {
-        void* params[] = {&a};
-        return hipModuleLaunchKernel(spec_fn, grid.x, grid.y, 1, 256, 1, 1, 0, stream, params, nullptr);
-    }
-    dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
-        hipLaunchKernelGGL((render_kernel<decltype(nobj)::value, decltype(simple)::value>), grid, dim3(256), 0, stream, a);
+    return launch_scene_kernel(spec_fn, grid, stream, a, [&] {
+        dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+            hipLaunchKernelGGL((render_kernel<decltype(nobj)::value, decltype(simple)::value>), grid, dim3(256), 0, stream, a);
+        });
     });
-    return hipGetLastError();
 }
 
-// The policy wanted a scene-compiled kernel and hiprtc did not deliver one.  RTC_AMD_SPECIALIZE=1: an error.  Default
-// policy: the ahead-of-time kernel renders the same image -- several times slower on area-light scenes -- so say so:
-// rtc_ctx_jit_status(), rtc_stats.flags, one line on stderr per process.
+// A slot's kernel with a frame stack of at least `depth` levels.  The options are the slot's own (rtc_ctx_set_scene wrote them
+// down) plus -DRTC_SPEC_MAX_DEPTH; the recursion frames of such a kernel all live in per-lane scratch -- the LDS placement of the
+// first levels (a tuning of the depth-5 glass-and-mirror frame) is not carried over.  Always a scene-compiled kernel, whatever
+// RTC_AMD_SPECIALIZE says: the ahead-of-time kernels stop at RTC_STACK_DEPTH_BASE.
+static rtc_status deep_kernel(rtc_ctx* c, int32_t depth, rtc_ctx::SceneKernel& s, hipFunction_t* out, std::string* out_id = nullptr) {
+    int cap = 2 * RTC_STACK_DEPTH_BASE;
+    while (cap < depth) cap *= 2;
+    if (cap > RTC_MAX_DEPTH) cap = RTC_MAX_DEPTH;
+    auto it = s.deep.find(cap);
+    if (it == s.deep.end()) {
+        if (s.variant.defs.empty()) return fail(RTC_ERR_INVALID_ARG, "depth %d: no kernel options recorded for this scene", depth);
+        std::vector<std::string> defs;
+        for (const auto& d : s.variant.defs)
+            if (d.rfind("-DRTC_SPEC_LDS_FRAMES=", 0) != 0) defs.push_back(d);
+        defs.push_back("-DRTC_SPEC_MAX_DEPTH=" + std::to_string(cap));
+        hipFunction_t fn = nullptr;
+        std::string id;
+        rtc_status st = jit_get(c->policy, c->device, defs, &fn, &id);
+        if (st != RTC_OK) return st;  // (the message is hiprtc's)
+        it = s.deep.emplace(cap, std::make_pair(fn, id)).first;
+    }
+    *out = it->second.first;
+    if (out_id) *out_id = it->second.second;
+    return RTC_OK;
+}
+// The kernel to launch for a slot at this depth, or null: the ahead-of-time family.  `want`: the specialisation policy asks for the
+// scene's own kernel, which is compiled on first use (`lazy`: as jit_get's); deeper than the ahead-of-time stack it is always a
+// scene kernel (deep_kernel).  When the policy wanted the scene's kernel and hiprtc did not deliver it, `failed` and `note`
+// remember that (the slot's own; the two refinement slots share theirs).  RTC_AMD_SPECIALIZE=1: an error.  Default policy: the
+// ahead-of-time kernel computes the same image -- several times slower on area-light scenes -- so say so: the note
+// (rtc_ctx_jit_status(), rtc_stats.flags) and one line on stderr per process and `doing` ("rendering with", "tracing with",
+// "refining with"; `named`: ... and the family's name).
+static rtc_status scene_kernel_for(rtc_ctx* c, rtc_ctx::SceneKernel& s, int32_t depth, bool want, bool lazy, bool& failed, std::string& note,
+                                   const char* doing, bool named, hipFunction_t* fn, std::string* id) {
+    *fn = nullptr;
+    if (depth > RTC_STACK_DEPTH_BASE) return deep_kernel(c, depth, s, fn, id);
+    if (!want || failed) return RTC_OK;
+    if (s.fn == nullptr) {
+        const rtc_status jst = jit_get(c->policy, c->device, s.variant.defs, &s.fn, &s.fn_id, lazy);
+        if (jst != RTC_OK) {
+            s.fn = nullptr;
+            failed = true;
+            note = rtc_last_error();
+            if (c->policy.specialise == 1) return jst;
+            static std::set<std::string> warned;
+            if (!c->policy.quiet && warned.insert(doing).second)
+                std::fprintf(stderr, "librtc_amd: scene specialisation unavailable, %s the slower ahead-of-time kernel%s%s: %.300s\n", doing,
+                             named ? " " : "", named ? s.variant.family_name.c_str() : "", note.c_str());
+            return RTC_OK;
+        }
+    }
+    *fn = s.fn, *id = s.fn_id;
+    return RTC_OK;
+}
+
+// The frame's kernel: compiled when the scene is set (or, lazy, when it comes again: compile_deferred), not by the first frame.
+// RTC_AMD_SPECIALIZE=1 and no kernel: the context has no scene.
 static std::string ctx_aot_id(const rtc_ctx* c) { return c->ss_k != 1u ? aot_ss_kernel_id(c->ss_k) : aot_kernel_id(); }
-static rtc_status jit_failed(rtc_ctx* c, int policy, rtc_status jst) {
-    c->spec_fn = nullptr;
-    c->spec_shares = false;
-    c->kernel_id = ctx_aot_id(c);
-    c->jit_note = rtc_last_error();
-    if (policy == 1) {
+static rtc_status compile_render_kernel(rtc_ctx* c, bool lazy) {
+    rtc_ctx::SceneKernel& r = c->render;
+    hipFunction_t fn = nullptr;
+    std::string id;
+    const rtc_status jst = scene_kernel_for(c, r, 0, true, lazy, r.failed, r.note, "rendering with", true, &fn, &id);
+    c->kernel_name = fn ? r.variant.spec_name : r.variant.family_name;
+    c->kernel_id = fn ? id : ctx_aot_id(c);
+    c->jit_deferred = !fn && !r.failed;  // (lazy: this frame by the ahead-of-time kernel)
+    if (r.failed) c->spec_shares = false;
+    if (jst != RTC_OK) {
         c->has_scene = false;
         c->soa_host.clear();
-        return jst;
     }
-    static bool warned = false;
-    if (!warned && !c->policy.quiet) {
-        warned = true;
-        std::fprintf(stderr, "librtc_amd: scene specialisation unavailable, rendering with the slower ahead-of-time kernel %s: %.300s\n",
-                     c->kernel_name.c_str(), c->jit_note.c_str());
-    }
-    return RTC_OK;
+    return jst;
 }
 
 // are these the records (and texels) that are resident on the device?
@@ -911,14 +964,11 @@ static bool same_records(const rtc_ctx* c, const std::vector<float4>& soa, const
 static rtc_status compile_deferred(rtc_ctx* c) {
     c->jit_deferred = false;
     HIP_TRY(hipDeviceSynchronize());  // (nothing of this context may be in flight while its kernel and lists change)
-    hipFunction_t fn = nullptr;
-    std::string id;
-    const rtc_status jst = jit_get(c->policy, c->device, c->spec_defs, &fn, &id);
-    if (jst != RTC_OK) return jit_failed(c, c->policy.specialise, jst);
-    c->spec_fn = fn, c->kernel_id = id, c->kernel_name = c->spec_name;
+    RTC_TRY(compile_render_kernel(c, false));
+    if (!c->render.fn) return RTC_OK;
     drop_block_lists(c);  // (lists of the ahead-of-time launches: the scene's kernel takes other ones)
     drop_scene_tile_lists(c);
-    c->deep_fn.clear();
+    c->render.deep.clear();
     return RTC_OK;
 }
 
@@ -950,8 +1000,8 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     // capacity beside a null pointer, nor a render path that believes the old scene is still there
     // (only the camera has moved -- an animation's usual frame: the records and texels that are resident stay)
     c->has_scene = false;
-    c->spec_fn = nullptr;
-    c->jit_note.clear();
+    c->render.fn = nullptr;
+    c->render.note.clear();
     if (!resident) {
         c->soa_host.clear();
         c->texels_host.clear();
@@ -963,6 +1013,11 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
         HIP_TRY(hipMemcpy(c->d_soa, soa.data(), soa.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
     ScenePlan plan = plan_scene(P, hdr, soa, scene, camera, heavy_boxes, region);  // which kernel will render this scene
+    // Ray streams (rtc_ctx_trace) and the refinement of an adaptive frame: kernels of their own, none compiled yet -- the first call
+    // that wants the scene's kernel compiles it
+    c->trace.kernel.reset(trace_variant(plan));
+    for (uint32_t i = 0; i < 2u; i++) c->adaptive.kernel[i].reset(refine_variant(plan, i ? 4u : 2u));
+    if (k != 1u) plan_supersampled(&plan, k);
     c->hdr = hdr;
     c->camera = *camera;
     c->ss_k = k;
@@ -975,7 +1030,6 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     if (same_frame && P.block_feedback) restart_block_lists(c);
     else drop_block_lists(c);  // (nothing is in flight any more: the synchronisation above)
     drop_scene_tile_lists(c);
-    c->deep_fn.clear();
     c->simple = plan.simple;
     c->heavy_tiles.swap(plan.heavy_tiles), c->heavy_w = plan.heavy_w, c->heavy_h = plan.heavy_h;
     c->scene_box_coverage = plan.scene_box_coverage;
@@ -988,70 +1042,16 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     if (plan.tree_waves) c->tree_waves = plan.tree_waves;
     c->wf_pays = plan.wf_pays;
     c->wf_disabled = false;
+    c->trace.compile_any_size = plan.compile_any_size, c->trace.compile_never = plan.compile_never;
+    c->trace.last = false;
+    c->trace.name.clear(), c->trace.id.clear();
+    c->adaptive.failed = false;
+    c->adaptive.note.clear(), c->adaptive.name.clear(), c->adaptive.id.clear();
+    c->render.reset(render_variant(plan));
     c->kernel_name = plan.family_name;
-    c->spec_defs = plan.spec_defs;
-    c->spec_name = plan.spec_name;
-    {
-        // Ray streams (rtc_ctx_trace): the scene's options with the launch shapes a stream does not have switched off, names of
-        // its own, no kernel yet -- the first trace that wants the scene's kernel compiles it.  (The same for a plain and a
-        // supersampled context: color_at does not read the camera.)
-        rtc_ctx::Trace& t = c->trace;
-        t.defs.clear();
-        // (lane sharing among them: a stream runs one lane per ray, and its kernel must not depend on the size of a frame it does not draw)
-        for (const auto& d : plan.spec_defs)
-            t.defs.push_back((d == "-DRTC_SPEC_BLOCKS_Y=1" || d == "-DRTC_SPEC_RECT=1" || d == "-DRTC_SPEC_SHARE=1") ? d.substr(0, d.size() - 1) + "0" : d);
-        if (!t.defs.empty()) t.defs.push_back("-DRTC_SPEC_TRACE=1");
-        auto renamed = [](const std::string& name) { return name.rfind("render_", 0) == 0 ? "trace_" + name.substr(7) : name; };
-        t.family_name = renamed(plan.family_name), t.spec_name = renamed(plan.spec_name);
-        t.compile_any_size = plan.compile_any_size, t.compile_never = plan.compile_never;
-        t.fn = nullptr, t.failed = false, t.last = false;
-        t.fn_id.clear(), t.note.clear(), t.name.clear(), t.id.clear();
-        t.deep.clear();
-        // ... and the refinement of an adaptive frame: a ray stream's options, an entry of its own per factor
-        rtc_ctx::Adaptive& ad = c->adaptive;
-        for (uint32_t i = 0; i < 2u; i++) {
-            rtc_ctx::Adaptive::PerK& pk = ad.per_k[i];
-            pk.defs.clear();
-            for (const auto& d : t.defs) pk.defs.push_back(d == "-DRTC_SPEC_TRACE=1" ? std::string("-DRTC_SPEC_ADAPTIVE=") + (i ? "4" : "2") : d);
-            pk.fn = nullptr, pk.fn_id.clear(), pk.deep.clear();
-        }
-        ad.failed = false;
-        ad.note.clear(), ad.name.clear(), ad.id.clear();
-    }
-    if (k != 1u) {
-        // Scene tiles, the scene rectangle and several blocks per workgroup address the canvas by fine pixels and are not carried
-        // over: such scenes are a plain grid here, where the scene-box early-out still applies.
-        c->scene_tile_mask.clear();
-        c->scene_rect[0] = c->scene_rect[1] = c->scene_rect[2] = c->scene_rect[3] = 0u;
-        c->spec_blocks_y = c->spec_rect = false;
-        c->wf_pays = false;
-        const std::string tag = std::to_string(k);
-        auto rename = [&](std::string* name) {  // render_kernel<...> -> ss_render_kernel<...;ss=k>, render_kernel_spec[...] likewise
-            if (name->empty()) return;
-            name->insert(0, "ss_");
-            name->insert(name->size() - 1, ";ss=" + tag);
-        };
-        rename(&c->kernel_name), rename(&c->spec_name);
-        if (!c->spec_defs.empty()) {
-            // (the supersampling body has neither the loop over blocks nor the rectangle's offsets: their options are off in its key)
-            for (auto& d : c->spec_defs)
-                if (d == "-DRTC_SPEC_BLOCKS_Y=1" || d == "-DRTC_SPEC_RECT=1") d.back() = '0';
-            c->spec_defs.push_back("-DRTC_SPEC_SS=" + tag);
-        }
-    }
     c->kernel_id = ctx_aot_id(c);
     c->jit_deferred = false;
-    if (plan.compile_now && !c->spec_defs.empty()) {
-        rtc_status jst = jit_get(P, c->device, c->spec_defs, &c->spec_fn, &c->kernel_id, c->lazy_jit && P.specialise == 2);
-        if (jst != RTC_OK) {
-            if ((jst = jit_failed(c, P.specialise, jst)) != RTC_OK) return jst;
-        } else if (c->spec_fn != nullptr) {
-            c->kernel_name = c->spec_name;
-        } else {
-            c->kernel_id = ctx_aot_id(c);  // (lazy: this frame by the ahead-of-time kernel, whose name kernel_name already holds)
-            c->jit_deferred = true;
-        }
-    }
+    if (plan.compile_now && !plan.spec_defs.empty()) return compile_render_kernel(c, c->lazy_jit && P.specialise == 2);
     return RTC_OK;
 }
 
@@ -1066,34 +1066,6 @@ rtc_status rtc_ctx_set_scene_ss(rtc_ctx* c, const rtc_scene* scene, const rtc_ca
     return set_scene(c, scene, &fine, k);
 }
 }  // extern "C"
-
-// The scene's kernel with a frame stack of at least `depth` levels (ctx_render_slot).  The options are the scene's own
-// (rtc_ctx_set_scene wrote them down) plus -DRTC_SPEC_MAX_DEPTH; the recursion frames of such a kernel all live in per-lane
-// scratch -- the LDS placement of the first levels (a tuning of the depth-5 glass-and-mirror frame) is not carried over.
-// Always a scene-compiled kernel, whatever RTC_AMD_SPECIALIZE says: the ahead-of-time kernels stop at RTC_STACK_DEPTH_BASE.
-// (`scene_defs`, `kernels`: the render's -- rtc_ctx::spec_defs, deep_fn -- or the ray streams' -- Trace::defs, deep)
-static rtc_status deep_kernel(rtc_ctx* c, int32_t depth, const std::vector<std::string>& scene_defs, rtc_ctx::DeepKernels& kernels, hipFunction_t* out,
-                              std::string* out_id = nullptr) {
-    int cap = 2 * RTC_STACK_DEPTH_BASE;
-    while (cap < depth) cap *= 2;
-    if (cap > RTC_MAX_DEPTH) cap = RTC_MAX_DEPTH;
-    auto it = kernels.find(cap);
-    if (it == kernels.end()) {
-        if (scene_defs.empty()) return fail(RTC_ERR_INVALID_ARG, "depth %d: no kernel options recorded for this scene", depth);
-        std::vector<std::string> defs;
-        for (const auto& d : scene_defs)
-            if (d.rfind("-DRTC_SPEC_LDS_FRAMES=", 0) != 0) defs.push_back(d);
-        defs.push_back("-DRTC_SPEC_MAX_DEPTH=" + std::to_string(cap));
-        hipFunction_t fn = nullptr;
-        std::string id;
-        rtc_status st = jit_get(c->policy, c->device, defs, &fn, &id);
-        if (st != RTC_OK) return st;  // (the message is hiprtc's)
-        it = kernels.emplace(cap, std::make_pair(fn, id)).first;
-    }
-    *out = it->second.first;
-    if (out_id) *out_id = it->second.second;
-    return RTC_OK;
-}
 
 // The scene's header as a launch of up to RTC_STACK_DEPTH_BASE levels takes it: where the packed counter of such a kernel cannot hold
 // the culled shadow rays one lane may answer (rtc_launch_plan.h culled_count_fits), the whole-light cull and the block cones are off
@@ -1421,13 +1393,11 @@ static rtc_status use_grid_feedback(rtc_ctx* c, const Partition& q, uint32_t row
 // frame 0.95 ms cold, 0.71 once any context of the process has launched the same code; mesh 11.2 / 3.4).  It is paid once per
 // process and queue, here: one workgroup of the same kernel over zero rows (it finds no pixel of its own and writes only
 // the counters the real launch overwrites), in front of the events that time the frame.
-static rtc_status warm_up(rtc_ctx* c, hipFunction_t spec_fn, hipStream_t stream, const RenderArgs& a) {
-    const auto key = std::make_pair(spec_fn ? (const void*)spec_fn : aot_family(c).key(c->ss_k), (const void*)stream);
-    if (c->warmed.count(key)) return RTC_OK;
-    c->warmed.insert(key);
-    RenderArgs w = a;
-    w.rows = 0u, w.tiles = nullptr, w.wave_ticks = nullptr, w.progress = nullptr, w.done = nullptr, w.fill_wg_rows = 0u, w.swizzle = 0u, w.blocks_y = 1u;
-    HIP_TRY(launch_render(c, spec_fn, dim3(1, 1), stream, w));
+// (`kernel`: the slot's kernel this launch runs -- `fn`, or the ahead-of-time family's key; `launch_no_op`: one workgroup of it over the
+// caller's no-op variant of its arguments)
+template <class Launch>
+static rtc_status warm_up(rtc_ctx::SceneKernel& s, const void* kernel, hipStream_t stream, Launch&& launch_no_op) {
+    if (s.warmed.insert(std::make_pair(kernel, (const void*)stream)).second) HIP_TRY(launch_no_op());
     return RTC_OK;
 }
 
@@ -1553,9 +1523,9 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     // camera.rs:76 takes any depth; the kernels' frame stack (one suspended shade_hit per level, world.rs:62-86) holds
     // RTC_STACK_DEPTH_BASE levels.  Deeper than that, the scene's kernel is compiled once more with a longer stack -- 16, 32,
     // ... RTC_MAX_DEPTH levels of per-lane scratch -- on first use, and kept with the context.
-    hipFunction_t spec_fn = c->spec_fn;
+    hipFunction_t spec_fn = c->render.fn;
     if (depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) depth = RTC_STACK_DEPTH_BASE;
-    if (depth > RTC_STACK_DEPTH_BASE && rows > 0u) RTC_TRY(deep_kernel(c, depth, c->spec_defs, c->deep_fn, &spec_fn));
+    if (depth > RTC_STACK_DEPTH_BASE && rows > 0u) RTC_TRY(deep_kernel(c, depth, c->render, &spec_fn));
     const bool shares = spec_fn && c->spec_shares;  // only kernels compiled for it share lanes
     // (supersampled: capped so that a k x k group lies in one wave's tile, rtc_launch_plan.h)
     const uint32_t share_log2 = shares ? std::min(choose_share_log2(c->hdr, rows, P, progress == nullptr), ss_max_share_log2(ss_k)) : 0u;
@@ -1598,7 +1568,11 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     // ---- warm up, time, launch, sum
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     HIP_TRY(next_event_pair(c, &ev));
-    RTC_TRY(warm_up(c, spec_fn, stream, a));
+    RTC_TRY(warm_up(c->render, spec_fn ? (const void*)spec_fn : aot_family(c).key(ss_k), stream, [&] {
+        RenderArgs w = a;
+        w.rows = 0u, w.tiles = nullptr, w.wave_ticks = nullptr, w.progress = nullptr, w.done = nullptr, w.fill_wg_rows = 0u, w.swizzle = 0u, w.blocks_y = 1u;
+        return launch_render(c, spec_fn, dim3(1, 1), stream, w);
+    }));
     HIP_TRY(hipEventRecord(ev->first, stream));
     const bool tile_fill = lp.shape == LaunchPlan::SCENE_TILES && L.scene_tiles->n_fill != 0;
     if (tile_fill) RTC_TRY(fork_tile_fill(c, *L.scene_tiles, d_out_rgb, rows, out_u8, stream));
@@ -1639,7 +1613,7 @@ rtc_status rtc::ctx_collect(rtc_ctx* c, uint32_t n_slots, rtc_stats* out) {
     HIP_TRY(sum_event_ms(c, &sum_ms));
     out->kernel_ms = (float)sum_ms;
     out->launches = (uint32_t)c->events_used;
-    out->flags = c->jit_note.empty() ? 0u : RTC_STATS_JIT_FALLBACK;
+    out->flags = c->render.note.empty() ? 0u : RTC_STATS_JIT_FALLBACK;
     c->events_used = 0;
     return RTC_OK;
 }
@@ -1787,9 +1761,16 @@ rtc_status rtc_diag_scene_plan(const rtc_scene* scene, const rtc_camera* camera,
              (int)p.simple, p.heavy_tiles.size(), p.heavy_w, p.heavy_h, (double)p.scene_box_coverage, p.scene_rect[0], p.scene_rect[1], p.scene_rect[2],
              p.scene_rect[3], (double)p.scene_rect_coverage, p.scene_tile_mask.size(), p.scene_tiles_w, p.scene_tiles_h, (int)p.spec_shares,
              (int)p.spec_blocks_y, (int)p.spec_rect, p.tree_waves, (int)p.wf_pays, (int)p.compile_now);
-    std::string out = std::string(b) + "family_name=" + p.family_name + "\nspec_name=" + p.spec_name + "\nspec_defs=";
-    for (size_t i = 0; i < p.spec_defs.size(); i++) out += (i ? " " : "") + p.spec_defs[i];
-    out += "\n";
+    std::string out = b;
+    auto add = [&](const std::string& prefix, const KernelVariant& v) {  // <prefix>family_name, <prefix>spec_name, <prefix>spec_defs
+        out += prefix + "family_name=" + v.family_name + "\n" + prefix + "spec_name=" + v.spec_name + "\n" + prefix + "spec_defs=";
+        for (size_t i = 0; i < v.defs.size(); i++) out += (i ? " " : "") + v.defs[i];
+        out += "\n";
+    };
+    add("", render_variant(p));
+    add("trace_", trace_variant(p));
+    for (uint32_t k : {2u, 4u}) add("adaptive" + std::to_string(k) + "_", refine_variant(p, k));
+    for (uint32_t k : {2u, 4u}) add("ss" + std::to_string(k) + "_", render_variant(p, k));  // (of this camera as the fine one)
     if (out.size() >= cap) return fail(RTC_ERR_INVALID_ARG, "rtc_diag_scene_plan: the text needs %zu bytes", out.size() + 1);
     std::memcpy(text, out.c_str(), out.size() + 1);
     return RTC_OK;
@@ -1846,43 +1827,12 @@ rtc_status rtc_ctx_render_hits(rtc_ctx* c, const rtc_partition* part, const rtc_
 }  // extern "C"
 
 // ---- ray streams (rtc_trace.h) ---------------------------------------------------
-// The scene's ray-stream kernel for this trace, or null: the ahead-of-time family.  `want`: the specialisation policy asks for
-// the scene's own kernel (rtc_ctx_set_scene's policy with the number of rays in the place of the frame's pixels); deeper than
-// the ahead-of-time stack it is always a scene kernel, compiled with a longer one (deep_kernel).  Compiled on first use.
-static rtc_status trace_kernel_for(rtc_ctx* c, int32_t depth, bool want, hipFunction_t* fn, std::string* id) {
-    rtc_ctx::Trace& t = c->trace;
-    *fn = nullptr;
-    if (depth > RTC_STACK_DEPTH_BASE) return deep_kernel(c, depth, t.defs, t.deep, fn, id);
-    if (!want || t.failed) return RTC_OK;
-    if (t.fn == nullptr) {
-        const rtc_status jst = jit_get(c->policy, c->device, t.defs, &t.fn, &t.fn_id);
-        if (jst != RTC_OK) {  // as jit_failed: RTC_AMD_SPECIALIZE=1 an error, else the ahead-of-time kernel, and say so
-            t.fn = nullptr;
-            t.failed = true;
-            t.note = rtc_last_error();
-            if (c->policy.specialise == 1) return jst;
-            static bool warned = false;
-            if (!warned && !c->policy.quiet) {
-                warned = true;
-                std::fprintf(stderr, "librtc_amd: scene specialisation unavailable, tracing with the slower ahead-of-time kernel %s: %.300s\n",
-                             t.family_name.c_str(), t.note.c_str());
-            }
-            return RTC_OK;
-        }
-    }
-    *fn = t.fn, *id = t.fn_id;
-    return RTC_OK;
-}
-
 static hipError_t launch_trace(rtc_ctx* c, hipFunction_t fn, uint32_t n_workgroups, hipStream_t stream, TraceArgs& a) {
-    if (fn) {
-        void* params[] = {&a};
-        return hipModuleLaunchKernel(fn, n_workgroups, 1, 1, 256, 1, 1, 0, stream, params, nullptr);
-    }
-    dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
-        hipLaunchKernelGGL((trace_kernel<decltype(nobj)::value, decltype(simple)::value>), dim3(n_workgroups), dim3(256), 0, stream, a);
+    return launch_scene_kernel(fn, dim3(n_workgroups), stream, a, [&] {
+        dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+            hipLaunchKernelGGL((trace_kernel<decltype(nobj)::value, decltype(simple)::value>), dim3(n_workgroups), dim3(256), 0, stream, a);
+        });
     });
-    return hipGetLastError();
 }
 
 // rtc_ctx_trace's and rtc_ctx_trace_reordered's argument checks, the context's last among them: all are decided on the host, before
@@ -1908,11 +1858,12 @@ static rtc_status trace_launch(rtc_ctx* c, int32_t depth, const void* d_origins,
     rtc_ctx::Trace& t = c->trace;
     const Policy& P = c->policy;
     if (depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) depth = RTC_STACK_DEPTH_BASE;  // (as rtc_ctx_render)
-    const bool want = !t.defs.empty() && wants_scene_kernel(P, n, t.compile_any_size, t.compile_never);
+    // (rtc_ctx_set_scene's policy with the number of rays in the place of the frame's pixels)
+    const bool want = !t.kernel.variant.defs.empty() && wants_scene_kernel(P, n, t.compile_any_size, t.compile_never);
     hipFunction_t fn = nullptr;
     std::string id;
-    RTC_TRY(trace_kernel_for(c, depth, want, &fn, &id));
-    t.name = fn ? t.spec_name : t.family_name;
+    RTC_TRY(scene_kernel_for(c, t.kernel, depth, want, false, t.kernel.failed, t.kernel.note, "tracing with", true, &fn, &id));
+    t.name = fn ? t.kernel.variant.spec_name : t.kernel.variant.family_name;
     t.id = fn ? id : aot_trace_kernel_id();
     // workspaces (grow-only; a trace in flight on this stream may still be writing the old partials: grow frees, which waits)
     const uint32_t n_workgroups = (uint32_t)(((uint64_t)n + 255u) / 256u);
@@ -1929,12 +1880,11 @@ static rtc_status trace_launch(rtc_ctx* c, int32_t depth, const void* d_origins,
     a.n = n;
     a.depth = depth;
     // warm up (warm_up: a code object's first launch on a queue, in front of the events), time, launch, sum
-    const auto key = std::make_pair(fn ? (const void*)fn : aot_family(c).key(), (const void*)stream);
-    if (t.warmed.insert(key).second) {
+    RTC_TRY(warm_up(t.kernel, fn ? (const void*)fn : aot_family(c).key(), stream, [&] {
         TraceArgs w = a;
         w.n = 0u;
-        HIP_TRY(launch_trace(c, fn, 1u, stream, w));
-    }
+        return launch_trace(c, fn, 1u, stream, w);
+    }));
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     HIP_TRY(next_event_pair(t.events, t.events_used, &ev));
     HIP_TRY(hipEventRecord(ev->first, stream));
@@ -2209,33 +2159,6 @@ const char* rtc_ctx_trace_kernel_id(rtc_ctx* c) { return c ? c->trace.id.c_str()
 
 // ---- adaptive supersampling (rtc_adaptive.h) ---------------------------------------
 static_assert(ADAPTIVE_STEP == ADAPTIVE_STEP_SLOTS, "the kernel's step is the plan's");
-// trace_kernel_for for the refinement kernel of factor k: the scene's own where the policy asks for it, always deeper than the
-// ahead-of-time stack, compiled on first use; null: the ahead-of-time family.
-static rtc_status adaptive_kernel_for(rtc_ctx* c, int32_t depth, uint32_t k, bool want, hipFunction_t* fn, std::string* id) {
-    rtc_ctx::Adaptive& ad = c->adaptive;
-    rtc_ctx::Adaptive::PerK& pk = ad.per_k[k == 4u ? 1 : 0];
-    *fn = nullptr;
-    if (depth > RTC_STACK_DEPTH_BASE) return deep_kernel(c, depth, pk.defs, pk.deep, fn, id);
-    if (!want || ad.failed) return RTC_OK;
-    if (pk.fn == nullptr) {
-        const rtc_status jst = jit_get(c->policy, c->device, pk.defs, &pk.fn, &pk.fn_id);
-        if (jst != RTC_OK) {  // as trace_kernel_for: RTC_AMD_SPECIALIZE=1 an error, else the ahead-of-time kernel, and say so
-            pk.fn = nullptr;
-            ad.failed = true;
-            ad.note = rtc_last_error();
-            if (c->policy.specialise == 1) return jst;
-            static bool warned = false;
-            if (!warned && !c->policy.quiet) {
-                warned = true;
-                std::fprintf(stderr, "librtc_amd: scene specialisation unavailable, refining with the slower ahead-of-time kernel: %.300s\n", ad.note.c_str());
-            }
-            return RTC_OK;
-        }
-    }
-    *fn = pk.fn, *id = pk.fn_id;
-    return RTC_OK;
-}
-
 // f(the ahead-of-time refinement kernel of the context's family and factor k)
 template <class F>
 static void dispatch_adaptive(rtc_ctx* c, uint32_t k, F&& f) {
@@ -2245,12 +2168,9 @@ static void dispatch_adaptive(rtc_ctx* c, uint32_t k, F&& f) {
     });
 }
 static hipError_t launch_adaptive(rtc_ctx* c, hipFunction_t fn, uint32_t k, uint32_t n_workgroups, hipStream_t stream, AdaptiveRefineArgs& a) {
-    if (fn) {
-        void* params[] = {&a};
-        return hipModuleLaunchKernel(fn, n_workgroups, 1, 1, 256, 1, 1, 0, stream, params, nullptr);
-    }
-    dispatch_adaptive(c, k, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_workgroups), dim3(256), 0, stream, a); });
-    return hipGetLastError();
+    return launch_scene_kernel(fn, dim3(n_workgroups), stream, a, [&] {
+        dispatch_adaptive(c, k, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_workgroups), dim3(256), 0, stream, a); });
+    });
 }
 // workgroups of the refinement kernel a compute unit holds at once (asked once per kernel; 0 from the runtime: one)
 static int adaptive_wgs_per_cu(rtc_ctx* c, hipFunction_t fn, uint32_t k, const void* key) {
@@ -2293,16 +2213,11 @@ rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float 
     // ---- the refinement kernel: the policy's question is asked with the frame's pixels, as the base pass asks it
     int32_t refine_depth = depth;
     if (refine_depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) refine_depth = RTC_STACK_DEPTH_BASE;  // (as rtc_ctx_render)
-    const rtc_ctx::Adaptive::PerK& pk = ad.per_k[k == 4u ? 1 : 0];
-    const bool want = !pk.defs.empty() && wants_scene_kernel(P, n_pixels, c->trace.compile_any_size, c->trace.compile_never);
+    rtc_ctx::SceneKernel& slot = ad.kernel[k == 4u ? 1 : 0];
+    const bool want = !slot.variant.defs.empty() && wants_scene_kernel(P, n_pixels, c->trace.compile_any_size, c->trace.compile_never);
     hipFunction_t fn = nullptr;
     std::string id;
-    RTC_TRY(adaptive_kernel_for(c, refine_depth, k, want, &fn, &id));
-    auto renamed = [&](const std::string& name) {  // trace_kernel<...> -> adaptive_refine_kernel<...;ss=k>
-        std::string out = name.rfind("trace_", 0) == 0 ? "adaptive_refine_" + name.substr(6) : name;
-        if (!out.empty()) out.insert(out.size() - 1, ";ss=" + std::to_string(k));
-        return out;
-    };
+    RTC_TRY(scene_kernel_for(c, slot, refine_depth, want, false, ad.failed, ad.note, "refining with", false, &fn, &id));
     // ---- workspaces (the list: first use / a larger frame only)
     HIP_TRY(grow(&ad.d_list, &ad.list_cap, n_pixels));
     if (!ad.d_queue) HIP_TRY(hipMalloc((void**)&ad.d_queue, sizeof(AdaptiveQueue)));
@@ -2323,11 +2238,11 @@ rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float 
     // ---- the base frame B: the context's normal render, with its tiles, lists, feedback and stats
     RTC_TRY(rtc_ctx_render(c, depth, nullptr, d_out_rgb, stream_));
     // ---- warm up (in front of the events), mask, refinement, sum
-    if (ad.warmed.insert(std::make_pair(kernel_key, (const void*)stream)).second) {
+    RTC_TRY(warm_up(slot, kernel_key, stream, [&] {
         AdaptiveRefineArgs w = a;
         w.warm = 1u;
-        HIP_TRY(launch_adaptive(c, fn, k, 1u, stream, w));
-    }
+        return launch_adaptive(c, fn, k, 1u, stream, w);
+    }));
     HIP_TRY(hipMemsetAsync(ad.d_queue, 0, sizeof(AdaptiveQueue), stream));
     HIP_TRY(hipEventRecord(ad.ev[0], stream));
     AdaptiveMaskArgs m;
@@ -2340,7 +2255,7 @@ rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float 
     HIP_TRY(launch_adaptive(c, fn, k, n_workgroups, stream, a));
     HIP_TRY(hipEventRecord(ad.ev[2], stream));
     // (named once it has been launched: a call that failed on the way names no kernel it did not run)
-    ad.name = renamed(fn ? c->trace.spec_name : c->trace.family_name);
+    ad.name = fn ? slot.variant.spec_name : slot.variant.family_name;
     ad.id = fn ? id : aot_adaptive_kernel_id(k);
     ad.ran = true;
     return RTC_OK;
@@ -2407,12 +2322,12 @@ rtc_status rtc_ctx_stats(rtc_ctx* c, rtc_stats* out) {
     if (c->trace.last) {  // the last launch was rtc_ctx_trace: its counters, and the traces' own events
         rtc_ctx::Trace& t = c->trace;
         out->pixels = t.last_n;
-        return read_launch_stats(c, t.d_total, t.events, t.events_used, t.note, out);
+        return read_launch_stats(c, t.d_total, t.events, t.events_used, t.kernel.note, out);
     }
     out->rows = c->last_rows;
     out->pixels = c->last_pixels;
     if (!c->rendered) return RTC_OK;
-    return read_launch_stats(c, c->d_total, c->events, c->events_used, c->jit_note, out);
+    return read_launch_stats(c, c->d_total, c->events, c->events_used, c->render.note, out);
 }
 
 const char* rtc_ctx_kernel_name(rtc_ctx* c) {
@@ -2423,7 +2338,7 @@ const char* rtc_ctx_kernel_name(rtc_ctx* c) {
     }
     return c->kernel_name.c_str();
 }
-const char* rtc_ctx_jit_status(rtc_ctx* c) { return c ? c->jit_note.c_str() : ""; }
+const char* rtc_ctx_jit_status(rtc_ctx* c) { return c ? c->render.note.c_str() : ""; }
 const char* rtc_ctx_kernel_id(rtc_ctx* c) { return c ? c->kernel_id.c_str() : ""; }
 
 rtc_status rtc_ctx_quantize(rtc_ctx* c, const void* d_rgb, uint64_t n, void* d_out_u8, void* stream_) {

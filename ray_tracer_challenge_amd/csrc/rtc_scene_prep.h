@@ -1,7 +1,8 @@
 // rtc_scene_prep.h -- getting a scene ready, on the host: rtc_scene + rtc_camera become the kernel's header and records
 // (flatten and its stages: object records, triangle pre-culling boxes, the traversal stream, scene box and region, light,
 // camera), and the resident records decide which kernel renders them (plan_scene: tile coverages, scene rectangle, the
-// option list and name of the scene's kernel).  This is where the arguments of ERROR_BUDGET.md (B6, B7, B8, B10, E1, E2)
+// option list and name of the scene's kernel; render_variant / trace_variant / refine_variant: those of the supersampling, ray-stream
+// and refinement kernels derived from it).  This is where the arguments of ERROR_BUDGET.md (B6, B7, B8, B10, E1, E2)
 // become numbers.  No device, no context: rtc_device.hip's rtc_ctx_set_scene uploads what flatten packed and copies a
 // ScenePlan into the context; tests/test_scene_prep.py reaches both through rtc_diag_scene_plan.
 // Included after rtc_kernel_core.h (SceneHdr, SceneSoA, the SHAPE_* / TRAV_* constants).
@@ -1751,6 +1752,72 @@ inline ScenePlan plan_scene(const Policy& P, const SceneHdr& hdr, const std::vec
         plan_many_kernel(P, hdr, soa, facts, defs, &p);
     }
     return p;
+}
+
+// ---- kernel variants ---------------------------------------------------------------------------------------------------
+// One kernel of a scene: the options it is compiled with -- in order: jit_get hashes them into the cache key and the kernel id;
+// empty: a world without objects -- and the names of the ahead-of-time family and of the scene's own kernel.  The plan's
+// spec_defs / family_name / spec_name are the frame's kernel; the functions below derive every other kernel a context keeps
+// from it, and nothing else rewrites an option or a name.
+struct KernelVariant {
+    std::vector<std::string> defs;
+    std::string family_name, spec_name;
+};
+// the launch shapes a variant does not have ("-DRTC_SPEC_RECT=" ...), off in its key
+inline void switch_off(std::vector<std::string>* defs, std::initializer_list<const char*> options) {
+    for (auto& d : *defs)
+        for (const char* o : options)
+            if (d == std::string(o) + "1") d.back() = '0';
+}
+// "kernel<...>" -> "kernel<...;ss=k>", "kernel_spec[...]" likewise (a name that is not there stays empty)
+inline std::string with_factor(std::string name, uint32_t k) {
+    if (!name.empty()) name.insert(name.size() - 1, ";ss=" + std::to_string(k));
+    return name;
+}
+inline std::string with_prefix(const std::string& name, const char* from, const char* to) {
+    return name.rfind(from, 0) == 0 ? to + name.substr(std::strlen(from)) : name;
+}
+// The frame's kernel of a context of factor k (rtc_supersample.h; 1: the plan's own): ss_render_kernel<...;ss=k>.  The
+// supersampling body has neither the loop over blocks nor the rectangle's offsets.
+inline KernelVariant render_variant(const ScenePlan& p, uint32_t k = 1u) {
+    KernelVariant v = {p.spec_defs, p.family_name, p.spec_name};
+    if (k == 1u) return v;
+    for (std::string* name : {&v.family_name, &v.spec_name})
+        if (!name->empty()) *name = "ss_" + with_factor(*name, k);
+    if (!v.defs.empty()) {
+        switch_off(&v.defs, {"-DRTC_SPEC_BLOCKS_Y=", "-DRTC_SPEC_RECT="});
+        v.defs.push_back("-DRTC_SPEC_SS=" + std::to_string(k));
+    }
+    return v;
+}
+// Ray streams (rtc_trace.h): trace_kernel<...>.  No launch shapes, lane sharing among them -- a stream runs one lane per ray, and
+// its kernel must not depend on the size of a frame it does not draw.  (Of the plan before plan_supersampled: color_at does not
+// read the camera, so a plain and a supersampled context trace with one kernel.)
+inline KernelVariant trace_variant(const ScenePlan& p) {
+    KernelVariant v = {p.spec_defs, with_prefix(p.family_name, "render_", "trace_"), with_prefix(p.spec_name, "render_", "trace_")};
+    switch_off(&v.defs, {"-DRTC_SPEC_BLOCKS_Y=", "-DRTC_SPEC_RECT=", "-DRTC_SPEC_SHARE="});
+    if (!v.defs.empty()) v.defs.push_back("-DRTC_SPEC_TRACE=1");
+    return v;
+}
+// The refinement of an adaptive frame (rtc_adaptive.h), k = 2, 4: adaptive_refine_kernel<...;ss=k>, a ray stream's options with
+// its factor in the place of -DRTC_SPEC_TRACE=1.
+inline KernelVariant refine_variant(const ScenePlan& p, uint32_t k) {
+    KernelVariant v = trace_variant(p);
+    v.family_name = with_factor(with_prefix(v.family_name, "trace_", "adaptive_refine_"), k);
+    v.spec_name = with_factor(with_prefix(v.spec_name, "trace_", "adaptive_refine_"), k);
+    if (!v.defs.empty()) v.defs.back() = "-DRTC_SPEC_ADAPTIVE=" + std::to_string(k);
+    return v;
+}
+// The plan of a supersampled context, k = 2, 4 (`p`: plan_scene of the FINE camera).  Scene tiles, the scene rectangle and several
+// blocks per workgroup address the canvas by fine pixels and are not carried over: such scenes are a plain grid, where the
+// scene-box early-out still applies; nor is the level-by-level renderer.
+inline void plan_supersampled(ScenePlan* p, uint32_t k) {
+    const KernelVariant v = render_variant(*p, k);
+    p->spec_defs = v.defs, p->family_name = v.family_name, p->spec_name = v.spec_name;
+    p->scene_tile_mask.clear();
+    p->scene_rect[0] = p->scene_rect[1] = p->scene_rect[2] = p->scene_rect[3] = 0u;
+    p->spec_blocks_y = p->spec_rect = false;
+    p->wf_pays = false;
 }
 
 }  // namespace rtc

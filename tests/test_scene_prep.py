@@ -157,6 +157,95 @@ def test_option_lists_are_well_formed(name, specialise, monkeypatch):
             assert plan["compile_now"] == "1" or plan["spec_name"] == "render_kernel_spec[any]", plan
 
 
+# ------------------------------------------------------------------------------------------------- kernel variants
+# (rtc_scene_prep.h render_variant / trace_variant / refine_variant: the options are the JIT cache key, in order, and what
+# rtc_ctx_*_kernel_id names; the names are what rtc_ctx_*_kernel_name reports)
+def _switched_off(options, shapes):
+    on = ["-DRTC_SPEC_%s=1" % s for s in shapes]
+    return [o[:-1] + "0" if o in on else o for o in options]
+
+
+def _variant(plan, prefix):
+    return plan[prefix + "spec_defs"].split(), plan[prefix + "family_name"], plan[prefix + "spec_name"]
+
+
+def _with_factor(name, k):
+    return name and name[:-1] + ";ss=%d" % k + name[-1]
+
+
+def _assert_variants_follow(plan, what):
+    render, family, spec = _variant(plan, "")
+    trace, trace_family, trace_spec = _variant(plan, "trace_")
+    assert trace == (_switched_off(render, ("BLOCKS_Y", "RECT", "SHARE")) + ["-DRTC_SPEC_TRACE=1"] if render else []), what
+    for name, traced in ((family, trace_family), (spec, trace_spec)):
+        assert name == "" or name.startswith("render_kernel"), (what, name)
+        assert traced == name.replace("render_", "trace_", 1), (what, traced)
+    for k in (2, 4):
+        refine, refine_family, refine_spec = _variant(plan, "adaptive%d_" % k)
+        assert refine == (trace[:-1] + ["-DRTC_SPEC_ADAPTIVE=%d" % k] if trace else []), (what, k)
+        assert refine_family == _with_factor(trace_family.replace("trace_", "adaptive_refine_", 1), k), (what, k, refine_family)
+        assert refine_spec == _with_factor(trace_spec.replace("trace_", "adaptive_refine_", 1), k), (what, k, refine_spec)
+        ss, ss_family, ss_spec = _variant(plan, "ss%d_" % k)
+        assert ss == (_switched_off(render, ("BLOCKS_Y", "RECT")) + ["-DRTC_SPEC_SS=%d" % k] if render else []), (what, k)
+        assert ss_family == "ss_" + _with_factor(family, k), (what, k, ss_family)
+        assert ss_spec == (spec and "ss_" + _with_factor(spec, k)), (what, k, ss_spec)
+
+
+@pytest.mark.parametrize("specialise", ["0", "1"])
+@pytest.mark.parametrize("name", SCENES)
+def test_kernel_variants_follow_the_render_kernel(name, specialise, monkeypatch):
+    monkeypatch.setenv("RTC_AMD_SPECIALIZE", specialise)
+    world, camera = _scene(name)
+    _assert_variants_follow(world.scene_plan(camera)[1], name)
+
+
+def test_kernel_variants_of_every_launch_shape_and_of_no_objects(monkeypatch):
+    """The frames above are thumbnails: the scene rectangle and several blocks per workgroup are for larger ones, and lane
+    sharing is not for all.  A world without objects has no options and no scene kernel's name: neither have its variants."""
+    seen = set()
+    for name, size in (("sphere_grid", (2048, 1536)), ("soft_shadows", (64, 48)), ("sphere_grid", (64, 48))):
+        world, camera = _scene(name, size)
+        plan = world.scene_plan(camera)[1]
+        seen |= {s for s in ("SHARE", "BLOCKS_Y", "RECT") if "-DRTC_SPEC_%s=1" % s in plan["spec_defs"].split()}
+        seen |= {"not " + s for s in ("SHARE", "BLOCKS_Y", "RECT") if "-DRTC_SPEC_%s=0" % s in plan["spec_defs"].split()}
+        _assert_variants_follow(plan, (name, size))
+    assert seen == {"SHARE", "BLOCKS_Y", "RECT", "not SHARE", "not BLOCKS_Y", "not RECT"}, seen
+    plan = P.World([], _scene("soft_shadows")[0].light).scene_plan(_scene("soft_shadows")[1])[1]
+    assert _variant(plan, "") == ([], "render_kernel<4,simple>", "")
+    assert _variant(plan, "trace_") == ([], "trace_kernel<4,simple>", "")
+    assert _variant(plan, "adaptive2_") == ([], "adaptive_refine_kernel<4,simple;ss=2>", "")
+    assert _variant(plan, "ss4_") == ([], "ss_render_kernel<4,simple;ss=4>", "")
+    _assert_variants_follow(plan, "no objects")
+
+
+def test_kernel_variant_names_of_three_scenes():
+    """... and literally, so that the rule above is not only restated."""
+    expected = {
+        "soft_shadows": ("<4,simple", ">", "_spec[0x402,0x1501,0x1500,0x1500;simple", "]"),
+        "hexagons": ("<tree", ">", "_spec[tree;patterns", "]"),
+        "mesh": ("<tree", ">", "_spec[tree;patterns", "]"),
+    }
+    for name, (family, family_end, spec, spec_end) in expected.items():
+        world, camera = _scene(name)
+        plan = world.scene_plan(camera)[1]
+        assert (plan["family_name"], plan["spec_name"]) == ("render_kernel" + family + family_end, "render_kernel" + spec + spec_end)
+        assert (plan["trace_family_name"], plan["trace_spec_name"]) == ("trace_kernel" + family + family_end, "trace_kernel" + spec + spec_end)
+        for k in ("2", "4"):
+            tag = ";ss=" + k
+            assert plan["adaptive%s_family_name" % k] == "adaptive_refine_kernel" + family + tag + family_end
+            assert plan["adaptive%s_spec_name" % k] == "adaptive_refine_kernel" + spec + tag + spec_end
+            assert plan["ss%s_family_name" % k] == "ss_render_kernel" + family + tag + family_end
+            assert plan["ss%s_spec_name" % k] == "ss_render_kernel" + spec + tag + spec_end
+    world, camera = _scene("soft_shadows")
+    plan = world.scene_plan(camera)[1]  # one of them in full
+    assert plan["adaptive4_spec_name"] == "adaptive_refine_kernel_spec[0x402,0x1501,0x1500,0x1500;simple;ss=4]"
+    assert plan["ss2_family_name"] == "ss_render_kernel<4,simple;ss=2>"
+    assert plan["trace_spec_defs"] == (
+        "-DRTC_SPEC_LIST=0x402,0x1501,0x1500,0x1500 -DRTC_SPEC_NOBJ=4 -DRTC_SPEC_SIMPLE=1 -DRTC_SPEC_LIGHT_KIND=1 -DRTC_SPEC_JITTER=2 "
+        "-DRTC_SPEC_PATTERNS=0 -DRTC_SPEC_GATES=0 -DRTC_LIGHT_VGPRS -DRTC_SPEC_SHARE=0 -DRTC_SPEC_BLOCKS_Y=0 -DRTC_SPEC_RECT=0 "
+        "-DRTC_SPEC_LIGHT_ZEROS=46 -DRTC_SPEC_ANY_REFL=1 -DRTC_SPEC_ANY_REFR=0 -DRTC_SPEC_REG_LEVELS=0 -DRTC_SPEC_ANY_SPECULAR=0 -DRTC_SPEC_TRACE=1")
+
+
 # ---------------------------------------------------------------------------------------- policy switches reach the packing
 def _tree_world():
     for seed in range(10):
