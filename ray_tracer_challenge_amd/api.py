@@ -11,6 +11,7 @@ Everything numeric happens behind the C ABI (include/rtc.h): scene math on the
 host in librtc_amd.so, rendering on the MI355X.  There is no fallback path.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -898,6 +899,25 @@ def default_world():
     s1 = Sphere(identity_4x4(), Material(color=(0.8, 1.0, 0.6), diffuse=0.7, specular=0.2))
     s2 = Sphere(scaling(0.5, 0.5, 0.5), Material())
     return World([s1, s2], PointLight(point(-10.0, 10.0, -10.0), color(1, 1, 1)))
+
+
+def jit_cache_publish(directory, file_name, code):
+    """rtc_diag_jit_cache_publish: the scene-kernel cache's publish (csrc/rtc_jit.h) of `code` (bytes) as
+    <directory>/<file_name>, without a GPU -> was the entry published."""
+    return L.lib().rtc_diag_jit_cache_publish(os.fsencode(directory), os.fsencode(file_name), code, len(code)) != 0
+
+
+def jit_cache_read(path):
+    """rtc_diag_jit_cache_read: the code object of a whole, undamaged cache entry, or None."""
+    size = os.path.getsize(path) if os.path.exists(path) else 0
+    out = C.create_string_buffer(max(size, 1))
+    n = L.lib().rtc_diag_jit_cache_read(os.fsencode(path), out, len(out))
+    return None if n < 0 else out.raw[:n]
+
+
+def deep_stack_cap(depth):
+    """rtc_diag_deep_stack_cap: the frame-stack size of the scene kernel compiled for a recursion of `depth` levels."""
+    return L.lib().rtc_diag_deep_stack_cap(int(depth))
 
 
 # -------------------------------------------------------------------- canvas.rs

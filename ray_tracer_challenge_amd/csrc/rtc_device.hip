@@ -1,18 +1,17 @@
 // rtc_device.hip -- the MI355X (gfx950 / CDNA4) render path of librtc_amd.so.
 //
 // This translation unit holds the HOST side of the device path: the persistent context, kernel
-// launches, the batched test entry points and the scene-specialising JIT.  Scene validation,
-// flattening and the choice of a scene's kernel are rtc_scene_prep.h, how a launch is cut
-// rtc_launch_plan.h (both host-only); the device code itself lives in rtc_kernel_core.h (shared
-// with the hiprtc compile).
+// launches, the batched test entry points and the device part of the scene-specialising JIT
+// (compile, load, remember).  Scene validation, flattening and the choice of a scene's kernels are
+// rtc_scene_prep.h, what a compile is made of and the disk cache's entries rtc_jit.h, how a launch
+// is cut rtc_launch_plan.h (all host-only); the device code itself lives in rtc_kernel_core.h
+// (shared with the hiprtc compile).
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
 #include <dlfcn.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
-#include <cerrno>
 #include <chrono>
 
 #include <algorithm>
@@ -23,10 +22,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <map>
 #include <mutex>
-#include <sstream>
 #include <string>
 #include <utility>
 #include <set>
@@ -338,16 +335,13 @@ static void drop_block_lists(rtc_ctx* c) {
 //  rtc_kernel_core.h once more with them baked in (-DRTC_SPEC_LIST=...): no kind switches, dead
 //  shape code removed, tighter scheduling -- C3 4.06 -> 3.13 ms with bit-identical output.  Only the
 //  scene's *shape* (object count, kinds, flags, light kind, jitter mode) is specialised; all values
-//  stay run-time data.  Compiled code is cached in-process and on disk (<lib dir>/jit_cache/).
+//  stay run-time data.  Compiled code is cached in-process and on disk (<lib dir>/jit_cache/);
+//  options, key, cache file name and the cache's entries are rtc_jit.h's (host-only).
 //  Policy: RTC_AMD_SPECIALIZE=0 never, =1 always; default: scenes of <= 8 objects rendered at >= 2^18
 //  pixels (a 0.7 s compile is not worth it for thumbnails; the AOT kernels produce the same bits).
 // ============================================================================
 namespace {
 
-struct CacheHeader {
-    char magic[8];
-    uint64_t size, checksum;
-};
 struct JitModule {
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
@@ -366,22 +360,10 @@ std::string lib_dir() {
     return ".";
 }
 
-uint64_t fnv1a(const std::string& s, uint64_t h = 1469598103934665603ull) { return rtc::fnv1a(s.data(), s.size(), h); }
-
-bool read_file(const std::string& path, std::string* out) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return false;
-    std::ostringstream ss;
-    ss << f.rdbuf();
-    *out = ss.str();
-    return true;
-}
-
 // The kernel source travels inside the library: rtc_kernel_core_embed.inc is rtc_kernel_core.h as a string literal,
 // written by ray_tracer_challenge_amd/build.py before every compile (under hiprtc the header needs no other file).  A
 // deployment is librtc_amd.so alone -- no csrc/ or include/ beside it.  RTC_AMD_JIT_SOURCE=<path> (development) reads
 // the header from disk instead, so a kernel experiment needs no rebuild of the library.
-// (k_ss_src: rtc_supersample.h likewise, for a scene's supersampling kernel)
 #include "rtc_kernel_core_embed.inc"
 
 std::string jit_cache_dir(const Policy& P) {  // RTC_AMD_JIT_CACHE=<dir>, or 0 / off to keep compiled kernels in memory only; default <lib dir>/jit_cache
@@ -389,16 +371,22 @@ std::string jit_cache_dir(const Policy& P) {  // RTC_AMD_JIT_CACHE=<dir>, or 0 /
     return lib_dir() + "/jit_cache";
 }
 
-// Compiles (or fetches) the specialised kernel for `defines` on the current device.
+// The text of the header beside the core that a kind's kernel includes ("" for the frame's own)
+const char* beside_text(JitKind kind) { return kind == JitKind::SS ? k_ss_src : kind == JitKind::TRACE ? k_trace_src : kind == JitKind::ADAPTIVE ? k_adaptive_src : ""; }
+// identifies the ahead-of-time kernels of this build: the source they were compiled from
+std::string aot_kernel_id(JitKind kind, uint32_t k = 1u) { return rtc::aot_kernel_id(kind, k, k_core_src, beside_text(kind)); }
+
+// Compiles (or fetches) the specialised kernel of variant `v` on the current device: what rtc_jit.h plans, compiled by hiprtc,
+// loaded and remembered.
 // `lazy` (the one-call seam, rtc_render_ex: the reference renders ONE frame per process): a kernel that is neither in this process's
 // memory nor in the disk cache is not compiled the first time its scene is seen -- *out stays null and the frame is rendered by the
 // ahead-of-time kernel: a compile is 0.5 - 2 s, the frame it speeds up a few milliseconds (tools/first_call.py: C3's first call 693 ms
 // with the compile, 121 with a filled cache, 123 ahead-of-time).  The second time the process asks for the same kernel -- frames
 // repeat -- it is compiled, and cached on disk for every process after it.
 std::set<std::string> g_jit_seen;
-rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& defines, hipFunction_t* out, std::string* id, bool lazy = false) {
+rtc_status jit_get(const Policy& P, int device, const KernelVariant& v, hipFunction_t* out, std::string* id, bool lazy = false) {
     std::string key = std::to_string(device) + "|";
-    for (const auto& d : defines) key += d + " ";
+    for (const auto& d : v.defs) key += d + " ";
     key += "|" + P.jit_source + "|" + P.jit_flags;  // (development builds: another source or other flags are another kernel)
     std::lock_guard<std::mutex> lock(g_jit_mutex);
     auto it = g_jit_cache.find(key);
@@ -407,77 +395,32 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
         *id = it->second.id;
         return RTC_OK;
     }
-    // -DRTC_SPEC_SS=k: the scene's supersampling kernel -- rtc_supersample.h beside the core, its own entry point
-    bool ss = false;
-    for (const auto& d : defines) ss = ss || d.rfind("-DRTC_SPEC_SS=", 0) == 0;
-    // -DRTC_SPEC_TRACE=1: the scene's ray-stream kernel -- rtc_trace.h beside the core, likewise (never both)
-    bool trace = false;
-    for (const auto& d : defines) trace = trace || d.rfind("-DRTC_SPEC_TRACE=", 0) == 0;
-    // -DRTC_SPEC_ADAPTIVE=k: the scene's refinement kernel of adaptive supersampling -- rtc_adaptive.h beside the core, likewise
-    bool adaptive = false;
-    for (const auto& d : defines) adaptive = adaptive || d.rfind("-DRTC_SPEC_ADAPTIVE=", 0) == 0;
-    const char* const entry = ss ? "ss_render_kernel_spec" : trace ? "trace_kernel_spec" : adaptive ? "adaptive_refine_kernel_spec" : "render_kernel_spec";
-    std::string core_file;
-    const char* core = k_core_src;
+    const JitKindFacts& kind = jit_kind_facts(v.kind);
+    std::string core = k_core_src, beside = beside_text(v.kind);
     if (!P.jit_source.empty()) {  // development builds only (Policy)
-        if (!read_file(P.jit_source, &core_file)) return fail(RTC_ERR_DEVICE, "scene specialisation: cannot read the kernel source %s", P.jit_source.c_str());
-        core = core_file.c_str();
-    }
-    // (... and rtc_supersample.h / rtc_trace.h from the same directory, when it is there: an experiment in either header needs no rebuild)
-    std::string beside_file;
-    const char* beside_src = trace ? k_trace_src : adaptive ? k_adaptive_src : k_ss_src;  // the header beside the core, whichever it is
-    const char* const beside_name = trace ? "rtc_trace.h" : adaptive ? "rtc_adaptive.h" : "rtc_supersample.h";
-    if ((ss || trace || adaptive) && !P.jit_source.empty()) {
+        if (!read_file(P.jit_source, &core)) return fail(RTC_ERR_DEVICE, "scene specialisation: cannot read the kernel source %s", P.jit_source.c_str());
+        // (... and the header beside it from the same directory, when it is there: an experiment in either header needs no rebuild)
         const size_t slash = P.jit_source.find_last_of('/');
-        const std::string beside = (slash == std::string::npos ? std::string() : P.jit_source.substr(0, slash + 1)) + beside_name;
-        if (read_file(beside, &beside_file)) beside_src = beside_file.c_str();
-    }
-    std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize"};
-    for (const auto& d : defines) opts.push_back(d);
-    // occupancy target of the specialised kernel: measured 4 -> 3.39, 5 -> 3.42, 6 -> 3.24, 7 -> 3.17, 8 -> 3.17 ms (C3) before
-    // light-cone culling; with it (more state per shade point) 5 -> 0.98, 6 -> 0.97, 7 -> 0.95, 8 -> 1.02 ms (tools/ab_env.py over -DRTC_WAVES_PER_SIMD)
-    bool waves_given = false;
-    for (const auto& d : defines) waves_given = waves_given || d.rfind("-DRTC_WAVES_PER_SIMD=", 0) == 0;
-    if (!waves_given) opts.push_back("-DRTC_WAVES_PER_SIMD=7");
-    if (!P.jit_flags.empty()) {  // development builds only: extra -D / -m flags, space separated
-        std::istringstream ss(P.jit_flags);
-        std::string tok;
-        while (ss >> tok) opts.push_back(tok);
-    }
-    // disk cache keyed by the source text, every option, the compiler's version and the ABI the argument block follows
-    std::string opt_text;
-    for (const auto& o : opts) opt_text += o + "\n";
-    if (P.jit_print) {  // development: the options, one line, as tools/spec_asm.sh takes them
-        std::string line;
-        for (size_t i = 5; i < opts.size(); i++) line += " " + opts[i];
-        std::fprintf(stderr, "librtc_amd: scene kernel options:%s\n", line.c_str());
+        std::string text;
+        if (*kind.header && read_file((slash == std::string::npos ? std::string() : P.jit_source.substr(0, slash + 1)) + kind.header, &text)) beside = text;
     }
     int rtc_major = 0, rtc_minor = 0;
     (void)hiprtcVersion(&rtc_major, &rtc_minor);
-    opt_text += "hiprtc " + std::to_string(rtc_major) + "." + std::to_string(rtc_minor) + " abi " + std::to_string(RTC_ABI_VERSION) +
-                " args " + std::to_string(sizeof(RenderArgs)) + "\n";
-    // (a ray-stream kernel takes TraceArgs: its layout is rtc_trace.h's text, hashed below, and its size is in the key as well)
-    if (trace) opt_text += "trace args " + std::to_string(sizeof(TraceArgs)) + "\n";
-    if (adaptive) opt_text += "adaptive args " + std::to_string(sizeof(AdaptiveRefineArgs)) + "\n";
-    // (Not in the key: WHICH libhiprtc this process holds.  A Python process that imported torch first compiles with the wheel's
-    // bundled compiler, the same script under rocprofv3 -- which puts /opt/rocm/lib first in LD_LIBRARY_PATH -- with the system's;
-    // both report one hiprtcVersion and emit different, equally valid code for these kernels (same images, same speed:
-    // profiles/r04_ab_compilers.txt).  Sharing the entry is what lets a profiled run measure the very code object a plain run
-    // compiled -- profiles/run_profile.sh compiles first, plainly -- and the id below says which binary it was.)
-    char name[64];
-    uint64_t source_hash = fnv1a(opt_text, fnv1a(core));
-    if (ss || trace || adaptive) source_hash = fnv1a(beside_src, source_hash);  // (the plain kernels' names do not move)
-    snprintf(name, sizeof(name), "spec_%016llx.hsaco", (unsigned long long)source_hash);
-    const std::string cache_dir = jit_cache_dir(P), cache_path = cache_dir + "/" + name;
+    const JitPlan plan = plan_jit(v.defs, v.kind, P.jit_flags, rtc_major, rtc_minor, {sizeof(RenderArgs), sizeof(TraceArgs), sizeof(AdaptiveRefineArgs)}, core, beside);
+    if (P.jit_print) {  // development: the options, one line, as tools/spec_asm.sh takes them
+        std::string line;
+        for (size_t i = 5; i < plan.opts.size(); i++) line += " " + plan.opts[i];
+        std::fprintf(stderr, "librtc_amd: scene kernel options:%s\n", line.c_str());
+    }
+    const std::string cache_dir = jit_cache_dir(P), cache_path = cache_dir + "/" + plan.cache_file;
     auto compile = [&](std::string* code) -> rtc_status {
         hiprtcProgram prog;
-        const char* src = ss ? "#include \"rtc_supersample.h\"\n" : trace ? "#include \"rtc_trace.h\"\n" : adaptive ? "#include \"rtc_adaptive.h\"\n" : "#include \"rtc_kernel_core.h\"\n";
-        const char* headers[] = {core, beside_src};
-        const char* header_names[] = {"rtc_kernel_core.h", beside_name};
-        if (hiprtcCreateProgram(&prog, src, "rtc_scene_spec.hip", (ss || trace || adaptive) ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
+        const char* headers[] = {core.c_str(), beside.c_str()};
+        const char* header_names[] = {"rtc_kernel_core.h", kind.header};
+        if (hiprtcCreateProgram(&prog, kind.program, "rtc_scene_spec.hip", *kind.header ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
             return fail(RTC_ERR_DEVICE, "hiprtcCreateProgram failed");
         std::vector<const char*> copts;
-        for (const auto& o : opts) copts.push_back(o.c_str());
+        for (const auto& o : plan.opts) copts.push_back(o.c_str());
         hiprtcResult r = hiprtcCompileProgram(prog, (int)copts.size(), copts.data());
         if (r != HIPRTC_SUCCESS) {
             size_t n = 0;
@@ -492,93 +435,33 @@ rtc_status jit_get(const Policy& P, int device, const std::vector<std::string>& 
         code->resize(n);
         hiprtcGetCode(prog, &(*code)[0]);
         hiprtcDestroyProgram(&prog);
-        // best effort: a read-only tree just means every process compiles for itself.  Only a completely written file
-        // is published (a short write -- disk full, quota -- would otherwise poison the cache for every later run).
-        if (!cache_dir.empty() && (::mkdir(cache_dir.c_str(), 0777) == 0 || errno == EEXIST)) {
-            const std::string tmp = cache_path + "." + std::to_string((long)getpid());
-            bool ok = false;
-            {
-                std::ofstream f(tmp, std::ios::binary);
-                if (f) {
-                    const CacheHeader h = {{'R', 'T', 'C', 'J', 'I', 'T', '1', 0}, (uint64_t)code->size(), fnv1a(*code)};
-                    f.write((const char*)&h, sizeof(h));
-                    f.write(code->data(), (std::streamsize)code->size());
-                    f.close();
-                    ok = f.good();
-                }
-            }
-            if (!ok || std::rename(tmp.c_str(), cache_path.c_str()) != 0) (void)::unlink(tmp.c_str());
-        }
+        (void)publish_cache_entry(cache_dir, cache_path, *code);
         return RTC_OK;
     };
-    // a cache entry is its header {magic, size, checksum} + the code object: a truncated or foreign file is ignored (the
-    // HIP runtime does not survive a damaged code object), and overwritten by the fresh compile
     std::string code;
-    bool cached = false;
-    if (!cache_dir.empty() && read_file(cache_path, &code) && code.size() > sizeof(CacheHeader)) {
-        CacheHeader h;
-        std::memcpy(&h, code.data(), sizeof(h));
-        code.erase(0, sizeof(h));
-        cached = std::memcmp(h.magic, "RTCJIT1", 8) == 0 && h.size == code.size() && h.checksum == fnv1a(code);
-    }
+    const bool cached = !cache_dir.empty() && read_cache_entry(cache_path, &code);
     if (!cached && lazy && g_jit_seen.insert(key).second) {  // (first sighting: see above)
         *out = nullptr;
         return RTC_OK;
     }
-    if (!cached) {
-        rtc_status st = compile(&code);
-        if (st != RTC_OK) return st;
-    }
+    if (!cached) RTC_TRY(compile(&code));
     JitModule m;
     hipError_t le = hipModuleLoadData(&m.mod, code.data());
-    if (le == hipSuccess) le = hipModuleGetFunction(&m.fn, m.mod, entry);
+    if (le == hipSuccess) le = hipModuleGetFunction(&m.fn, m.mod, plan.entry);
     if (le != hipSuccess && cached) {
         // a cached code object that does not load (truncated, or from another toolchain): drop it and compile once
         (void)hipGetLastError();
         (void)::unlink(cache_path.c_str());
-        rtc_status st = compile(&code);
-        if (st != RTC_OK) return st;
+        RTC_TRY(compile(&code));
         le = hipModuleLoadData(&m.mod, code.data());
-        if (le == hipSuccess) le = hipModuleGetFunction(&m.fn, m.mod, entry);
+        if (le == hipSuccess) le = hipModuleGetFunction(&m.fn, m.mod, plan.entry);
     }
     if (le != hipSuccess) return fail(RTC_ERR_DEVICE, "scene specialisation: the compiled kernel does not load: %s", hipGetErrorString(le));
-    // The id names the code object itself: "spec_<hash of source, options, compiler>.<checksum of the compiled code>".  The second
-    // half is there because one source does not always give one binary: a hiprtc compile inside a process started under rocprofv3
-    // came out different from the same compile in a plain process (LABNOTES "Round 4": 436 against 484 B of scratch per lane, 421 M
-    // against 387 M VALU instructions a C3 frame), and a profile must never be quoted for a binary it did not measure.
-    char sum[16];
-    snprintf(sum, sizeof(sum), ".%08x", (unsigned)(fnv1a(code) & 0xffffffffu));
-    m.id = std::string(name, std::strlen(name) - 6) + sum;  // without ".hsaco"
+    m.id = code_object_id(plan.cache_file, code);
     g_jit_cache[key] = m;
     *out = m.fn;
     *id = m.id;
     return RTC_OK;
-}
-
-// identifies the ahead-of-time kernels of this build: the source they were compiled from
-std::string aot_kernel_id() {
-    char b[40];
-    snprintf(b, sizeof(b), "aot_%016llx", (unsigned long long)fnv1a(k_core_src));
-    return b;
-}
-// ... and its supersampling kernels: the core's text and rtc_supersample.h's
-std::string aot_ss_kernel_id(uint32_t k) {
-    char b[48];
-    snprintf(b, sizeof(b), "aot_ss%u_%016llx", k, (unsigned long long)fnv1a(k_ss_src, fnv1a(k_core_src)));
-    return b;
-}
-// ... and its ray-stream kernels: the core's text and rtc_trace.h's
-std::string aot_trace_kernel_id() {
-    char b[48];
-    snprintf(b, sizeof(b), "aot_trace_%016llx", (unsigned long long)fnv1a(k_trace_src, fnv1a(k_core_src)));
-    return b;
-}
-
-// ... and its refinement kernels of adaptive supersampling: the core's text and rtc_adaptive.h's
-std::string aot_adaptive_kernel_id(uint32_t k) {
-    char b[56];
-    snprintf(b, sizeof(b), "aot_adaptive%u_%016llx", k, (unsigned long long)fnv1a(k_adaptive_src, fnv1a(k_core_src)));
-    return b;
 }
 
 }  // namespace
@@ -880,26 +763,17 @@ static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hi
     });
 }
 
-// A slot's kernel with a frame stack of at least `depth` levels.  The options are the slot's own (rtc_ctx_set_scene wrote them
-// down) plus -DRTC_SPEC_MAX_DEPTH; the recursion frames of such a kernel all live in per-lane scratch -- the LDS placement of the
-// first levels (a tuning of the depth-5 glass-and-mirror frame) is not carried over.  Always a scene-compiled kernel, whatever
-// RTC_AMD_SPECIALIZE says: the ahead-of-time kernels stop at RTC_STACK_DEPTH_BASE.
+// A slot's kernel with a frame stack of at least `depth` levels (rtc_scene_prep.h deep_variant of the slot's own).  Always a
+// scene-compiled kernel, whatever RTC_AMD_SPECIALIZE says: the ahead-of-time kernels stop at RTC_STACK_DEPTH_BASE.
 static rtc_status deep_kernel(rtc_ctx* c, int32_t depth, rtc_ctx::SceneKernel& s, hipFunction_t* out, std::string* out_id = nullptr) {
-    int cap = 2 * RTC_STACK_DEPTH_BASE;
-    while (cap < depth) cap *= 2;
-    if (cap > RTC_MAX_DEPTH) cap = RTC_MAX_DEPTH;
-    auto it = s.deep.find(cap);
+    auto it = s.deep.find(deep_stack_cap(depth));
     if (it == s.deep.end()) {
-        if (s.variant.defs.empty()) return fail(RTC_ERR_INVALID_ARG, "depth %d: no kernel options recorded for this scene", depth);
-        std::vector<std::string> defs;
-        for (const auto& d : s.variant.defs)
-            if (d.rfind("-DRTC_SPEC_LDS_FRAMES=", 0) != 0) defs.push_back(d);
-        defs.push_back("-DRTC_SPEC_MAX_DEPTH=" + std::to_string(cap));
+        KernelVariant deep;
+        RTC_TRY(deep_variant(s.variant, depth, &deep));
         hipFunction_t fn = nullptr;
         std::string id;
-        rtc_status st = jit_get(c->policy, c->device, defs, &fn, &id);
-        if (st != RTC_OK) return st;  // (the message is hiprtc's)
-        it = s.deep.emplace(cap, std::make_pair(fn, id)).first;
+        RTC_TRY(jit_get(c->policy, c->device, deep, &fn, &id));  // (the message is hiprtc's)
+        it = s.deep.emplace(deep_stack_cap(depth), std::make_pair(fn, id)).first;
     }
     *out = it->second.first;
     if (out_id) *out_id = it->second.second;
@@ -918,7 +792,7 @@ static rtc_status scene_kernel_for(rtc_ctx* c, rtc_ctx::SceneKernel& s, int32_t 
     if (depth > RTC_STACK_DEPTH_BASE) return deep_kernel(c, depth, s, fn, id);
     if (!want || failed) return RTC_OK;
     if (s.fn == nullptr) {
-        const rtc_status jst = jit_get(c->policy, c->device, s.variant.defs, &s.fn, &s.fn_id, lazy);
+        const rtc_status jst = jit_get(c->policy, c->device, s.variant, &s.fn, &s.fn_id, lazy);
         if (jst != RTC_OK) {
             s.fn = nullptr;
             failed = true;
@@ -937,7 +811,7 @@ static rtc_status scene_kernel_for(rtc_ctx* c, rtc_ctx::SceneKernel& s, int32_t 
 
 // The frame's kernel: compiled when the scene is set (or, lazy, when it comes again: compile_deferred), not by the first frame.
 // RTC_AMD_SPECIALIZE=1 and no kernel: the context has no scene.
-static std::string ctx_aot_id(const rtc_ctx* c) { return c->ss_k != 1u ? aot_ss_kernel_id(c->ss_k) : aot_kernel_id(); }
+static std::string ctx_aot_id(const rtc_ctx* c) { return aot_kernel_id(c->render.variant.kind, c->render.variant.k); }
 static rtc_status compile_render_kernel(rtc_ctx* c, bool lazy) {
     rtc_ctx::SceneKernel& r = c->render;
     hipFunction_t fn = nullptr;
@@ -1762,19 +1636,54 @@ rtc_status rtc_diag_scene_plan(const rtc_scene* scene, const rtc_camera* camera,
              p.scene_rect[3], (double)p.scene_rect_coverage, p.scene_tile_mask.size(), p.scene_tiles_w, p.scene_tiles_h, (int)p.spec_shares,
              (int)p.spec_blocks_y, (int)p.spec_rect, p.tree_waves, (int)p.wf_pays, (int)p.compile_now);
     std::string out = b;
-    auto add = [&](const std::string& prefix, const KernelVariant& v) {  // <prefix>family_name, <prefix>spec_name, <prefix>spec_defs
-        out += prefix + "family_name=" + v.family_name + "\n" + prefix + "spec_name=" + v.spec_name + "\n" + prefix + "spec_defs=";
-        for (size_t i = 0; i < v.defs.size(); i++) out += (i ? " " : "") + v.defs[i];
-        out += "\n";
+    // ... and what the JIT makes of every variant (rtc_jit.h), with this process's hiprtc and the embedded source
+    int major = 0, minor = 0;
+    (void)hiprtcVersion(&major, &minor);
+    const JitArgSizes sizes = {sizeof(RenderArgs), sizeof(TraceArgs), sizeof(AdaptiveRefineArgs)};
+    out += "hiprtc=" + std::to_string(major) + "." + std::to_string(minor) + "\nkey_tail=" + jit_key_tail(JitKind::RENDER, major, minor, sizes) +
+           "render_args=" + std::to_string(sizes.render) + "\ntrace_args=" + std::to_string(sizes.trace) + "\nadaptive_args=" + std::to_string(sizes.adaptive) + "\n";
+    auto joined = [](const std::vector<std::string>& defs) {
+        std::string line;
+        for (size_t i = 0; i < defs.size(); i++) line += (i ? " " : "") + defs[i];
+        return line + "\n";
     };
-    add("", render_variant(p));
-    add("trace_", trace_variant(p));
+    // <prefix>family_name, spec_name, spec_defs, entry, header, options (hiprtc's), cache_file, aot_id; `deep`: <prefix>deep16_spec_defs, deep16_cache_file, deep32_
+    // (a world without objects: <prefix>deep16_error = status and message)
+    auto add = [&](const std::string& prefix, const KernelVariant& v, bool deep = false) {
+        const JitKindFacts& kind = jit_kind_facts(v.kind);
+        out += prefix + "family_name=" + v.family_name + "\n" + prefix + "spec_name=" + v.spec_name + "\n" + prefix + "spec_defs=" + joined(v.defs);
+        const JitPlan jit = plan_jit(v.defs, v.kind, P.jit_flags, major, minor, sizes, k_core_src, beside_text(v.kind));
+        out += prefix + "entry=" + jit.entry + "\n" + prefix + "header=" + kind.header + "\n" + prefix + "options=" + joined(jit.opts) + prefix + "cache_file=" +
+               jit.cache_file + "\n" + prefix + "aot_id=" + aot_kernel_id(v.kind, v.k) + "\n";
+        for (int depth : {16, 32}) {
+            KernelVariant d;
+            if (!deep) continue;
+            const std::string name = prefix + "deep" + std::to_string(depth);
+            const rtc_status st = deep_variant(v, depth, &d);
+            if (st != RTC_OK) out += name + "_error=" + std::to_string((int)st) + " " + rtc_last_error() + "\n";
+            else out += name + "_spec_defs=" + joined(d.defs) + name + "_cache_file=" + plan_jit(d.defs, d.kind, P.jit_flags, major, minor, sizes, k_core_src, beside_text(d.kind)).cache_file + "\n";
+        }
+    };
+    add("", render_variant(p), true);
+    add("trace_", trace_variant(p), true);
     for (uint32_t k : {2u, 4u}) add("adaptive" + std::to_string(k) + "_", refine_variant(p, k));
     for (uint32_t k : {2u, 4u}) add("ss" + std::to_string(k) + "_", render_variant(p, k));  // (of this camera as the fine one)
     if (out.size() >= cap) return fail(RTC_ERR_INVALID_ARG, "rtc_diag_scene_plan: the text needs %zu bytes", out.size() + 1);
     std::memcpy(text, out.c_str(), out.size() + 1);
     return RTC_OK;
 }
+
+// rtc_jit.h's cache entries and rtc_scene_prep.h's stack cap, as they are (tests/test_jit_plan.py).  _read: the code's length, or -1.
+int32_t rtc_diag_jit_cache_publish(const char* dir, const char* file, const void* bytes, uint64_t n) {
+    return publish_cache_entry(dir, std::string(dir) + "/" + file, std::string((const char*)bytes, (size_t)n)) ? 1 : 0;
+}
+int64_t rtc_diag_jit_cache_read(const char* path, void* out, uint64_t cap) {
+    std::string code;
+    if (!read_cache_entry(path, &code)) return -1;
+    if (out) std::memcpy(out, code.data(), std::min<size_t>(code.size(), (size_t)cap));
+    return (int64_t)code.size();
+}
+int32_t rtc_diag_deep_stack_cap(int32_t depth) { return deep_stack_cap(depth); }
 
 rtc_status rtc_ctx_render(rtc_ctx* c, int32_t depth, const rtc_partition* part, void* d_out_rgb, void* stream) {
     return rtc::ctx_render_slot(c, depth, part, d_out_rgb, stream, 0u);
@@ -1864,7 +1773,7 @@ static rtc_status trace_launch(rtc_ctx* c, int32_t depth, const void* d_origins,
     std::string id;
     RTC_TRY(scene_kernel_for(c, t.kernel, depth, want, false, t.kernel.failed, t.kernel.note, "tracing with", true, &fn, &id));
     t.name = fn ? t.kernel.variant.spec_name : t.kernel.variant.family_name;
-    t.id = fn ? id : aot_trace_kernel_id();
+    t.id = fn ? id : aot_kernel_id(JitKind::TRACE);
     // workspaces (grow-only; a trace in flight on this stream may still be writing the old partials: grow frees, which waits)
     const uint32_t n_workgroups = (uint32_t)(((uint64_t)n + 255u) / 256u);
     const size_t n_counts = (size_t)n_workgroups * 4u;
@@ -2256,7 +2165,7 @@ rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float 
     HIP_TRY(hipEventRecord(ad.ev[2], stream));
     // (named once it has been launched: a call that failed on the way names no kernel it did not run)
     ad.name = fn ? slot.variant.spec_name : slot.variant.family_name;
-    ad.id = fn ? id : aot_adaptive_kernel_id(k);
+    ad.id = fn ? id : aot_kernel_id(JitKind::ADAPTIVE, k);
     ad.ran = true;
     return RTC_OK;
 }

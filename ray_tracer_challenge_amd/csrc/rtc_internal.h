@@ -4,6 +4,7 @@
 #define RTC_INTERNAL_H
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 
 #include "rtc.h"
@@ -11,6 +12,15 @@
 namespace rtc {
 
 rtc_status fail(rtc_status code, const char* fmt, ...);
+
+// 64-bit FNV-1a, continued from `h`: the digests of rtc_diag_scene_plan, and the JIT's keys, checksums and ids (rtc_jit.h)
+inline uint64_t fnv1a(const void* data, size_t n, uint64_t h = 1469598103934665603ull) {
+    for (size_t i = 0; i < n; i++) {
+        h ^= ((const unsigned char*)data)[i];
+        h *= 1099511628211ull;
+    }
+    return h;
+}
 
 // matrix.rs:163-182 -- drop one row and one column of a row-major NxN matrix
 template <int N>

@@ -1,8 +1,8 @@
 // rtc_scene_prep.h -- getting a scene ready, on the host: rtc_scene + rtc_camera become the kernel's header and records
 // (flatten and its stages: object records, triangle pre-culling boxes, the traversal stream, scene box and region, light,
 // camera), and the resident records decide which kernel renders them (plan_scene: tile coverages, scene rectangle, the
-// option list and name of the scene's kernel; render_variant / trace_variant / refine_variant: those of the supersampling, ray-stream
-// and refinement kernels derived from it).  This is where the arguments of ERROR_BUDGET.md (B6, B7, B8, B10, E1, E2)
+// option list and name of the scene's kernel; render_variant / trace_variant / refine_variant / deep_variant: those of the
+// supersampling, ray-stream, refinement and deep-recursion kernels derived from it).  This is where the arguments of ERROR_BUDGET.md (B6, B7, B8, B10, E1, E2)
 // become numbers.  No device, no context: rtc_device.hip's rtc_ctx_set_scene uploads what flatten packed and copies a
 // ScenePlan into the context; tests/test_scene_prep.py reaches both through rtc_diag_scene_plan.
 // Included after rtc_kernel_core.h (SceneHdr, SceneSoA, the SHAPE_* / TRAV_* constants).
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "rtc_internal.h"
+#include "rtc_jit.h"
 
 namespace rtc {
 
@@ -39,13 +40,6 @@ inline float float_of(uint32_t u) {
     float f;
     std::memcpy(&f, &u, 4);
     return f;
-}
-inline uint64_t fnv1a(const void* data, size_t n, uint64_t h = 1469598103934665603ull) {
-    for (size_t i = 0; i < n; i++) {
-        h ^= ((const unsigned char*)data)[i];
-        h *= 1099511628211ull;
-    }
-    return h;
 }
 
 inline uint32_t padded_count(uint32_t n) { return n ? (n + 7u) & ~7u : 8u; }
@@ -1472,6 +1466,7 @@ struct ScenePlan {
     // without objects), its name, and `compile_now`: does the policy want the scene-compiled kernel for ordinary depths.
     std::vector<std::string> spec_defs;
     std::string spec_name;
+    uint32_t ss_k = 1u;  // the frame's kernel is the supersampling one of this factor (plan_supersampled)
     bool compile_now = false;
     // ... and the policy's two exceptions to "from 2^18 pixels", which rtc_ctx_trace applies to its number of rays: worlds with divided
     // meshes are compiled whatever the size, a mixed list of many objects (and a world without objects) never
@@ -1756,12 +1751,15 @@ inline ScenePlan plan_scene(const Policy& P, const SceneHdr& hdr, const std::vec
 
 // ---- kernel variants ---------------------------------------------------------------------------------------------------
 // One kernel of a scene: the options it is compiled with -- in order: jit_get hashes them into the cache key and the kernel id;
-// empty: a world without objects -- and the names of the ahead-of-time family and of the scene's own kernel.  The plan's
-// spec_defs / family_name / spec_name are the frame's kernel; the functions below derive every other kernel a context keeps
-// from it, and nothing else rewrites an option or a name.
+// empty: a world without objects --, the names of the ahead-of-time family and of the scene's own kernel, and which of the four
+// kernels it is (rtc_jit.h: entry point, the header beside the core; `k`: the factor of a supersampling or refinement kernel).
+// The plan's spec_defs / family_name / spec_name / ss_k are the frame's kernel; the functions below derive every other kernel a
+// context keeps from it, and nothing else rewrites an option or a name.
 struct KernelVariant {
     std::vector<std::string> defs;
     std::string family_name, spec_name;
+    JitKind kind = JitKind::RENDER;
+    uint32_t k = 1u;
 };
 // the launch shapes a variant does not have ("-DRTC_SPEC_RECT=" ...), off in its key
 inline void switch_off(std::vector<std::string>* defs, std::initializer_list<const char*> options) {
@@ -1780,8 +1778,9 @@ inline std::string with_prefix(const std::string& name, const char* from, const 
 // The frame's kernel of a context of factor k (rtc_supersample.h; 1: the plan's own): ss_render_kernel<...;ss=k>.  The
 // supersampling body has neither the loop over blocks nor the rectangle's offsets.
 inline KernelVariant render_variant(const ScenePlan& p, uint32_t k = 1u) {
-    KernelVariant v = {p.spec_defs, p.family_name, p.spec_name};
+    KernelVariant v = {p.spec_defs, p.family_name, p.spec_name, p.ss_k == 1u ? JitKind::RENDER : JitKind::SS, p.ss_k};
     if (k == 1u) return v;
+    v.kind = JitKind::SS, v.k = k;
     for (std::string* name : {&v.family_name, &v.spec_name})
         if (!name->empty()) *name = "ss_" + with_factor(*name, k);
     if (!v.defs.empty()) {
@@ -1794,7 +1793,7 @@ inline KernelVariant render_variant(const ScenePlan& p, uint32_t k = 1u) {
 // its kernel must not depend on the size of a frame it does not draw.  (Of the plan before plan_supersampled: color_at does not
 // read the camera, so a plain and a supersampled context trace with one kernel.)
 inline KernelVariant trace_variant(const ScenePlan& p) {
-    KernelVariant v = {p.spec_defs, with_prefix(p.family_name, "render_", "trace_"), with_prefix(p.spec_name, "render_", "trace_")};
+    KernelVariant v = {p.spec_defs, with_prefix(p.family_name, "render_", "trace_"), with_prefix(p.spec_name, "render_", "trace_"), JitKind::TRACE};
     switch_off(&v.defs, {"-DRTC_SPEC_BLOCKS_Y=", "-DRTC_SPEC_RECT=", "-DRTC_SPEC_SHARE="});
     if (!v.defs.empty()) v.defs.push_back("-DRTC_SPEC_TRACE=1");
     return v;
@@ -1806,14 +1805,32 @@ inline KernelVariant refine_variant(const ScenePlan& p, uint32_t k) {
     v.family_name = with_factor(with_prefix(v.family_name, "trace_", "adaptive_refine_"), k);
     v.spec_name = with_factor(with_prefix(v.spec_name, "trace_", "adaptive_refine_"), k);
     if (!v.defs.empty()) v.defs.back() = "-DRTC_SPEC_ADAPTIVE=" + std::to_string(k);
+    v.kind = JitKind::ADAPTIVE, v.k = k;
     return v;
+}
+// A variant with a frame stack of at least `depth` levels, for recursion deeper than RTC_STACK_DEPTH_BASE: 16, 32, ... up to
+// RTC_MAX_DEPTH (deep_stack_cap), -DRTC_SPEC_MAX_DEPTH=<cap> last.  The recursion frames of such a kernel all live in per-lane
+// scratch -- the LDS placement of the first levels (a tuning of the depth-5 glass-and-mirror frame) is not carried over.
+inline int deep_stack_cap(int depth) {
+    int cap = 2 * RTC_STACK_DEPTH_BASE;
+    while (cap < depth) cap *= 2;
+    return std::min(cap, RTC_MAX_DEPTH);
+}
+inline rtc_status deep_variant(const KernelVariant& v, int depth, KernelVariant* deep) {
+    if (v.defs.empty()) return fail(RTC_ERR_INVALID_ARG, "depth %d: no kernel options recorded for this scene", depth);
+    *deep = v;
+    deep->defs.clear();
+    for (const auto& d : v.defs)
+        if (d.rfind("-DRTC_SPEC_LDS_FRAMES=", 0) != 0) deep->defs.push_back(d);
+    deep->defs.push_back("-DRTC_SPEC_MAX_DEPTH=" + std::to_string(deep_stack_cap(depth)));
+    return RTC_OK;
 }
 // The plan of a supersampled context, k = 2, 4 (`p`: plan_scene of the FINE camera).  Scene tiles, the scene rectangle and several
 // blocks per workgroup address the canvas by fine pixels and are not carried over: such scenes are a plain grid, where the
 // scene-box early-out still applies; nor is the level-by-level renderer.
 inline void plan_supersampled(ScenePlan* p, uint32_t k) {
     const KernelVariant v = render_variant(*p, k);
-    p->spec_defs = v.defs, p->family_name = v.family_name, p->spec_name = v.spec_name;
+    p->spec_defs = v.defs, p->family_name = v.family_name, p->spec_name = v.spec_name, p->ss_k = k;
     p->scene_tile_mask.clear();
     p->scene_rect[0] = p->scene_rect[1] = p->scene_rect[2] = p->scene_rect[3] = 0u;
     p->spec_blocks_y = p->spec_rect = false;
