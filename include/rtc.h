@@ -35,7 +35,8 @@ extern "C" {
                              adaptive supersampling: rtc_ctx_render_adaptive, rtc_ctx_adaptive_stats, rtc_ctx_adaptive_kernel_name
                              / _id and the struct rtc_adaptive_stats are additions, nothing that existed has moved;
                              ray reordering: rtc_ctx_ray_order, rtc_ctx_trace_reordered, rtc_ctx_reorder_stats and the struct
-                             rtc_reorder_stats, additions likewise) */
+                             rtc_reorder_stats, additions likewise; supersampling through the one-call seam: rtc_render_ss, one
+                             entry point more -- rtc_opts and rtc_stats are what they were) */
 /* reflection_recursion_depth (camera.rs:76: any i16; reference default 5, constants.rs:4; its author renders
  * reflect_refract at 20).  Accepted: 0 .. RTC_MAX_DEPTH.  The kernels keep one frame per suspended shade_hit
  * (world.rs:62-86); up to RTC_STACK_DEPTH_BASE levels every kernel has them, above that the scene's kernel is compiled
@@ -346,7 +347,26 @@ rtc_status rtc_render(const rtc_scene* scene, const rtc_camera* camera, int32_t 
  * RTC_AMD_SPECIALIZE=1 compiles at first sight, =0 never; the persistent contexts below (rtc_ctx_set_scene) always compile at once. */
 rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, const rtc_opts* opts,
                          void* out, rtc_stats* stats);
-/* Frees everything rtc_render / rtc_render_ex keep between calls (all devices). */
+/* rtc_render_ex with k x k rays per pixel of `output_camera` (W x H), reduced inside the render kernel: the frame that
+ * rtc_ctx_set_scene_ss defines (below: the fixed-order f32 box filter of the fine camera's frame, jitter keys from the fine pixel
+ * index, last row and column dimmed), in one call, with everything rtc_render_ex offers -- `out` is H x W x 3 f32, or bytes with
+ * opts->quantize (scale_color of the reduced colour), host memory (pageable or page-locked) or device memory
+ * (opts->out_on_device); the rows leave chunk by chunk while later rows render; opts->band_rows counts OUTPUT rows (0 -> 64) and
+ * the bands are dealt round-robin over opts->devices (a device may be listed several times, and may own no row).  The fine
+ * frame never exists in memory and never crosses the link: a call moves 1 / k^2 of what rtc_render_ex of the fine camera moves.
+ * k = 1 is rtc_render_ex; k = 2 or 4; any other k, or a fine frame rtc_camera_supersampled refuses, is RTC_ERR_INVALID_ARG with
+ * a message, decided on the host before any device call, in the order rtc_render_ex checks its arguments (null `out` or camera,
+ * empty canvas, then k).  The per-device state is rtc_render_ex's own: calls with k = 1, 2, 4 of one scene may alternate, each
+ * gives its own frame (another factor is another kernel: the scene is planned again, its records stay resident), and
+ * rtc_render_release frees it.  Its contexts launch a variant of the supersampling kernels of their own (bytes, write-through stores,
+ * progress words; named "ss_seam_render_kernel<...;ss=k>" / "ss_render_kernel_spec[...;ss=k;seam]", ids "aot_ss<k>_<hash>.seam" /
+ * "spec_..."), never the kernels of rtc_ctx_set_scene_ss's contexts.  A launch drawn from a block list (a divided mesh under a point light) cannot report its rows:
+ * its chunks leave when its stream is done, as in rtc_render_ex.  stats: rays, shaded_hits and pixels are the fine frame's
+ * ((k W - 1)(k H - 1) pixels), summed over the devices; rows = H; launches = one per entry of opts->devices that owns a row,
+ * however many chunks its rows leave in; kernel_ms and gather_ms as for rtc_render_ex. */
+rtc_status rtc_render_ss(const rtc_scene* scene, const rtc_camera* output_camera, int32_t depth, uint32_t k,
+                         const rtc_opts* opts, void* out, rtc_stats* stats);
+/* Frees everything rtc_render / rtc_render_ex / rtc_render_ss keep between calls (all devices). */
 void rtc_render_release(void);
 /* Page-locked host memory (hipHostMalloc): an `out` buffer allocated here is filled by DMA straight from the device. */
 void* rtc_host_alloc(size_t bytes);
@@ -380,7 +400,7 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* ctx, const rtc_scene* scene, const rtc_cam
  * "aot_ss<k>_..." or "spec_..." ids of their own).  The rules of rtc_ctx_set_scene hold: unchanged records are not uploaded,
  * a scene of the same frame size and factor keeps the schedule.  A later rtc_ctx_set_scene leaves supersampled mode.
  * rtc_ctx_render_hits on a supersampled context is RTC_ERR_UNSUPPORTED (a first hit per output pixel is not defined).
- * rtc_render / rtc_render_ex (the one-call seam, its progress words and u8 frames) do not supersample. */
+ * The one-call seam supersamples through rtc_render_ss (above): the same frame, f32 or bytes, host buffer out, several devices. */
 rtc_status rtc_ctx_set_scene_ss(rtc_ctx* ctx, const rtc_scene* scene, const rtc_camera* output_camera, uint32_t k);
 /* Rows this partition produces (sum of its bands' heights). */
 uint32_t rtc_partition_rows(uint32_t height, const rtc_partition* part);

@@ -480,6 +480,19 @@ struct Camera {
         check(rtc_render_ex(&scene, &c, reflection_recursion_depth, &opts, canvas.data.data(), &last_stats));
         return canvas;
     }
+    // ... and antialiased: k x k rays per pixel (k = 1, 2 or 4) reduced inside the render kernel (rtc_render_ss) -- the canvas is
+    // this camera's width x height, the box filter of the frame Camera(k * width, k * height, fov, transform) renders
+    Canvas render_supersampled(World world, int16_t reflection_recursion_depth, uint32_t k, const std::vector<int32_t>& devices = {0}) {
+        std::vector<rtc_object> objs;
+        std::vector<rtc_group> groups;
+        for (Shape& s : world.objects) flatten(s, objs, groups);
+        rtc_scene scene{(uint32_t)objs.size(), objs.data(), world.light ? &world.light->l : nullptr,
+                        (uint32_t)groups.size(), groups.data()};
+        rtc_opts opts{devices.data(), (uint32_t)devices.size(), 0u, 0, 0};
+        Canvas canvas(c.width, c.height);
+        check(rtc_render_ss(&scene, &c, reflection_recursion_depth, k, &opts, canvas.data.data(), &last_stats));
+        return canvas;
+    }
 };
 
 constexpr float PI = 3.14159265358979323846264338327950288f;  // std::f32::consts::PI

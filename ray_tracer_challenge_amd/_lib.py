@@ -161,6 +161,8 @@ SIGNATURES = {
                              C.POINTER(rtc_stats)]),
     "rtc_render_ex": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.POINTER(rtc_opts), C.c_void_p,
                                 C.POINTER(rtc_stats)]),
+    "rtc_render_ss": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.c_uint32, C.POINTER(rtc_opts), C.c_void_p,
+                                C.POINTER(rtc_stats)]),
     "rtc_render_release": (None, []),
     "rtc_host_alloc": (C.c_void_p, [C.c_size_t]),
     "rtc_host_free": (None, [C.c_void_p]),
@@ -258,6 +260,10 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
          "rtc_diag_scene_tile_mask": (C.c_uint32, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]),
          "rtc_diag_ctx_scene_tiles": (None, [C.c_void_p, C.POINTER(rtc_partition), C.POINTER(C.c_uint32)]),
          "rtc_diag_seam_ctx": (C.c_void_p, [C.c_uint32]),
+         # the one-call seam supersampled: a reporting launch's chunks in output rows, and whether an entry's last launch reported
+         # (tests/test_seam_supersample_boundary.py, tests/test_gpu_seam_supersample.py)
+         "rtc_diag_ss_chunks": (C.c_int32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32)]),
+         "rtc_diag_seam_progress": (C.c_int32, [C.c_uint32, C.POINTER(C.c_uint32)]),
          # the packed work counter's capacity: does a launch count a light's culled shadow rays, or run with the culls off (tests/test_light_grid_limits.py)
          "rtc_diag_culled_count_fits": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32])}
 

@@ -161,6 +161,9 @@ struct rtc_ctx {
     // (row-major bitmap, empty: no block list), and the list last built -- for the partition it was built for
     int tree_waves = 6;  // waves per SIMD the scene's tree kernel was compiled for (rtc_ctx_set_scene)
     bool lazy_jit = false;      // a context of the one-call seam (rtc::ctx_mark_one_shot): see jit_get
+    // ... and what else such a context is: supersampled, its kernels are the variant that stores bytes and reports its rows
+    // (rtc_supersample.h SEAM: ss_seam_render_kernel<...>, -DRTC_SPEC_SS_SEAM=1), and ctx_render_slot accepts out_u8 / progress
+    bool seam_kernels = false;
     bool jit_deferred = false;  // the resident scene's kernel was left uncompiled by its first sighting: the next render of this scene compiles it
     std::vector<uint8_t> heavy_tiles;
     uint32_t heavy_w = 0, heavy_h = 0;
@@ -751,7 +754,10 @@ static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hi
         sa.out_width = a.hdr.width / c->ss_k, sa.out_rows = a.rows / c->ss_k;
         return launch_scene_kernel(spec_fn, grid, stream, sa, [&] {
             dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
-                if (c->ss_k == 2u) hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
+                // (a context of the one-call seam launches the variant that stores bytes and reports its rows: rtc_supersample.h SEAM)
+                if (c->seam_kernels && c->ss_k == 2u) hipLaunchKernelGGL((ss_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
+                else if (c->seam_kernels) hipLaunchKernelGGL((ss_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, sa);
+                else if (c->ss_k == 2u) hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
                 else hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, sa);
             });
         });
@@ -811,7 +817,10 @@ static rtc_status scene_kernel_for(rtc_ctx* c, rtc_ctx::SceneKernel& s, int32_t 
 
 // The frame's kernel: compiled when the scene is set (or, lazy, when it comes again: compile_deferred), not by the first frame.
 // RTC_AMD_SPECIALIZE=1 and no kernel: the context has no scene.
-static std::string ctx_aot_id(const rtc_ctx* c) { return aot_kernel_id(c->render.variant.kind, c->render.variant.k); }
+// (the one-call seam's variant of the supersampling kernels is a code object of its own: "aot_ss<k>_<hash>.seam")
+static std::string ctx_aot_id(const rtc_ctx* c) {
+    return aot_kernel_id(c->render.variant.kind, c->render.variant.k) + (c->seam_kernels && c->render.variant.kind == JitKind::SS ? ".seam" : "");
+}
 static rtc_status compile_render_kernel(rtc_ctx* c, bool lazy) {
     rtc_ctx::SceneKernel& r = c->render;
     hipFunction_t fn = nullptr;
@@ -891,7 +900,7 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     // that wants the scene's kernel compiles it
     c->trace.kernel.reset(trace_variant(plan));
     for (uint32_t i = 0; i < 2u; i++) c->adaptive.kernel[i].reset(refine_variant(plan, i ? 4u : 2u));
-    if (k != 1u) plan_supersampled(&plan, k);
+    if (k != 1u) plan_supersampled(&plan, k, c->seam_kernels);
     c->hdr = hdr;
     c->camera = *camera;
     c->ss_k = k;
@@ -1376,7 +1385,10 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     const uint32_t ss_k = c->ss_k;
     rtc_partition fine_part;
     if (ss_k != 1u) {
-        if (progress || out_u8) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render: a supersampled context renders f32 frames without progress words");
+        // progress words and the u8 canvas (rtc_render_ss): the plain grid reports, a block-list launch is finished when its stream
+        // is.  Only the kernels of the one-call seam's contexts have those paths (rtc_supersample.h SEAM).
+        if ((progress || out_u8) && !c->seam_kernels)
+            return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render: a supersampled context renders f32 frames without progress words (bytes and progress words: rtc_render_ss)");
         const Partition o = resolve(part);
         if (o.band_rows > 0xffffffffu / ss_k) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: band_rows %u times the supersampling factor %u", o.band_rows, ss_k);
         fine_part.band_rows = o.band_rows * ss_k, fine_part.n_parts = o.n_parts, fine_part.part = o.part;
@@ -1435,14 +1447,18 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
         const size_t words = lp.progress_words(PROGRESS_STRIDE);
         HIP_TRY(grow(&c->d_progress, &c->progress_cap, words));
         HIP_TRY(hipMemsetAsync(c->d_progress, 0, words * sizeof(uint32_t), stream));
+        // (the counters are the FINE grid's, one per block row of lp.grid_y; the caller's rows are output rows)
+        uint32_t chunk_rows = 0u;
+        if (!chunk_output_rows(lp, ss_k, &chunk_rows))
+            return fail(RTC_ERR_DEVICE, "rtc_ctx_render: chunks of %u blocks of %u fine rows do not end between output rows (factor %u)", lp.chunk_block_rows, lp.block_h, ss_k);
         progress->n_chunks = lp.n_chunks;
-        progress->chunk_rows = lp.chunk_block_rows * lp.block_h;
+        progress->chunk_rows = chunk_rows;
     }
     RenderArgs a = render_args(c, q, rows, depth, share_log2, d_out_rgb, out_u8, total, progress, lp, L);
     // ---- warm up, time, launch, sum
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     HIP_TRY(next_event_pair(c, &ev));
-    RTC_TRY(warm_up(c->render, spec_fn ? (const void*)spec_fn : aot_family(c).key(ss_k), stream, [&] {
+    RTC_TRY(warm_up(c->render, spec_fn ? (const void*)spec_fn : aot_family(c).key(ss_k, ss_k != 1u && c->seam_kernels), stream, [&] {
         RenderArgs w = a;
         w.rows = 0u, w.tiles = nullptr, w.wave_ticks = nullptr, w.progress = nullptr, w.done = nullptr, w.fill_wg_rows = 0u, w.swizzle = 0u, w.blocks_y = 1u;
         return launch_render(c, spec_fn, dim3(1, 1), stream, w);
@@ -1469,7 +1485,7 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
 // After the caller has synchronised with every launch: counters summed over slots [0, n_slots), kernel_ms = the SUM
 // of the launches' HIP-event times since the last stats call (the launches of one frame run back to back).
 void rtc::ctx_mark_one_shot(rtc_ctx* c) {
-    if (c) c->lazy_jit = true;
+    if (c) c->lazy_jit = c->seam_kernels = true;
 }
 
 rtc_status rtc::ctx_collect(rtc_ctx* c, uint32_t n_slots, rtc_stats* out) {
@@ -1607,6 +1623,18 @@ uint32_t rtc_diag_ss_plan(uint32_t k, uint32_t share_log2, const uint32_t* list,
     for (size_t i = 0; out && i < made.size() && i < cap; i++) out[i] = made[i];
     if (n_out) *n_out = (uint32_t)made.size();
     return s;
+}
+// The progress chunks of a supersampled launch that reports (rtc_render_ss; tests/test_seam_supersample_boundary.py): a partition of
+// out_rows rows of out_width output pixels at factor k, the frame's own choice of lanes per pixel share_log2 (capped as the launch caps
+// it), swizzled or not, want_chunks asked for.  out = {grid_x, grid_y, block_h, chunk_block_rows, n_chunks, chunk rows in OUTPUT rows,
+// lanes per pixel (log2) planned with, PROGRESS_MAX_CHUNKS}; -> 1 when a chunk is a whole number of output rows, else 0.
+int32_t rtc_diag_ss_chunks(uint32_t out_width, uint32_t out_rows, uint32_t k, uint32_t share_log2, int32_t swizzle, uint32_t want_chunks, uint32_t out[8]) {
+    const LaunchPlan lp = plan_ss_chunks(out_width, out_rows, k, share_log2, swizzle != 0, want_chunks, PROGRESS_MAX_CHUNKS);
+    uint32_t chunk_rows = 0u;
+    const bool whole = chunk_output_rows(lp, k, &chunk_rows);
+    const uint32_t v[8] = {lp.grid_x, lp.grid_y, lp.block_h, lp.chunk_block_rows, lp.n_chunks, chunk_rows, std::min(share_log2, ss_max_share_log2(k)), PROGRESS_MAX_CHUNKS};
+    std::memcpy(out, v, sizeof(v));
+    return whole ? 1 : 0;
 }
 
 // A scene's preparation on the host, under the environment's policy (as rtc_scene_validate): flatten, then plan_scene.

@@ -88,6 +88,7 @@ constexpr uint32_t CTX_TOTAL_SLOTS = 64;
 // Progress reporting of one launch (RenderArgs::progress): in -- where the host words live, how many chunks the caller
 // would like, this frame's epoch; out -- how the launch's rows were cut (n_chunks == 0: this launch cannot report -- a
 // block list, a scene rectangle, several blocks per workgroup -- and the caller waits for the stream instead).
+// A supersampled context (rtc_render_ss): the rows are the caller's, OUTPUT rows -- rtc_launch_plan.h chunk_output_rows.
 struct ProgressPlan {
     uint32_t* d_done;      // device-visible address of the page-locked host words, one per chunk (>= PROGRESS_MAX_CHUNKS)
     uint32_t want_chunks, epoch;

@@ -403,6 +403,27 @@ inline void plan_chunks(LaunchPlan* p, uint32_t want_chunks, uint32_t max_chunks
     if (p->swizzle) p->chunk_block_rows = (p->chunk_block_rows + 3u) & ~3u;  // (block rows finish four at a time)
     p->n_chunks = (p->grid_y + p->chunk_block_rows - 1u) / p->chunk_block_rows;
 }
+// ... and what a chunk is to the caller of a supersampled launch (rtc_render_ss), whose buffer holds OUTPUT rows: the plan is the
+// fine frame's, a chunk is chunk_block_rows blocks of block_h fine rows, k fine rows make an output row.  block_h is 16, 8 or 4
+// and never below k -- the lanes per pixel are capped by ss_max_share_log2(k): k = 4 stops at 8 x 4 tiles, blocks of 8 rows -- so
+// the division is exact and a chunk ends between two output rows.  false: it would not be (the caller asserts; k = 1: as it is).
+inline bool chunk_output_rows(const LaunchPlan& p, uint32_t k, uint32_t* out_rows) {
+    *out_rows = 0u;
+    if (k == 0u) return false;
+    const uint64_t fine = (uint64_t)p.chunk_block_rows * p.block_h;
+    *out_rows = (uint32_t)(fine / k);
+    return fine % k == 0u && fine / k <= 0xffffffffull;
+}
+// The progress chunks of a supersampled partition of `out_rows` rows of `out_width` output pixels, as ctx_render_slot plans them
+// for the plain regular grid (tests/test_seam_supersample_boundary.py through rtc_diag_ss_chunks): the fine grid at
+// min(share_log2, cap) lanes per pixel, padded where it is swizzled, cut by plan_chunks.
+inline LaunchPlan plan_ss_chunks(uint32_t out_width, uint32_t out_rows, uint32_t k, uint32_t share_log2, bool swizzle, uint32_t want_chunks,
+                                 uint32_t max_chunks) {
+    LaunchPlan p = plan_grid(out_width * std::max(k, 1u), out_rows * std::max(k, 1u), std::min(share_log2, ss_max_share_log2(k)), false, 0u);
+    if (swizzle) p.pad_for_swizzle();
+    plan_chunks(&p, want_chunks, max_chunks);
+    return p;
+}
 
 }  // namespace rtc
 

@@ -1,4 +1,5 @@
-// rtc_oneshot.hip -- Camera::render (camera.rs:76-91) in ONE call, host buffer out: rtc_render / rtc_render_ex.
+// rtc_oneshot.hip -- Camera::render (camera.rs:76-91) in ONE call, host buffer out: rtc_render / rtc_render_ex, and rtc_render_ss,
+// the same call with k x k rays per pixel (the frame rtc_ctx_set_scene_ss defines; bands, chunks and staging count output rows).
 //
 // What a caller of the reference's seam pays for is the whole call, not the kernel: context, scene upload, kernel
 // compile, output allocation, the kernel, and 201 MB (4096^2 f32) back over PCIe.  Everything that can be kept between
@@ -139,6 +140,8 @@ struct DevState {
     uint32_t* h_done = nullptr;  // page-locked host words the render kernel reports finished chunks in (RenderArgs::done)
     uint32_t* d_done = nullptr;  // ... as the device addresses them
     uint32_t epoch = 0;          // this call's value of a finished chunk's word
+    bool last_reported = false;  // the last call's launch on this entry reported its chunks (rtc_diag_seam_progress)
+    uint32_t last_chunks = 0;    // ... and how many chunks its share had
 
     void release() {
         if (device < 0) return;
@@ -235,10 +238,28 @@ rtc_ctx* rtc_diag_seam_ctx(uint32_t k) {
     return k < g_state.size() ? g_state[k].ctx : nullptr;
 }
 
-rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, const rtc_opts* opts, void* out,
-                         rtc_stats* stats) {
+// ... and whether that entry's launch of the last call reported its rows chunk by chunk, and how many chunks its share had
+// (tests/test_gpu_seam_supersample.py: a launch that silently fell back to "finished when the stream is" gives the same frame).
+// out = {reported, chunks}; -> 0: no such entry.
+int32_t rtc_diag_seam_progress(uint32_t k, uint32_t out[2]) {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    out[0] = out[1] = 0u;
+    if (k >= g_state.size() || g_state[k].device < 0) return 0;
+    out[0] = g_state[k].last_reported ? 1u : 0u, out[1] = g_state[k].last_chunks;
+    return 1;
+}
+
+// rtc_render_ex (ss = 1) and rtc_render_ss (ss = 2, 4: `camera` is the OUTPUT camera; W, H, rows, bands, chunks and staging below
+// are the output's -- the fine frame exists only inside the contexts, rtc_ctx_set_scene_ss).
+static rtc_status render_seam(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, uint32_t ss, const rtc_opts* opts, void* out,
+                              rtc_stats* stats) {
     if (!out || !camera) return fail(RTC_ERR_INVALID_ARG, "rtc_render: null argument");
     if (camera->width == 0 || camera->height == 0) return fail(RTC_ERR_INVALID_ARG, "empty canvas");
+    rtc_camera fine = *camera;
+    if (ss != 1u) {  // host only: answered on a machine without a device
+        if (ss != 2u && ss != 4u) return fail(RTC_ERR_INVALID_ARG, "rtc_render_ss: supersampling factor %u: 1, 2 or 4 rays per pixel side", ss);
+        RTC_TRY(rtc_camera_supersampled(camera, ss, &fine));
+    }
     const int32_t dev0 = 0;
     const int32_t* devices = (opts && opts->devices && opts->n_devices) ? opts->devices : &dev0;
     const uint32_t D = (opts && opts->devices && opts->n_devices) ? opts->n_devices : 1u;
@@ -310,7 +331,8 @@ rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32
             std::memset(S.h_done, 0, PROGRESS_MAX_CHUNKS * sizeof(uint32_t));
             S.epoch = 1u;
         }
-        RTC_TRY(rtc_ctx_set_scene(S.ctx, scene, camera));  // a no-op when this very scene is resident already
+        // (a no-op when this very scene is resident already, at this factor)
+        RTC_TRY(ss == 1u ? rtc_ctx_set_scene(S.ctx, scene, camera) : rtc_ctx_set_scene_ss(S.ctx, scene, camera, ss));
         rtc_partition part = {band_rows, D, k};
         sh.rows = rtc_partition_rows(H, &part);
         for_each_band(H, resolve(&part), [&](uint32_t y0, uint32_t y1, uint32_t local0) {
@@ -328,6 +350,7 @@ rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32
         plan.n_chunks = plan.chunk_rows = 0u;
         RTC_TRY(ctx_render_slot(S.ctx, depth, &part, S.d_out, S.s_render, 0u, &plan, quantize));
         sh.reports = plan.n_chunks != 0u;
+        S.last_reported = sh.reports, S.last_chunks = 0u;
         if (sh.reports) {
             sh.n_chunks = sh.rows == 0u ? 0u : plan.n_chunks;
             sh.chunk_rows = plan.chunk_rows;
@@ -340,6 +363,7 @@ rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32
             sh.chunk_rows = sh.rows == 0u ? 0u : (sh.rows + want - 1u) / want;
             sh.n_chunks = sh.rows == 0u ? 0u : (sh.rows + sh.chunk_rows - 1u) / sh.chunk_rows;
         }
+        S.last_chunks = sh.n_chunks;
         if (staged && sh.rows) {
             const size_t need = (size_t)std::min(sh.rows, sh.chunk_rows) * row_out;
             if (need > S.stage_cap) {
@@ -495,7 +519,7 @@ rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32
         total.launches += s.launches;
         total.flags |= s.flags;
     }
-    total.pixels = (uint64_t)(W - 1) * (H - 1);
+    total.pixels = (uint64_t)(fine.width - 1) * (fine.height - 1);  // (supersampled: the fine frame's, as rays and shaded_hits are)
     total.rows = H;
     total.gather_ms = (float)wall_ms;
     if (stats) *stats = total;
@@ -506,6 +530,16 @@ rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32
 #endif
     drain.ok = true;
     return RTC_OK;
+}
+
+rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, const rtc_opts* opts, void* out,
+                         rtc_stats* stats) {
+    return render_seam(scene, camera, depth, 1u, opts, out, stats);
+}
+
+rtc_status rtc_render_ss(const rtc_scene* scene, const rtc_camera* output_camera, int32_t depth, uint32_t k, const rtc_opts* opts,
+                         void* out, rtc_stats* stats) {
+    return render_seam(scene, output_camera, depth, k, opts, out, stats);
 }
 
 rtc_status rtc_render(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, int32_t device, float* out_rgb,

@@ -1331,7 +1331,8 @@ struct KernelFamily {
     int nobj;  // -1, 4, 8, 0
     bool simple;
     // (no code object's address; ss_k: the supersampling instantiations of the family, rtc_supersample.h, are kernels of their own)
-    const void* key(uint32_t ss_k = 1u) const { return (const void*)(uintptr_t)(0x1000 + 0x100 * ss_k + 2 * (nobj + 1) + (simple ? 1 : 0)); }
+    // seam: the family's ss_seam_render_kernel instantiations, the one-call seam's variant of the supersampling kernels
+    const void* key(uint32_t ss_k = 1u, bool seam = false) const { return (const void*)(uintptr_t)(0x1000 + (seam ? 0x800 : 0) + 0x100 * ss_k + 2 * (nobj + 1) + (simple ? 1 : 0)); }
     std::string name(const char* tree_how = "tree") const {
         if (nobj < 0) return std::string("render_kernel<") + tree_how + ">";
         return "render_kernel<" + std::to_string(nobj) + (simple ? ",simple>" : ",general>");
@@ -1828,9 +1829,18 @@ inline rtc_status deep_variant(const KernelVariant& v, int depth, KernelVariant*
 // The plan of a supersampled context, k = 2, 4 (`p`: plan_scene of the FINE camera).  Scene tiles, the scene rectangle and several
 // blocks per workgroup address the canvas by fine pixels and are not carried over: such scenes are a plain grid, where the
 // scene-box early-out still applies; nor is the level-by-level renderer.
-inline void plan_supersampled(ScenePlan* p, uint32_t k) {
+inline void plan_supersampled(ScenePlan* p, uint32_t k, bool seam = false) {
     const KernelVariant v = render_variant(*p, k);
     p->spec_defs = v.defs, p->family_name = v.family_name, p->spec_name = v.spec_name, p->ss_k = k;
+    // a context of the one-call seam (rtc_render_ss): the variant of the supersampling body that stores bytes and reports its rows
+    // (rtc_supersample.h SEAM) -- another option, so another kernel id and cache entry than the persistent context's kernel
+    // ... and a name that says so: "ss_seam_render_kernel<...;ss=k>" is the ahead-of-time kernel launched, "ss_render_kernel_spec[...;ss=k;seam]"
+    // the scene's own (its entry point keeps its name: the variant is an option of the compile)
+    if (seam) {
+        if (!p->spec_defs.empty()) p->spec_defs.push_back("-DRTC_SPEC_SS_SEAM=1");
+        p->family_name = with_prefix(p->family_name, "ss_render_kernel<", "ss_seam_render_kernel<");
+        if (!p->spec_name.empty()) p->spec_name.insert(p->spec_name.size() - 1, ";seam");
+    }
     p->scene_tile_mask.clear();
     p->scene_rect[0] = p->scene_rect[1] = p->scene_rect[2] = p->scene_rect[3] = 0u;
     p->spec_blocks_y = p->spec_rect = false;

@@ -12,7 +12,17 @@
 // render_body calls: where_is_lane (never a scene rectangle launch, one block per workgroup), primary_ray, color_at,
 // store_wave_counts -- all but image_row, whose two lines are written out below.  Not supported, because the host never
 // asks a supersampled launch for them: scene rectangle launches and their zero-filling workgroups, several blocks per
-// workgroup, progress words, the u8 canvas.
+// workgroup.
+// The one-call seam (rtc_render_ss) asks for what it asks of render_body, of the one lane per output pixel that stores after the
+// reduce: the u8 canvas (RenderArgs::out_u8: [out_rows][out_width][3] bytes) and progress words (RenderArgs::progress, regular
+// grid only: gridDim.y counts FINE block rows, a chunk is chunk_block_rows of them, the host turns them into output rows).
+// render_body's write-through stores and its progress tail are repeated here, not shared: a scene's plain render kernel is
+// identified by the TEXT of rtc_kernel_core.h (JitKind::RENDER hashes the core alone), so moving them into a function of the
+// core would change every plain kernel's id -- the ones profiles/*_pmc.json and bench.py match -- for no change in code.
+// Both are a COMPILE-TIME variant (SEAM; ss_seam_render_kernel<...>, -DRTC_SPEC_SS_SEAM=1), launched by the seam's contexts alone:
+// as wave-uniform run-time branches on the kernel's arguments -- render_body's way -- they moved the register allocation of the
+// kernels the persistent context launches (four of the twelve ahead-of-time instantiations spilled 18 to 40 VGPRs more, DESIGN.md
+// 8b).  With SEAM = false this body compiles to what it was.  Within the variant, u8 and reporting are run-time, wave-uniform.
 #ifndef RTC_SUPERSAMPLE_H
 #define RTC_SUPERSAMPLE_H
 
@@ -60,7 +70,7 @@ DI float ss_reduce(float v, uint32_t sl, uint32_t tw_log2) {
     return v * (1.0f / (float)(K * K));  // 0.25f / 0.0625f: exact constants
 }
 
-template <int NOBJ, bool SIMPLE, int K>
+template <int NOBJ, bool SIMPLE, int K, bool SEAM>
 DI void ss_render_body(const SsRenderArgs& SA) {
     const RenderArgs& A = SA.fine;
     const SceneHdr& H = A.hdr;
@@ -76,6 +86,15 @@ DI void ss_render_body(const SsRenderArgs& SA) {
     if (timed) ticks0 = (uint32_t)wall_clock64();
     __shared__ float stash_lds[LDS_SLOTS * 256];
     const LaneStash stash = {stash_lds + threadIdx.x, 256u};
+    [[maybe_unused]] uint32_t* waves_done = nullptr;  // progress reporting: how many of this workgroup's waves have stored their pixels
+    if constexpr (SEAM) {
+        __shared__ uint32_t waves_done_lds;
+        waves_done = &waves_done_lds;
+        if (A.progress != nullptr) {  // wave-uniform (a kernel argument); the one barrier, in front of all work
+            if (threadIdx.x == 0) waves_done_lds = 0u;
+            __syncthreads();
+        }
+    }
     // A lane outside the fine frame contributes zero.  Such lanes only ever form whole K x K blocks: the fine width, the fine
     // rows of a partition and every band are multiples of K, and so is every tile's origin.
     V3 col = v3(0.0f, 0.0f, 0.0f);
@@ -104,17 +123,57 @@ DI void ss_render_body(const SsRenderArgs& SA) {
     col.y = ss_reduce<K>(col.y, sl, tw_log2);
     col.z = ss_reduce<K>(col.z, sl, tw_log2);
     // One lane per output pixel stores: the block's first slot, the lead lane of a pixel's lanes.  Three dword stores, 1 / K^2 of
-    // the fine frame's.
+    // the fine frame's -- or three bytes, scale_color of the reduced colour (render_body's arithmetic), and write-through
+    // (system scope) when the launch reports its rows (RenderArgs::progress).
     if (cnt.lead() && (qx & (uint32_t)(K - 1)) == 0u && (qy & (uint32_t)(K - 1)) == 0u) {
         const uint32_t ox = x / (uint32_t)K, oy = yl / (uint32_t)K;
         if (ox < SA.out_width && oy < SA.out_rows) {
-            float* dst = A.out + ((size_t)oy * SA.out_width + ox) * 3;
-            dst[0] = col.x;
-            dst[1] = col.y;
-            dst[2] = col.z;
+            const bool through = SEAM && A.progress != nullptr;  // wave-uniform
+            const size_t at = ((size_t)oy * SA.out_width + ox) * 3;
+            if (SEAM && A.out_u8 != nullptr) {  // wave-uniform
+                uint8_t* dst = A.out_u8 + at;
+                const uint8_t r = (uint8_t)fmaxf(fminf(col.x * 255.0f, 255.0f), 0.0f), g = (uint8_t)fmaxf(fminf(col.y * 255.0f, 255.0f), 0.0f),
+                              b = (uint8_t)fmaxf(fminf(col.z * 255.0f, 255.0f), 0.0f);
+                if (through) {
+                    __hip_atomic_store(dst, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(dst + 1, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(dst + 2, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                } else {
+                    dst[0] = r, dst[1] = g, dst[2] = b;
+                }
+            } else {
+                float* dst = A.out + at;
+                if (through) {
+                    __hip_atomic_store(dst, col.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(dst + 1, col.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(dst + 2, col.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                } else {
+                    dst[0] = col.x;
+                    dst[1] = col.y;
+                    dst[2] = col.z;
+                }
+            }
         }
     }
     store_wave_counts(A, cnt, timed, ticks0);
+    // render_body's progress tail (see RenderArgs::progress, and the head of this file for why it is written out a second
+    // time): the wave's stores are acknowledged -- write-through: in memory -- before it counts itself done; the workgroup's last
+    // wave counts the block row, the row's last workgroup the chunk, the chunk's last row writes the host's word.
+    if (SEAM && A.progress != nullptr) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_s_waitcnt(0);
+        uint32_t last = 0u;
+        if (lane == 0) last = __hip_atomic_fetch_add(waves_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 3u ? 1u : 0u;
+        if (__builtin_amdgcn_readfirstlane((int)last) != 0 && lane == 0) {
+            const uint32_t row = blockIdx.y;
+            if (__hip_atomic_fetch_add(&A.progress[row * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == gridDim.x) {
+                const uint32_t ch = row / A.chunk_block_rows;
+                const uint32_t in_chunk = min(A.chunk_block_rows, gridDim.y - ch * A.chunk_block_rows);
+                if (__hip_atomic_fetch_add(&A.progress[(gridDim.y + ch) * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == in_chunk)
+                    __hip_atomic_store(&A.done[ch], A.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
 }
 
 #ifdef RTC_SPEC_LIST
@@ -122,14 +181,23 @@ DI void ss_render_body(const SsRenderArgs& SA) {
 }  // namespace rtc
 // The supersampling kernel of a scene-specialised (hiprtc) build.
 extern "C" __global__ __launch_bounds__(256, RTC_WAVES_PER_SIMD) void ss_render_kernel_spec(rtc::SsRenderArgs A) {
-    rtc::ss_render_body<RTC_SPEC_NOBJ, RTC_SPEC_SIMPLE != 0, RTC_SPEC_SS>(A);
+#if defined(RTC_SPEC_SS_SEAM) && RTC_SPEC_SS_SEAM
+    rtc::ss_render_body<RTC_SPEC_NOBJ, RTC_SPEC_SIMPLE != 0, RTC_SPEC_SS, true>(A);  // a context of the one-call seam
+#else
+    rtc::ss_render_body<RTC_SPEC_NOBJ, RTC_SPEC_SIMPLE != 0, RTC_SPEC_SS, false>(A);
+#endif
 }
 namespace rtc {
 #endif
 #else
 template <int NOBJ, bool SIMPLE, int K>
 __global__ __launch_bounds__(256, RTC_WAVES_PER_SIMD) void ss_render_kernel(SsRenderArgs A) {
-    ss_render_body<NOBJ, SIMPLE, K>(A);
+    ss_render_body<NOBJ, SIMPLE, K, false>(A);
+}
+// ... and the one the one-call seam's contexts launch: bytes, write-through stores and progress words on request
+template <int NOBJ, bool SIMPLE, int K>
+__global__ __launch_bounds__(256, RTC_WAVES_PER_SIMD) void ss_seam_render_kernel(SsRenderArgs A) {
+    ss_render_body<NOBJ, SIMPLE, K, true>(A);
 }
 #endif
 

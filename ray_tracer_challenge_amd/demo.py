@@ -33,6 +33,8 @@ def main(argv=None):
     ap.add_argument("file", nargs="?", help="the demo's argv[1] (OBJ mesh / PPM texture)")
     ap.add_argument("--size", help="WxH (default: the demo's own)")
     ap.add_argument("--out", help="write the PPM here instead of stdout")
+    ap.add_argument("--supersample", type=int, choices=(1, 2, 4), default=1, metavar="K",
+                    help="K x K rays per pixel, reduced in the render kernel (1, 2 or 4; default 1: the demo's own frame)")
     a = ap.parse_args(argv)
     fn, size, file_kw = DEMOS[a.demo]
     if a.size:
@@ -46,7 +48,7 @@ def main(argv=None):
     t0 = time.time()
     world, camera, depth = fn(size[0], size[1], **kw)
     t1 = time.time()
-    canvas = camera.render(world, depth)
+    canvas = camera.render(world, depth) if a.supersample == 1 else camera.render(world, depth, supersample=a.supersample)
     ppm = canvas.to_ppm()
     t2 = time.time()
     st = camera.last_stats
