@@ -129,7 +129,7 @@ DI void adaptive_refine_body(const AdaptiveRefineArgs& A) {
             dst[2] = col.z;
         }
         const uint4 counts = reduce_wave_counts(cnt);
-        if (lane == 0u) acc[wave][0] += counts.x, acc[wave][1] += counts.y, acc[wave][2] += counts.z;
+        if (lane == COUNTS_LANE) acc[wave][0] += counts.x, acc[wave][1] += counts.y, acc[wave][2] += counts.z;
     }
     // one partial per wave, added to the totals the host zeroed; no workgroup barrier (a finished wave leaves); a wave that
     // took no step adds nothing

@@ -521,6 +521,19 @@ struct SceneHdr {
     float cell_hd;
 };
 constexpr uint32_t CULL_ENABLED = 1u, CULL_DARK = 2u, CULL_FAST_SHADOW = 4u, CULL_CELLS = 8u, CULL_OWN_BLOCKS = 16u;
+// SceneHdr::cull_flags where one of its switches is asked for.  In the short form of the wave's fixed part (RTC_WAVE_FIXED_SHORT, decided
+// below the kernels' arguments: the scene kernels with one lane per pixel) the word is hidden from the compiler behind an empty asm, so each
+// switch is a scalar bit test at its place.  Seen through, the five tests are hoisted to the head of color_at as 64-bit lane masks that do not
+// fit the SGPRs, and C3's kernel spills VGPRs to scratch besides (five spill and reload instructions, two of the reloads inside the shading
+// loop; 432 -> 420 B and 72 -> 71 VGPRs without them: what is left in scratch is the recursion's frames).  C3's kernel 0.5174 -> 0.5105 ms
+// (profiles/wave_fixed_cost_ab.txt).  Every other kernel reads the word plainly, as before.
+DI uint32_t cull_flags_of(const SceneHdr& H) {
+    uint32_t f = H.cull_flags;
+#if defined(RTC_SPEC_LIST) && !(defined(RTC_SPEC_SHARE) && RTC_SPEC_SHARE)  // (RTC_WAVE_FIXED_SHORT's condition: that macro is defined further down)
+    asm volatile("" : "+s"(f));
+#endif
+    return f;
+}
 constexpr uint32_t RTC_MAX_GATES = 8;
 
 // Structure-of-arrays scene records in HBM: 4 float4 of geometry (64 B) and
@@ -1734,7 +1747,7 @@ DI uint32_t light_cull_mask(const SceneHdr& H, const SceneSoA& S, V3 p, bool& da
     const float pmax = fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fabsf(p.z));
     // the samples stay inside the parallelogram only for jitter in [0, 1] (the hashed source draws from (0, 1])
     const bool hashed = spec_jitter_mode(H.jitter_mode) == RTC_JITTER_HASHED;
-    if (!(H.cull_flags & CULL_ENABLED)) return 0u;
+    if (!(cull_flags_of(H) & CULL_ENABLED)) return 0u;
     if (!hashed && !(H.jitter_const >= 0.0f && H.jitter_const <= 1.0f)) return 0u;
     // a decision costs about as much as four or five ray-object tests: not worth it for a handful of samples
     if (H.u_steps * H.v_steps < 8) return 0u;
@@ -1981,7 +1994,7 @@ DI uint32_t light_cull_mask(const SceneHdr& H, const SceneSoA& S, V3 p, bool& da
             for (uint32_t i = 0; i < H.n_objects; i++) reach(i, false);
         }
     }
-    if (noncasters_left || !(H.cull_flags & CULL_DARK)) dark = false;  // a non-caster might be hit first
+    if (noncasters_left || !(cull_flags_of(H) & CULL_DARK)) dark = false;  // a non-caster might be hit first
     return mask;
 }
 
@@ -2008,7 +2021,7 @@ enum { SHADOW_LIT = 0, SHADOW_BLOCKED = 1, SHADOW_UNCERTAIN = 2 };
 template <int NOBJ, bool SIMPLE>
 DI bool shadow_fast_usable(const SceneHdr& H, const SceneSoA& S, uint32_t skip) {
     if constexpr (!SIMPLE || NOBJ <= 0) return false;
-    if (!(H.cull_flags & CULL_FAST_SHADOW)) return false;
+    if (!(cull_flags_of(H) & CULL_FAST_SHADOW)) return false;
     bool ok = true;
 #pragma unroll
     for (uint32_t i = 0; i < (uint32_t)(NOBJ > 0 ? NOBJ : 1); i++) {
@@ -2155,7 +2168,7 @@ DI V3 point_on_light(V3 corner, V3 uvec, V3 vvec, float a, float b) {
 // whatever else is in play as long as every CASTER in play is such a sphere: a non-caster never shadows (world.rs:117).
 template <int NOBJ>
 DI bool blocks_usable(const SceneHdr& H, const SceneSoA& S, uint32_t skip) {  // wave-uniform
-    if (!(H.cull_flags & CULL_CELLS) || !(H.cell_hd > 0.0f) || ((H.u_steps | H.v_steps) & 1) != 0) return false;
+    if (!(cull_flags_of(H) & CULL_CELLS) || !(H.cell_hd > 0.0f) || ((H.u_steps | H.v_steps) & 1) != 0) return false;
     if (spec_jitter_mode(H.jitter_mode) == RTC_JITTER_SEQUENCE) return false;  // (its draws are numbered in the reference's cell order: the plain loop)
     bool ok = true;
 #pragma unroll
@@ -2239,7 +2252,7 @@ DI float intensity_at(const SceneHdr& H, const SceneSoA& S, V3 p, uint32_t pixel
             // gains no instruction.  NaN sq (a shade point inside the block cone's base) holds in no comparison, as before.
             // (oo <= 1.21 is implied by the mute zone, oo <= 1.001 R^2 ~ 1.062: it is written out because it is the bound B2's
             // argument and the T_lit inequality above are stated for.)
-            const bool own = (H.cull_flags & CULL_OWN_BLOCKS) != 0u;  // wave-uniform
+            const bool own = (cull_flags_of(H) & CULL_OWN_BLOCKS) != 0u;  // wave-uniform
 #pragma unroll
             for (int i = 0; i < N; i++) {
                 const uint32_t bits = spec_bits(i, __float_as_uint(S.geo[i].w));
@@ -3105,6 +3118,35 @@ struct RenderArgs {
 };
 constexpr uint32_t PROGRESS_STRIDE = 16;
 
+// What every wave does around color_at, short form: RTC_WAVE_FIXED_SHORT.  The scene-compiled kernels with one lane per pixel -- what
+// bench.py's frames and every large frame run -- read the arguments of their epilogue where it starts (late_args), find a pixel's
+// image row without a division where none is needed (image_row) and sum the wave's counters with DPP (reduce_wave_counts).  The
+// ahead-of-time kernels and the lane-sharing scene kernels (-DRTC_SPEC_SHARE=1) keep the earlier form of all three, instruction for
+// instruction: these kernels are compiled to the last register, some of them lost scratch bytes to the short form
+// (profiles/wave_fixed_cost_codegen.txt is the guard), and the lane-sharing frames -- a few thousand waves that do not fill the chip -- measured
+// no faster with it (C1, mesh: profiles/wave_fixed_cost_ab.txt).
+#if defined(RTC_SPEC_LIST) && !(defined(RTC_SPEC_SHARE) && RTC_SPEC_SHARE)
+#define RTC_WAVE_FIXED_SHORT 1
+#else
+#define RTC_WAVE_FIXED_SHORT 0
+#endif
+
+// The kernel's argument struct ARGS read where it is asked for.  ARGS must be the kernel's argument at byte KERNARG_OFFSET of its
+// kernel-argument segment -- 0: the kernel's first (here: only) argument; every __global__ entry whose body calls this says so.
+// Loads from a kernel's by-value argument are placed in its entry block, so what a wave needs only after color_at -- the
+// canvas, the counters' buffers, the progress words, the pixel's place -- was loaded in front of it, written to VGPR lanes
+// to survive it (SGPRs run out first) and read back at the end: C3's kernel held 307 v_writelane / v_readlane, 92 of them in front of
+// the primary ray's square root (tools/codegen_table.py's two lane figures).  Through this pointer, which the empty asm hides from the
+// compiler, they are scalar loads that start where the epilogue starts; the address space is the constant one again after inlining, so
+// they stay s_load.
+template <class ARGS, uint32_t KERNARG_OFFSET = 0u>
+DI const ARGS& late_args() {
+    static_assert(KERNARG_OFFSET % 8u == 0u, "a kernel argument struct with pointers is 8-byte aligned");
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();  // (a pointer into the constant address space)
+    asm volatile("" : "+s"(p));
+    return *(const ARGS*)((const char*)p + KERNARG_OFFSET);
+}
+
 // One of the launch's first workgroups (render_body): zero the part outside the scene rectangle of its share of the rows.
 // Memory-bound work running beside the arithmetic-bound rendering; 16-byte stores where rows and segments are aligned to
 // that (widths that are multiples of 4; the rectangle's columns are multiples of 16 pixels).
@@ -3133,7 +3175,18 @@ DI void fill_outside(const RenderArgs& A, uint32_t fill_row) {
 // counters' wave reduce.
 
 // Compact local row of a partition -> global row of the image: the partition owns every n_parts-th band of band_rows rows.
+// The arguments but `yl` are the kernel's (wave-uniform), so the two cases that need no division are scalar branches: one
+// part owns every band (band * band_rows + rest is yl again; the host admits only part < n_parts, so `part` is 0 and
+// band_rows is never 0), and a band of 2^k rows is a shift and a mask -- k found with a scalar count of leading zeros.  The
+// general case is a full 32-bit division, about 22 VALU instructions in front of every wave.  All three give the same integer.
 DI uint32_t image_row(uint32_t yl, uint32_t band_rows, uint32_t n_parts, uint32_t part) {
+#if RTC_WAVE_FIXED_SHORT
+    if (n_parts == 1u) return yl;
+    if ((band_rows & (band_rows - 1u)) == 0u) {
+        const uint32_t k = 31u - (uint32_t)__builtin_clz(band_rows);
+        return ((((yl >> k) * n_parts + part)) << k) + (yl & (band_rows - 1u));
+    }
+#endif
     const uint32_t band = yl / band_rows;
     return (band * n_parts + part) * band_rows + (yl - band * band_rows);
 }
@@ -3169,8 +3222,32 @@ DI bool primary_ray(const SceneHdr& H, uint32_t x, uint32_t y, V3& origin, V3& p
     return sees_nothing;
 }
 
-// work statistics: the wave's {rays, shaded hits, culled shadow rays, 0}, whole in lane 0
+// One step of the wave's sum: v plus v as data-parallel-primitive control CTRL moves it between lanes.  A lane that CTRL gives no
+// source (the shift runs off its row of 16) or that ROWS leaves out adds zero (`old` is 0, bound_ctrl zero-fills).
+template <int CTRL, int ROWS>
+DI uint32_t sum_dpp(uint32_t v) { return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, true); }
+// The sum of v over the wave's 64 lanes, whole in lane COUNTS_LANE: row_shr:1, 2, 4, 8 leave each row's sum in its last lane,
+// row_bcast:15 adds that of rows 0 and 2 to rows 1 and 3, row_bcast:31 that of lane 31 to rows 2 and 3.  Six adds that take
+// their operand through DPP -- where five __shfl_down were five ds_bpermute_b32 with their address arithmetic and LDS waits.
+// Every lane of the wave must be enabled (a disabled lane is a hole in the shifts); integer sums do not depend on order.
+#if RTC_WAVE_FIXED_SHORT
+constexpr uint32_t COUNTS_LANE = 63u;
+#else
+constexpr uint32_t COUNTS_LANE = 0u;  // (the earlier form: eighteen __shfl_down towards lane 0)
+#endif
+DI uint32_t wave_sum(uint32_t v) {
+    v = sum_dpp<0x111, 0xf>(v);
+    v = sum_dpp<0x112, 0xf>(v);
+    v = sum_dpp<0x114, 0xf>(v);
+    v = sum_dpp<0x118, 0xf>(v);
+    v = sum_dpp<0x142, 0xa>(v);
+    return sum_dpp<0x143, 0xc>(v);
+}
+// work statistics: the wave's {rays, shaded hits, culled shadow rays, 0}, whole in lane COUNTS_LANE
 DI uint4 reduce_wave_counts(const Counters& cnt) {
+#if RTC_WAVE_FIXED_SHORT
+    return make_uint4(wave_sum(cnt.rays), wave_sum(cnt.shaded_count()), wave_sum(cnt.culled_count()), 0u);
+#else
     uint32_t rays = cnt.rays, shaded = cnt.shaded_count(), culled = cnt.culled_count();
     for (int off = 32; off > 0; off >>= 1) {
         rays += __shfl_down(rays, off, 64);
@@ -3178,6 +3255,7 @@ DI uint4 reduce_wave_counts(const Counters& cnt) {
         culled += __shfl_down(culled, off, 64);
     }
     return make_uint4(rays, shaded, culled, 0u);
+#endif
 }
 
 // Where a lane's pixel is, for render_body and ss_render_body: block `rep` (< blocks_y) of this workgroup, in a block list
@@ -3237,7 +3315,7 @@ DI void store_wave_counts(const RenderArgs& A, const Counters& cnt, bool timed, 
     // one partial per WAVE and no workgroup barrier: a wave that is done leaves (where neighbouring tiles differ a lot in
     // depth of recursion -- the edge of a glass ball -- the waiting waves were holding the slots of the next workgroup)
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 3) A.total[threadIdx.x] = 0ull;  // for sum_counts_kernel's atomics
-    if (lane == 0) A.block_counts[slot + wave] = counts;
+    if (lane == COUNTS_LANE) A.block_counts[slot + wave] = counts;
     if (timed && lane == 0) A.wave_ticks[slot + wave] = (uint32_t)wall_clock64() - ticks0;
 }
 
@@ -3301,9 +3379,16 @@ DI void render_body(const RenderArgs& A) {
     for (uint32_t rep = 0; rep < blocks_y; rep++) {
     const Where w = where_is_lane<RECT_LAUNCH>(A, lane, wave, blocks_y, rep);
     const uint32_t x = w.x, yl = w.yl;
+#if RTC_WAVE_FIXED_SHORT
+    const bool in_image = (!RECT_LAUNCH || !w.fills) && x < H.width && yl < A.rows;
+    V3 col = v3(0.0f, 0.0f, 0.0f);
+    if (in_image) {
+        const uint32_t y = image_row(yl, A.band_rows, A.n_parts, A.part);
+#else
     if ((!RECT_LAUNCH || !w.fills) && x < H.width && yl < A.rows) {
         const uint32_t y = image_row(yl, A.band_rows, A.n_parts, A.part);
         V3 col = v3(0.0f, 0.0f, 0.0f);
+#endif
         // camera.rs:80-81: `0..height-1` x `0..width-1` -- the last row and column stay black
         if (x < H.width - 1u && y < H.height - 1u) {
             V3 origin, pixel;
@@ -3322,15 +3407,28 @@ DI void render_body(const RenderArgs& A) {
 #ifdef RTC_DEBUG_STEPS  // group tests | exact tests << 20, leaf box tests, entries the WAVE stepped through
         col = v3(__uint_as_float(dbg_steps()[0] | dbg_steps()[2] << 20), __uint_as_float(dbg_steps()[1]), __uint_as_float(dbg_steps()[3]));
 #endif
-        // The canvas store (canvas.rs:26-43: row-major RGB): three dword stores per lane at a 12-byte stride.  (Round 4 measured the
-        // obvious alternative -- the wave's 8 x 8 tile transposed through LDS and stored as 48 sixteen-byte pieces, six per row: C3 +3 %,
-        // C5 +3 %, first_plane +6 %, profiles/r04_ab_wide_stores.txt.  The memory system merges the partial lines; the transpose costs
-        // an LDS round trip and registers in front of every wave's exit.)
+#if RTC_WAVE_FIXED_SHORT
+    }
+#endif
+    // The canvas store (canvas.rs:26-43: row-major RGB): three dword stores per lane at a 12-byte stride.  (Round 4 measured the
+    // obvious alternative -- the wave's 8 x 8 tile transposed through LDS and stored as 48 sixteen-byte pieces, six per row: C3 +3 %,
+    // C5 +3 %, first_plane +6 %, profiles/r04_ab_wide_stores.txt.  The memory system merges the partial lines; the transpose costs
+    // an LDS round trip and registers in front of every wave's exit.)
+    // Short form (RTC_WAVE_FIXED_SHORT): what it needs of the arguments is loaded here (late_args); the pixels' branch is closed in
+    // front of it and opened again behind it, so that the pointer is formed where the whole wave runs -- an SGPR written under a
+    // divergent branch is not something every instantiation compiles.  Earlier form: the arguments as they are, inside the branch.
+    {
+#if RTC_WAVE_FIXED_SHORT
+        const RenderArgs& L = late_args<RenderArgs>();
+        if (in_image && cnt.lead()) {
+#else
+        const RenderArgs& L = A;
         if (cnt.lead()) {
-            const bool through = A.progress != nullptr;  // wave-uniform: write-through stores (RenderArgs::progress)
-            const Where ws = where_is_lane<RECT_LAUNCH>(A, lane, wave, blocks_y, rep);
-            if (A.out_u8 != nullptr) {  // wave-uniform: scale_color on the way out (the arithmetic of quantize_kernel)
-                uint8_t* dst = A.out_u8 + ((size_t)ws.yl * H.width + ws.x) * 3;
+#endif
+            const bool through = L.progress != nullptr;  // wave-uniform: write-through stores (RenderArgs::progress)
+            const Where ws = where_is_lane<RECT_LAUNCH>(L, lane, wave, blocks_y, rep);
+            if (L.out_u8 != nullptr) {  // wave-uniform: scale_color on the way out (the arithmetic of quantize_kernel)
+                uint8_t* dst = L.out_u8 + ((size_t)ws.yl * L.hdr.width + ws.x) * 3;
                 const uint8_t r = (uint8_t)fmaxf(fminf(col.x * 255.0f, 255.0f), 0.0f), g = (uint8_t)fmaxf(fminf(col.y * 255.0f, 255.0f), 0.0f),
                               b = (uint8_t)fmaxf(fminf(col.z * 255.0f, 255.0f), 0.0f);
                 if (through) {
@@ -3341,7 +3439,7 @@ DI void render_body(const RenderArgs& A) {
                     dst[0] = r, dst[1] = g, dst[2] = b;
                 }
             } else {
-                float* dst = A.out + ((size_t)ws.yl * H.width + ws.x) * 3;
+                float* dst = L.out + ((size_t)ws.yl * L.hdr.width + ws.x) * 3;
                 if (through) {
                     __hip_atomic_store(dst, col.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     __hip_atomic_store(dst + 1, col.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -3354,9 +3452,17 @@ DI void render_body(const RenderArgs& A) {
             }
         }
     }
+#if !RTC_WAVE_FIXED_SHORT
     }
-    store_wave_counts(A, cnt, timed, ticks0);
-    if (A.progress != nullptr) {  // see RenderArgs::progress
+#endif
+    }
+#if RTC_WAVE_FIXED_SHORT
+    const RenderArgs& L = late_args<RenderArgs>();
+#else
+    const RenderArgs& L = A;
+#endif
+    store_wave_counts(L, cnt, timed, ticks0);
+    if (L.progress != nullptr) {  // see RenderArgs::progress
         // every store of this wave has been acknowledged -- and, being write-through, is in memory -- before the wave counts
         // itself done
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -3365,11 +3471,11 @@ DI void render_body(const RenderArgs& A) {
         if (lane == 0) last = __hip_atomic_fetch_add(&waves_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 3u ? 1u : 0u;
         if (__builtin_amdgcn_readfirstlane((int)last) != 0 && lane == 0) {
             const uint32_t row = blockIdx.y;
-            if (__hip_atomic_fetch_add(&A.progress[row * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == gridDim.x) {
-                const uint32_t ch = row / A.chunk_block_rows;
-                const uint32_t in_chunk = min(A.chunk_block_rows, gridDim.y - ch * A.chunk_block_rows);
-                if (__hip_atomic_fetch_add(&A.progress[(gridDim.y + ch) * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == in_chunk)
-                    __hip_atomic_store(&A.done[ch], A.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (__hip_atomic_fetch_add(&L.progress[row * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == gridDim.x) {
+                const uint32_t ch = row / L.chunk_block_rows;
+                const uint32_t in_chunk = min(L.chunk_block_rows, gridDim.y - ch * L.chunk_block_rows);
+                if (__hip_atomic_fetch_add(&L.progress[(gridDim.y + ch) * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == in_chunk)
+                    __hip_atomic_store(&L.done[ch], L.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
     }
@@ -3378,6 +3484,7 @@ DI void render_body(const RenderArgs& A) {
 #ifdef RTC_SPEC_LIST
 }  // namespace rtc
 // The one kernel of a scene-specialised (hiprtc) build.
+// (A is the kernel's first and only argument: render_body's late_args reads it at offset 0 of the kernel-argument segment)
 extern "C" __global__ __launch_bounds__(256, RTC_WAVES_PER_SIMD) void render_kernel_spec(rtc::RenderArgs A) {
     rtc::render_body<RTC_SPEC_NOBJ, RTC_SPEC_SIMPLE != 0>(A);
 }

@@ -125,13 +125,21 @@ DI void ss_render_body(const SsRenderArgs& SA) {
     // One lane per output pixel stores: the block's first slot, the lead lane of a pixel's lanes.  Three dword stores, 1 / K^2 of
     // the fine frame's -- or three bytes, scale_color of the reduced colour (render_body's arithmetic), and write-through
     // (system scope) when the launch reports its rows (RenderArgs::progress).
+    // (short form, RTC_WAVE_FIXED_SHORT: the arguments as late_args hands them out -- what the stores and the counters need is loaded here,
+    // behind color_at; earlier form: the arguments as they are)
+#if RTC_WAVE_FIXED_SHORT
+    const SsRenderArgs& LS = late_args<SsRenderArgs>();
+#else
+    const SsRenderArgs& LS = SA;
+#endif
+    const RenderArgs& L = LS.fine;
     if (cnt.lead() && (qx & (uint32_t)(K - 1)) == 0u && (qy & (uint32_t)(K - 1)) == 0u) {
         const uint32_t ox = x / (uint32_t)K, oy = yl / (uint32_t)K;
-        if (ox < SA.out_width && oy < SA.out_rows) {
-            const bool through = SEAM && A.progress != nullptr;  // wave-uniform
-            const size_t at = ((size_t)oy * SA.out_width + ox) * 3;
-            if (SEAM && A.out_u8 != nullptr) {  // wave-uniform
-                uint8_t* dst = A.out_u8 + at;
+        if (ox < LS.out_width && oy < LS.out_rows) {
+            const bool through = SEAM && L.progress != nullptr;  // wave-uniform
+            const size_t at = ((size_t)oy * LS.out_width + ox) * 3;
+            if (SEAM && L.out_u8 != nullptr) {  // wave-uniform
+                uint8_t* dst = L.out_u8 + at;
                 const uint8_t r = (uint8_t)fmaxf(fminf(col.x * 255.0f, 255.0f), 0.0f), g = (uint8_t)fmaxf(fminf(col.y * 255.0f, 255.0f), 0.0f),
                               b = (uint8_t)fmaxf(fminf(col.z * 255.0f, 255.0f), 0.0f);
                 if (through) {
@@ -142,7 +150,7 @@ DI void ss_render_body(const SsRenderArgs& SA) {
                     dst[0] = r, dst[1] = g, dst[2] = b;
                 }
             } else {
-                float* dst = A.out + at;
+                float* dst = L.out + at;
                 if (through) {
                     __hip_atomic_store(dst, col.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     __hip_atomic_store(dst + 1, col.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -155,22 +163,22 @@ DI void ss_render_body(const SsRenderArgs& SA) {
             }
         }
     }
-    store_wave_counts(A, cnt, timed, ticks0);
+    store_wave_counts(L, cnt, timed, ticks0);
     // render_body's progress tail (see RenderArgs::progress, and the head of this file for why it is written out a second
     // time): the wave's stores are acknowledged -- write-through: in memory -- before it counts itself done; the workgroup's last
     // wave counts the block row, the row's last workgroup the chunk, the chunk's last row writes the host's word.
-    if (SEAM && A.progress != nullptr) {
+    if (SEAM && L.progress != nullptr) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_waitcnt(0);
         uint32_t last = 0u;
         if (lane == 0) last = __hip_atomic_fetch_add(waves_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 3u ? 1u : 0u;
         if (__builtin_amdgcn_readfirstlane((int)last) != 0 && lane == 0) {
             const uint32_t row = blockIdx.y;
-            if (__hip_atomic_fetch_add(&A.progress[row * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == gridDim.x) {
-                const uint32_t ch = row / A.chunk_block_rows;
-                const uint32_t in_chunk = min(A.chunk_block_rows, gridDim.y - ch * A.chunk_block_rows);
-                if (__hip_atomic_fetch_add(&A.progress[(gridDim.y + ch) * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == in_chunk)
-                    __hip_atomic_store(&A.done[ch], A.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (__hip_atomic_fetch_add(&L.progress[row * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == gridDim.x) {
+                const uint32_t ch = row / L.chunk_block_rows;
+                const uint32_t in_chunk = min(L.chunk_block_rows, gridDim.y - ch * L.chunk_block_rows);
+                if (__hip_atomic_fetch_add(&L.progress[(gridDim.y + ch) * PROGRESS_STRIDE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == in_chunk)
+                    __hip_atomic_store(&L.done[ch], L.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
     }
@@ -180,6 +188,7 @@ DI void ss_render_body(const SsRenderArgs& SA) {
 #ifdef RTC_SPEC_SS
 }  // namespace rtc
 // The supersampling kernel of a scene-specialised (hiprtc) build.
+// (A is the kernel's first and only argument: ss_render_body's late_args reads it at offset 0 of the kernel-argument segment)
 extern "C" __global__ __launch_bounds__(256, RTC_WAVES_PER_SIMD) void ss_render_kernel_spec(rtc::SsRenderArgs A) {
 #if defined(RTC_SPEC_SS_SEAM) && RTC_SPEC_SS_SEAM
     rtc::ss_render_body<RTC_SPEC_NOBJ, RTC_SPEC_SIMPLE != 0, RTC_SPEC_SS, true>(A);  // a context of the one-call seam

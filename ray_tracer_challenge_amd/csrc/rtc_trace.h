@@ -38,7 +38,7 @@ DI void store_trace_counts(const TraceArgs& A, const Counters& cnt) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint4 counts = reduce_wave_counts(cnt);
     if (blockIdx.x == 0 && threadIdx.x < 3) A.total[threadIdx.x] = 0ull;  // for sum_counts_kernel's atomics
-    if (lane == 0) A.wave_counts[(size_t)blockIdx.x * 4u + wave] = counts;
+    if (lane == COUNTS_LANE) A.wave_counts[(size_t)blockIdx.x * 4u + wave] = counts;
 }
 
 template <int NOBJ, bool SIMPLE>

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256, 6) void wf_trace_kernel(WfArgs A) {
     }
     // ---- statistics: one partial per wave
     const uint4 counts = reduce_wave_counts(cnt);
-    if (lane == 0) A.wave_counts[A.count_base + ((blockIdx.y * gridDim.x + blockIdx.x) << 2) + (threadIdx.x >> 6)] = counts;
+    if (lane == COUNTS_LANE) A.wave_counts[A.count_base + ((blockIdx.y * gridDim.x + blockIdx.x) << 2) + (threadIdx.x >> 6)] = counts;
 }
 
 // after a level has been traced: how many nodes exist now (the combine pass's range for that level)

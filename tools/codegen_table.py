@@ -3,8 +3,9 @@
 
     python tools/codegen_table.py CSRC [OTHER_CSRC] [--out FILE]
 
-Per kernel: VGPRs, SGPRs, scratch bytes per lane, LDS bytes (the code object's metadata), instructions and `scratch_`
-instructions (counted in the assembly).  Covered: every kernel of the ahead-of-time library (rtc_device.hip, rtc_oneshot.hip,
+Per kernel: VGPRs, SGPRs, scratch bytes per lane, LDS bytes (the code object's metadata), instructions, `scratch_`
+instructions, v_writelane_b32 + v_readlane_b32 instructions -- SGPR spills into VGPR lanes -- and how many of those stand in front of the
+kernel's first v_sqrt_f32 / v_rsq_f32, the primary ray's normalisation in the per-pixel kernels (counted in the assembly, in program order).  Covered: every kernel of the ahead-of-time library (rtc_device.hip, rtc_oneshot.hip,
 build.py's flags, device only); the scene kernels of the eight profiled workloads (tools/check_profile_ids.sh), their options
 taken from World.scene_plan(camera) and compiled as tools/spec_asm.sh does; C3's supersampling scene kernel at k = 2
 (the fine camera's options as rtc_ctx_set_scene_ss rewrites them); and, where the directory has rtc_trace.h, the same eight
@@ -33,7 +34,8 @@ from ray_tracer_challenge_amd import scenes  # noqa: E402
 SCENES = [("C3", "soft_shadows", 4096, 4096), ("C4", "glass_and_mirror", 4096, 4096), ("C5", "sphere_grid", 8192, 8192),
           ("hexagons", "hexagons", 4096, 2048), ("mesh", "mesh", 2048, 2048), ("dragons", "here_be_dragons", 1000, 400),
           ("reflect_refract", "reflect_refract", 4096, 2048), ("first_textures", "first_textures", 4096, 2048)]
-FIGURES = ("vgpr", "sgpr", "scratch", "lds", "insts", "scratch_insts")
+FIGURES = ("vgpr", "sgpr", "scratch", "lds", "insts", "scratch_insts", "lane_insts", "lane_front")
+PAIR_FIGURES = FIGURES[:6]  # (--trace-pairs, --hits-pairs: the six their files have had from the start)
 
 
 def scene_defs(name, w, h, ss=0, trace=False):
@@ -71,6 +73,11 @@ def read_asm(path):
         body = body[:body.index(".Lfunc_end")]
         insts = [ln.split()[0] for ln in body.splitlines() if re.match(r"^\t[a-z]", ln)]
         r["insts"], r["scratch_insts"] = len(insts), sum(1 for i in insts if i.startswith("scratch_"))
+        lane = [i in ("v_writelane_b32", "v_readlane_b32") for i in insts]  # SGPRs spilled into VGPR lanes, and read back
+        # ... of them, those in front of the kernel's first v_sqrt_f32 / v_rsq_f32 in program order: for the per-pixel kernels that is the
+        # primary ray's normalisation, so the figure is what stands between a wave's entry and its first ray (all of them where there is no such instruction)
+        first_root = next((n for n, i in enumerate(insts) if i.startswith(("v_sqrt_f32", "v_rsq_f32"))), len(insts))
+        r["lane_insts"], r["lane_front"] = sum(lane), sum(lane[:first_root])
     return rows
 
 
@@ -119,7 +126,8 @@ def main():
     own = os.path.join(ROOT, "ray_tracer_challenge_amd", "csrc")
     with tempfile.TemporaryDirectory() as tmp:
         tables = [table(os.path.abspath(c), tmp, "t%d" % i, device_only) for i, c in enumerate(args.csrc)]
-    lines = ["figures per kernel: VGPRs / SGPRs / scratch bytes per lane / LDS bytes / instructions / scratch_ instructions"]
+    lines = ["figures per kernel: VGPRs / SGPRs / scratch bytes per lane / LDS bytes / instructions / scratch_ instructions / "
+             "v_writelane_b32 + v_readlane_b32 instructions / those of them in front of the first v_sqrt_f32 or v_rsq_f32 (the primary ray's normalisation)"]
     if len(tables) == 2:
         lines.append("first: %s   second: %s   (* a figure that differs)" % tuple(os.path.relpath(os.path.abspath(c), ROOT) if os.path.abspath(c) == own else "the parent's csrc" for c in args.csrc))
     differing = []
@@ -130,7 +138,7 @@ def main():
             which = [f for f in FIGURES if k not in tables[0] or k not in tables[1] or tables[0][k][f] != tables[1][k][f]]
             mark = "   * " + ", ".join(which)
             differing.append((k, which))
-        lines.append("%-110s %s%s" % (k, "   |   ".join("%-36s" % c for c in cells), mark))
+        lines.append("%-110s %s%s" % (k, "   |   ".join("%-48s" % c for c in cells), mark))
     if len(tables) == 2:
         hard = [k for k, which in differing if set(which) & {"vgpr", "scratch", "lds"}]
         lines.append("kernels with a differing figure: %d of %d; with differing VGPRs, scratch bytes or LDS bytes: %d%s"
@@ -147,7 +155,7 @@ def main():
             if ": trace_kernel" not in k:
                 continue
             sib = k.replace(" trace: trace_kernel_spec", ": render_kernel_spec").replace(": trace_kernel<", ": render_kernel<")
-            cells = [" / ".join(str(t[n][f]) for f in FIGURES) if n in t else "-" for n in (k, sib)]
+            cells = [" / ".join(str(t[n][f]) for f in PAIR_FIGURES) if n in t else "-" for n in (k, sib)]
             pairs.append("%-62s %-36s   |   %-36s %+d B" % (k, cells[0], cells[1], t[k]["scratch"] - t[sib]["scratch"] if sib in t else 0))
         open(args.trace_pairs, "w").write("\n".join(pairs) + "\n")
     if args.hits_pairs:
@@ -161,7 +169,7 @@ def main():
                 sib = k[:k.index(": ")] + ": rtc::is_shadowed_kernel"  # (not a template: the mangled name carries no return type)
             else:
                 continue
-            cells = [" / ".join(str(t[n][f]) for f in FIGURES) if n in t else "-" for n in (k, sib)]
+            cells = [" / ".join(str(t[n][f]) for f in PAIR_FIGURES) if n in t else "-" for n in (k, sib)]
             pairs.append("%-58s %-32s   |   %-32s %-32s %+d B" % (k, cells[0], sib.split(": ")[1].replace("rtc::", ""), cells[1], t[k]["scratch"] - t[sib]["scratch"] if sib in t else 0))
         open(args.hits_pairs, "w").write("\n".join(pairs) + "\n")
 
