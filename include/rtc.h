@@ -36,7 +36,8 @@ extern "C" {
                              / _id and the struct rtc_adaptive_stats are additions, nothing that existed has moved;
                              ray reordering: rtc_ctx_ray_order, rtc_ctx_trace_reordered, rtc_ctx_reorder_stats and the struct
                              rtc_reorder_stats, additions likewise; supersampling through the one-call seam: rtc_render_ss, one
-                             entry point more -- rtc_opts and rtc_stats are what they were) */
+                             entry point more -- rtc_opts and rtc_stats are what they were; the thin-lens camera: rtc_lens_rays,
+                             rtc_ctx_set_scene_lens and the struct rtc_lens, additions likewise) */
 /* reflection_recursion_depth (camera.rs:76: any i16; reference default 5, constants.rs:4; its author renders
  * reflect_refract at 20).  Accepted: 0 .. RTC_MAX_DEPTH.  The kernels keep one frame per suspended shade_hit
  * (world.rs:62-86); up to RTC_STACK_DEPTH_BASE levels every kernel has them, above that the scene's kernel is compiled
@@ -204,6 +205,15 @@ typedef struct rtc_partition {
     uint32_t part;
 } rtc_partition;
 
+/* A thin lens in front of a camera (rtc_ctx_set_scene_lens, rtc_lens_rays): rays leave from a disc of aperture_radius around the
+ * camera's origin, in the plane of its x and y axes, and meet where the pinhole's ray is at focal_distance times its unnormalised
+ * length (the plane in focus: camera-space z = -focal_distance).  aperture_radius >= 0, focal_distance > 0, both finite. */
+typedef struct rtc_lens {
+    float aperture_radius;
+    float focal_distance;
+    uint32_t seed; /* of the lens points' jitter */
+} rtc_lens;
+
 typedef struct rtc_stats {
     uint64_t rays;        /* World::intersect evaluations of the last launch (primary, shadow, reflect, refract) */
     uint64_t shaded_hits; /* shade_hit evaluations of the last launch (world.rs:62)                           */
@@ -313,6 +323,26 @@ void rtc_ray_for_pixel(const rtc_camera* c, uint32_t x, uint32_t y, float origin
  * (half_width * 2) / (k W as f32).  k = 1, 2 or 4; any other k, or a fine frame beyond what a launch addresses (2^32 pixels:
  * the pixel index is the jitter key; 2^17 rows), is RTC_ERR_INVALID_ARG with a message.  Host only. */
 rtc_status rtc_camera_supersampled(const rtc_camera* camera, uint32_t k, rtc_camera* fine);
+/* The rays of a lens frame (rtc_ctx_set_scene_lens), which this function DEFINES: k x k rays per pixel of `output_camera` (W x H),
+ * k = 2 or 4, each from its own point of the lens.  Let Cf = rtc_camera_supersampled(output_camera, k).  The ray of fine pixel
+ * (x, y) of Cf, all in f32, nothing fused, operands in the order written:
+ *  1. o, p: the origin and the world-space pixel point of ray_for_pixel (camera.rs:60-74) for (x, y) of Cf, before it normalises.
+ *  2. key = y * k W + x.  ju = J(mix32(mix32(key ^ seed) + 1 * 0x9E3779B9)), jv = J(mix32(mix32(key ^ seed) + 2 * 0x9E3779B9)), where
+ *     mix32(h): h ^= h >> 16, h *= 0x7feb352d, h ^= h >> 15, h *= 0x846ca68b, h ^= h >> 16 (32-bit) and J(h) = ((h >> 9) + 1) * 2^-23,
+ *     in (0, 1] -- the keyed hash of RTC_JITTER_HASHED lights.
+ *  3. i = x mod k, j = y mod k; the lens cell is the sub-pixel cell turned by a quarter: ci = j, cj = k - 1 - i.
+ *     u = ((float)ci + ju) / (float)k, v = ((float)cj + jv) / (float)k, r = aperture_radius * sqrtf(u), theta = 6.2831855f * v,
+ *     lx = r * cosf(theta), ly = r * cosf(theta - 1.5707964f).  sqrtf is IEEE, cosf the C library's (glibc: correctly rounded in
+ *     practice; the kernels carry a bit-exact restatement).
+ *  4. right = (inv[0], inv[4], inv[8]), up = (inv[1], inv[5], inv[9]) of the camera; o' = (o + right * lx) + up * ly, per component.
+ *  5. P = o + (p - o) * focal_distance; d = (P - o') / |P - o'| (tuple.rs:29-43: the square root of the sum of squares, three divisions).
+ * Writes the rays of fine rows y0 .. y0 + n_rows - 1, every column, in image order, to HOST buffers in rtc_ctx_trace's layout:
+ * origins[j] = (o', 1), directions[j] = (d, 0), 16 bytes each, j = (y - y0) * k W + x; either may be NULL.  The last fine row
+ * and column are written too (a lens frame does not trace them).  Host only, no device.  RTC_ERR_INVALID_ARG with a message: a
+ * null camera or lens, k not 2 or 4, aperture_radius negative or not finite, focal_distance <= 0 or not finite, a fine frame
+ * rtc_camera_supersampled refuses, y0 + n_rows beyond k H. */
+rtc_status rtc_lens_rays(const rtc_camera* output_camera, uint32_t k, const rtc_lens* lens, uint32_t y0, uint32_t n_rows,
+                         float* origins, float* directions);
 
 /* Runs the checks and the flattening rtc_ctx_set_scene performs (shape / pattern kinds, affine transforms, group
  * nesting, light and camera sanity), without touching a device: RTC_OK, or the status rtc_ctx_set_scene would
@@ -402,6 +432,24 @@ rtc_status rtc_ctx_set_scene(rtc_ctx* ctx, const rtc_scene* scene, const rtc_cam
  * rtc_ctx_render_hits on a supersampled context is RTC_ERR_UNSUPPORTED (a first hit per output pixel is not defined).
  * The one-call seam supersamples through rtc_render_ss (above): the same frame, f32 or bytes, host buffer out, several devices. */
 rtc_status rtc_ctx_set_scene_ss(rtc_ctx* ctx, const rtc_scene* scene, const rtc_camera* output_camera, uint32_t k);
+/* A thin-lens camera: depth of field.  rtc_ctx_set_scene_ss with the k x k samples of an output pixel leaving from k x k points of
+ * `lens` (k = 2 or 4).  Afterwards rtc_ctx_render writes the W x H frame that is, by definition, rtc_ctx_set_scene_ss's box filter
+ * (same order, same constants) of the fine frame F whose pixel (x, y) is World::color_at (world.rs:88-101) of the ray
+ * rtc_lens_rays gives it, at the render's depth, with jitter key y * k W + x; F's last row and column are zero (camera.rs:80-81
+ * at the fine resolution).  aperture_radius = 0 is allowed: every ray leaves the camera's origin towards its focus point -- a
+ * supersampled pinhole whose directions are rounded differently; no bit equality with rtc_ctx_set_scene_ss's frame is promised.
+ * Everything else is a supersampled context's: partitions count output rows, rtc_stats counts the fine frame, unchanged records
+ * are not uploaded -- another lens or camera on the resident scene uploads nothing, so a focus pull costs three words of the next
+ * launch's arguments.  The kernel is one of its own (rtc_ctx_kernel_name "lens_render_kernel<...;ss=k>" /
+ * "lens_render_kernel_spec[...;ss=k;lens]", ids "aot_lens<k>_<hash>" / "spec_..."); the scene-box early-out of the pinhole kernels,
+ * argued for rays from the camera's origin, is off.  A later rtc_ctx_set_scene or rtc_ctx_set_scene_ss leaves lens mode.
+ * On a lens context rtc_ctx_render_hits and rtc_ctx_render_adaptive are RTC_ERR_UNSUPPORTED; rtc_ctx_trace, rtc_ctx_trace_hits,
+ * rtc_ctx_is_shadowed and rtc_ctx_camera_rays are what they are on any context.
+ * RTC_ERR_INVALID_ARG with a message, decided on the host before any device call and before the context is looked at: a null lens
+ * or camera, k not 2 or 4, aperture_radius negative or not finite, focal_distance <= 0 or not finite, a fine frame
+ * rtc_camera_supersampled refuses.  Not offered: lens frames through rtc_render_*, rtc.hpp, several devices. */
+rtc_status rtc_ctx_set_scene_lens(rtc_ctx* ctx, const rtc_scene* scene, const rtc_camera* output_camera, uint32_t k,
+                                  const rtc_lens* lens);
 /* Rows this partition produces (sum of its bands' heights). */
 uint32_t rtc_partition_rows(uint32_t height, const rtc_partition* part);
 /* Launches the render kernel on `stream` (a hipStream_t; NULL = default

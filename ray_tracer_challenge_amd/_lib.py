@@ -75,6 +75,10 @@ class rtc_camera(C.Structure):
                 ("inv", C.c_float * 16)]
 
 
+class rtc_lens(C.Structure):
+    _fields_ = [("aperture_radius", C.c_float), ("focal_distance", C.c_float), ("seed", C.c_uint32)]
+
+
 class rtc_partition(C.Structure):
     _fields_ = [("band_rows", C.c_uint32), ("n_parts", C.c_uint32), ("part", C.c_uint32)]
 
@@ -157,6 +161,7 @@ SIGNATURES = {
     "rtc_camera_new": (C.c_int, [C.c_uint32, C.c_uint32, C.c_float, FP, C.POINTER(rtc_camera)]),
     "rtc_ray_for_pixel": (None, [C.POINTER(rtc_camera), C.c_uint32, C.c_uint32, FP, FP]),
     "rtc_camera_supersampled": (C.c_int, [C.POINTER(rtc_camera), C.c_uint32, C.POINTER(rtc_camera)]),
+    "rtc_lens_rays": (C.c_int, [C.POINTER(rtc_camera), C.c_uint32, C.POINTER(rtc_lens), C.c_uint32, C.c_uint32, FP, FP]),
     "rtc_render": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.c_int32, FP,
                              C.POINTER(rtc_stats)]),
     "rtc_render_ex": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.POINTER(rtc_opts), C.c_void_p,
@@ -171,6 +176,7 @@ SIGNATURES = {
     "rtc_ctx_destroy": (None, [C.c_void_p]),
     "rtc_ctx_set_scene": (C.c_int, [C.c_void_p, C.POINTER(rtc_scene), C.POINTER(rtc_camera)]),
     "rtc_ctx_set_scene_ss": (C.c_int, [C.c_void_p, C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_uint32]),
+    "rtc_ctx_set_scene_lens": (C.c_int, [C.c_void_p, C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_uint32, C.POINTER(rtc_lens)]),
     "rtc_partition_rows": (C.c_uint32, [C.c_uint32, C.POINTER(rtc_partition)]),
     "rtc_ctx_render": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(rtc_partition), C.c_void_p, C.c_void_p]),
     "rtc_ctx_stats": (C.c_int, [C.c_void_p, C.POINTER(rtc_stats)]),

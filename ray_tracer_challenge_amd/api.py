@@ -947,6 +947,19 @@ class Canvas:
 
 
 # -------------------------------------------------------------------- camera.rs
+class Lens:
+    """A thin lens in front of a camera (rtc_lens): rays leave from a disc of aperture_radius around the camera's origin and meet
+    at focal_distance (camera-space z = -focal_distance is in focus); seed: of the lens points' jitter.  Checked by the library
+    where it is used: aperture_radius >= 0, focal_distance > 0, both finite."""
+
+    def __init__(self, aperture_radius, focal_distance, seed=0):
+        self.aperture_radius, self.focal_distance, self.seed = float(f32(aperture_radius)), float(f32(focal_distance)), int(seed) & 0xFFFFFFFF
+        self._c = L.rtc_lens(self.aperture_radius, self.focal_distance, self.seed)
+
+    def __repr__(self):
+        return "Lens(aperture_radius=%r, focal_distance=%r, seed=%r)" % (self.aperture_radius, self.focal_distance, self.seed)
+
+
 class Camera:
     """Camera::new(width_pixels, height_pixels, field_of_view, transform) -- camera.rs:23-56"""
 
@@ -988,6 +1001,21 @@ class Camera:
         cam.transform = self.transform.copy()
         cam.last_stats = None
         return cam
+
+    def lens_rays(self, k, lens, y0=0, n_rows=None):
+        """The rays of a lens frame (rtc_lens_rays, which defines them; host only): k x k rays per pixel of this camera, k = 2 or
+        4, for rows [y0, y0 + n_rows) of the fine frame (default: to the last) -> (origins (n, 4), directions (n, 4)) float32 in
+        image order, Renderer.trace's layout; ray j of row y has jitter key y * k * width + x."""
+        k, y0 = int(k), int(y0)
+        n_rows = k * self.height - y0 if n_rows is None else int(n_rows)
+        # (the library checks the factor, the lens and the fine frame; the rows are checked here too: they size the buffers)
+        if k in (2, 4) and not (y0 >= 0 and n_rows >= 0 and y0 + n_rows <= k * self.height):
+            raise ValueError("rows [%d, %d) of a fine frame of %d" % (y0, y0 + n_rows, k * self.height))
+        n = n_rows * k * self.width if k in (2, 4) else 0
+        o, d = np.zeros((n, 4), dtype=f32), np.zeros((n, 4), dtype=f32)
+        L.check(L.lib().rtc_lens_rays(C.byref(self._cam), k, C.byref(lens._c) if lens is not None else None, y0 if n else 0, n_rows if n else 0,
+                                      _p(o), _p(d)))
+        return o, d
 
     def ray_for_pixel(self, x, y):
         o, d = np.zeros(4, dtype=f32), np.zeros(4, dtype=f32)

@@ -34,6 +34,7 @@
 #include "rtc_kernel_core.h"
 #include "rtc_hits.h"
 #include "rtc_supersample.h"
+#include "rtc_lens.h"
 #include "rtc_trace.h"
 #include "rtc_adaptive.h"
 #include "rtc_reorder.h"
@@ -122,6 +123,10 @@ struct rtc_ctx {
     // Supersampling (rtc_ctx_set_scene_ss; rtc_supersample.h): 1, or k = 2 / 4 -- `hdr` is then the FINE camera's, and everything that
     // plans, schedules and feeds back does so in fine space; only the canvas and rtc_stats.rows speak of the output frame
     uint32_t ss_k = 1u;
+    // A thin lens (rtc_ctx_set_scene_lens; rtc_lens.h): the context is a supersampled one in every respect but its kernel -- the
+    // lens kernel of the same factor -- and the three words that kernel takes; a focus pull replaces the words and nothing else
+    bool lens_mode = false;
+    rtc_lens lens = {0.0f, 1.0f, 0u};
     float4* d_soa = nullptr;
     size_t soa_cap = 0;  // float4 entries
     float* d_texels = nullptr;  // UVImage canvases (RGB f32), grow-only
@@ -374,8 +379,14 @@ std::string jit_cache_dir(const Policy& P) {  // RTC_AMD_JIT_CACHE=<dir>, or 0 /
     return lib_dir() + "/jit_cache";
 }
 
-// The text of the header beside the core that a kind's kernel includes ("" for the frame's own)
-const char* beside_text(JitKind kind) { return kind == JitKind::SS ? k_ss_src : kind == JitKind::TRACE ? k_trace_src : kind == JitKind::ADAPTIVE ? k_adaptive_src : ""; }
+// The text of the header beside the core that a kind's kernel includes ("" for the frame's own) -- the lens kernel's: of the two,
+// rtc_supersample.h and then rtc_lens.h, which includes it (rtc_jit.h: what a hash folds in)
+std::string beside_text(JitKind kind) {
+    if (kind == JitKind::LENS) return std::string(k_ss_src) + k_lens_src;
+    return kind == JitKind::SS ? k_ss_src : kind == JitKind::TRACE ? k_trace_src : kind == JitKind::ADAPTIVE ? k_adaptive_src : "";
+}
+// The sizes of the kernels' argument blocks, which a key carries
+constexpr JitArgSizes k_jit_arg_sizes = {sizeof(RenderArgs), sizeof(TraceArgs), sizeof(AdaptiveRefineArgs), sizeof(LensRenderArgs)};
 // identifies the ahead-of-time kernels of this build: the source they were compiled from
 std::string aot_kernel_id(JitKind kind, uint32_t k = 1u) { return rtc::aot_kernel_id(kind, k, k_core_src, beside_text(kind)); }
 
@@ -399,17 +410,20 @@ rtc_status jit_get(const Policy& P, int device, const KernelVariant& v, hipFunct
         return RTC_OK;
     }
     const JitKindFacts& kind = jit_kind_facts(v.kind);
-    std::string core = k_core_src, beside = beside_text(v.kind);
+    // (`beside`: the header the kind's kernel includes; `below`: the header that one includes -- the lens kernel's rtc_supersample.h)
+    std::string core = k_core_src, beside = v.kind == JitKind::LENS ? k_lens_src : beside_text(v.kind), below = *kind.header_below ? k_ss_src : "";
     if (!P.jit_source.empty()) {  // development builds only (Policy)
         if (!read_file(P.jit_source, &core)) return fail(RTC_ERR_DEVICE, "scene specialisation: cannot read the kernel source %s", P.jit_source.c_str());
-        // (... and the header beside it from the same directory, when it is there: an experiment in either header needs no rebuild)
+        // (... and the headers beside it from the same directory, when they are there: an experiment in any of them needs no rebuild)
         const size_t slash = P.jit_source.find_last_of('/');
+        const std::string dir = slash == std::string::npos ? std::string() : P.jit_source.substr(0, slash + 1);
         std::string text;
-        if (*kind.header && read_file((slash == std::string::npos ? std::string() : P.jit_source.substr(0, slash + 1)) + kind.header, &text)) beside = text;
+        if (*kind.header && read_file(dir + kind.header, &text)) beside = text;
+        if (*kind.header_below && read_file(dir + kind.header_below, &text)) below = text;
     }
     int rtc_major = 0, rtc_minor = 0;
     (void)hiprtcVersion(&rtc_major, &rtc_minor);
-    const JitPlan plan = plan_jit(v.defs, v.kind, P.jit_flags, rtc_major, rtc_minor, {sizeof(RenderArgs), sizeof(TraceArgs), sizeof(AdaptiveRefineArgs)}, core, beside);
+    const JitPlan plan = plan_jit(v.defs, v.kind, P.jit_flags, rtc_major, rtc_minor, k_jit_arg_sizes, core, below + beside);
     if (P.jit_print) {  // development: the options, one line, as tools/spec_asm.sh takes them
         std::string line;
         for (size_t i = 5; i < plan.opts.size(); i++) line += " " + plan.opts[i];
@@ -418,9 +432,9 @@ rtc_status jit_get(const Policy& P, int device, const KernelVariant& v, hipFunct
     const std::string cache_dir = jit_cache_dir(P), cache_path = cache_dir + "/" + plan.cache_file;
     auto compile = [&](std::string* code) -> rtc_status {
         hiprtcProgram prog;
-        const char* headers[] = {core.c_str(), beside.c_str()};
-        const char* header_names[] = {"rtc_kernel_core.h", kind.header};
-        if (hiprtcCreateProgram(&prog, kind.program, "rtc_scene_spec.hip", *kind.header ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
+        const char* headers[] = {core.c_str(), beside.c_str(), below.c_str()};
+        const char* header_names[] = {"rtc_kernel_core.h", kind.header, kind.header_below};
+        if (hiprtcCreateProgram(&prog, kind.program, "rtc_scene_spec.hip", *kind.header_below ? 3 : *kind.header ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
             return fail(RTC_ERR_DEVICE, "hiprtcCreateProgram failed");
         std::vector<const char*> copts;
         for (const auto& o : plan.opts) copts.push_back(o.c_str());
@@ -752,6 +766,19 @@ static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hi
         SsRenderArgs sa;
         sa.fine = a;
         sa.out_width = a.hdr.width / c->ss_k, sa.out_rows = a.rows / c->ss_k;
+        if (c->lens_mode) {  // ... whose rays leave from a lens (rtc_lens.h)
+            LensRenderArgs la;
+            la.ss = sa;
+            // the scene-box early-out is argued for rays from the camera's origin (primary_ray): not for these
+            la.ss.fine.hdr.has_scene_box = 0u;
+            la.aperture_radius = c->lens.aperture_radius, la.focal_distance = c->lens.focal_distance, la.seed = c->lens.seed;
+            return launch_scene_kernel(spec_fn, grid, stream, la, [&] {
+                dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+                    if (c->ss_k == 2u) hipLaunchKernelGGL((lens_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, la);
+                    else hipLaunchKernelGGL((lens_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, la);
+                });
+            });
+        }
         return launch_scene_kernel(spec_fn, grid, stream, sa, [&] {
             dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
                 // (a context of the one-call seam launches the variant that stores bytes and reports its rows: rtc_supersample.h SEAM)
@@ -819,7 +846,7 @@ static rtc_status scene_kernel_for(rtc_ctx* c, rtc_ctx::SceneKernel& s, int32_t 
 // RTC_AMD_SPECIALIZE=1 and no kernel: the context has no scene.
 // (the one-call seam's variant of the supersampling kernels is a code object of its own: "aot_ss<k>_<hash>.seam")
 static std::string ctx_aot_id(const rtc_ctx* c) {
-    return aot_kernel_id(c->render.variant.kind, c->render.variant.k) + (c->seam_kernels && c->render.variant.kind == JitKind::SS ? ".seam" : "");
+    return aot_kernel_id(c->render.variant.kind, c->render.variant.k) + (c->seam_kernels && c->render.variant.kind == JitKind::SS ? ".seam" : "");  // (a lens kernel has no such variant)
 }
 static rtc_status compile_render_kernel(rtc_ctx* c, bool lazy) {
     rtc_ctx::SceneKernel& r = c->render;
@@ -859,7 +886,8 @@ static rtc_status compile_deferred(rtc_ctx* c) {
 
 // rtc_ctx_set_scene (k = 1), and rtc_ctx_set_scene_ss with the FINE camera (k = 2, 4; rtc_camera_supersampled has checked it):
 // a supersampled context flattens, plans, schedules and feeds back in fine space, with the code that exists.
-static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera* camera, uint32_t k) {
+// `lens` (rtc_ctx_set_scene_lens has checked it; k = 2, 4): the same, with the lens kernel in the supersampling kernel's place.
+static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera* camera, uint32_t k, const rtc_lens* lens = nullptr) {
     if (!c) return fail(RTC_ERR_INVALID_ARG, "ctx is NULL");
     SceneHdr hdr;
     std::vector<float4> soa;
@@ -872,13 +900,17 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     HIP_TRY(hipSetDevice(c->device));
     const bool resident = same_records(c, soa, texels);
     // the very scene that is resident (records, camera, light; the switches are the context's for life): nothing to replace
-    if (resident && c->ss_k == k && std::memcmp(&hdr, &c->hdr, sizeof(hdr)) == 0) return c->jit_deferred ? compile_deferred(c) : RTC_OK;
+    // (another lens on it -- a focus pull: three words of the next launch's arguments)
+    if (resident && c->ss_k == k && c->lens_mode == (lens != nullptr) && std::memcmp(&hdr, &c->hdr, sizeof(hdr)) == 0) {
+        if (lens) c->lens = *lens;
+        return c->jit_deferred ? compile_deferred(c) : RTC_OK;
+    }
     // Renders are asynchronous on caller streams (torch's are non-blocking: the null-stream copies below do not order
     // against them), and a render still in flight reads the records and the counters this call replaces.  Wait for
     // everything the context has launched before touching them.  (rtc.h: one stream at a time per context.)
     HIP_TRY(hipDeviceSynchronize());
     // (block lists: below; another factor is another kernel and other lane caps -- its lists start afresh)
-    const bool same_frame = c->has_scene && c->hdr.width == hdr.width && c->hdr.height == hdr.height && c->ss_k == k;
+    const bool same_frame = c->has_scene && c->hdr.width == hdr.width && c->hdr.height == hdr.height && c->ss_k == k && c->lens_mode == (lens != nullptr);
     // until the new scene is fully resident the context has none: a failed allocation below must not leave a stale
     // capacity beside a null pointer, nor a render path that believes the old scene is still there
     // (only the camera has moved -- an animation's usual frame: the records and texels that are resident stay)
@@ -900,10 +932,13 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     // that wants the scene's kernel compiles it
     c->trace.kernel.reset(trace_variant(plan));
     for (uint32_t i = 0; i < 2u; i++) c->adaptive.kernel[i].reset(refine_variant(plan, i ? 4u : 2u));
-    if (k != 1u) plan_supersampled(&plan, k, c->seam_kernels);
+    if (k != 1u) plan_supersampled(&plan, k, c->seam_kernels && !lens);
+    if (lens) plan_lens(&plan);
     c->hdr = hdr;
     c->camera = *camera;
     c->ss_k = k;
+    c->lens_mode = lens != nullptr;
+    if (lens) c->lens = *lens;
     c->n_objects = hdr.n_objects;
     c->has_scene = true;
     if (!resident) {
@@ -947,6 +982,15 @@ rtc_status rtc_ctx_set_scene_ss(rtc_ctx* c, const rtc_scene* scene, const rtc_ca
     rtc_camera fine;
     RTC_TRY(rtc_camera_supersampled(output_camera, k, &fine));
     return set_scene(c, scene, &fine, k);
+}
+
+// The argument checks come first (rtc::check_lens_args, host only: the lens, the factor, the fine frame), then the context: all of
+// them are decided before any device call.  Without a context: RTC_ERR_NO_DEVICE where there is no device to have made one on.
+rtc_status rtc_ctx_set_scene_lens(rtc_ctx* c, const rtc_scene* scene, const rtc_camera* output_camera, uint32_t k, const rtc_lens* lens) {
+    rtc_camera fine;
+    RTC_TRY(check_lens_args("rtc_ctx_set_scene_lens", output_camera, k, lens, &fine));
+    if (!c && usable_devices() <= 0) return fail(RTC_ERR_NO_DEVICE, "no HIP device visible; librtc_amd has no CPU fallback");
+    return set_scene(c, scene, &fine, k, lens);
 }
 }  // extern "C"
 
@@ -1387,7 +1431,7 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     if (ss_k != 1u) {
         // progress words and the u8 canvas (rtc_render_ss): the plain grid reports, a block-list launch is finished when its stream
         // is.  Only the kernels of the one-call seam's contexts have those paths (rtc_supersample.h SEAM).
-        if ((progress || out_u8) && !c->seam_kernels)
+        if ((progress || out_u8) && (!c->seam_kernels || c->lens_mode))
             return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render: a supersampled context renders f32 frames without progress words (bytes and progress words: rtc_render_ss)");
         const Partition o = resolve(part);
         if (o.band_rows > 0xffffffffu / ss_k) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: band_rows %u times the supersampling factor %u", o.band_rows, ss_k);
@@ -1458,7 +1502,7 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     // ---- warm up, time, launch, sum
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     HIP_TRY(next_event_pair(c, &ev));
-    RTC_TRY(warm_up(c->render, spec_fn ? (const void*)spec_fn : aot_family(c).key(ss_k, ss_k != 1u && c->seam_kernels), stream, [&] {
+    RTC_TRY(warm_up(c->render, spec_fn ? (const void*)spec_fn : aot_family(c).key(ss_k, ss_k != 1u && c->seam_kernels && !c->lens_mode, c->lens_mode), stream, [&] {
         RenderArgs w = a;
         w.rows = 0u, w.tiles = nullptr, w.wave_ticks = nullptr, w.progress = nullptr, w.done = nullptr, w.fill_wg_rows = 0u, w.swizzle = 0u, w.blocks_y = 1u;
         return launch_render(c, spec_fn, dim3(1, 1), stream, w);
@@ -1664,10 +1708,14 @@ rtc_status rtc_diag_scene_plan(const rtc_scene* scene, const rtc_camera* camera,
              p.scene_rect[3], (double)p.scene_rect_coverage, p.scene_tile_mask.size(), p.scene_tiles_w, p.scene_tiles_h, (int)p.spec_shares,
              (int)p.spec_blocks_y, (int)p.spec_rect, p.tree_waves, (int)p.wf_pays, (int)p.compile_now);
     std::string out = b;
+    // the ball triangle pre-culling is argued for (SceneHdr::has_tbox, cull_c, cull_r2): rays that start outside it do not pre-cull
+    snprintf(b, sizeof(b), "tri_cull=%u %.9g %.9g %.9g %.9g\n", hdr.has_tbox, (double)hdr.cull_c[0], (double)hdr.cull_c[1], (double)hdr.cull_c[2],
+             (double)hdr.cull_r2);
+    out += b;
     // ... and what the JIT makes of every variant (rtc_jit.h), with this process's hiprtc and the embedded source
     int major = 0, minor = 0;
     (void)hiprtcVersion(&major, &minor);
-    const JitArgSizes sizes = {sizeof(RenderArgs), sizeof(TraceArgs), sizeof(AdaptiveRefineArgs)};
+    const JitArgSizes sizes = k_jit_arg_sizes;
     out += "hiprtc=" + std::to_string(major) + "." + std::to_string(minor) + "\nkey_tail=" + jit_key_tail(JitKind::RENDER, major, minor, sizes) +
            "render_args=" + std::to_string(sizes.render) + "\ntrace_args=" + std::to_string(sizes.trace) + "\nadaptive_args=" + std::to_string(sizes.adaptive) + "\n";
     auto joined = [](const std::vector<std::string>& defs) {
@@ -1681,6 +1729,7 @@ rtc_status rtc_diag_scene_plan(const rtc_scene* scene, const rtc_camera* camera,
         const JitKindFacts& kind = jit_kind_facts(v.kind);
         out += prefix + "family_name=" + v.family_name + "\n" + prefix + "spec_name=" + v.spec_name + "\n" + prefix + "spec_defs=" + joined(v.defs);
         const JitPlan jit = plan_jit(v.defs, v.kind, P.jit_flags, major, minor, sizes, k_core_src, beside_text(v.kind));
+        if (*kind.header_below) out += prefix + "header_below=" + kind.header_below + "\n";
         out += prefix + "entry=" + jit.entry + "\n" + prefix + "header=" + kind.header + "\n" + prefix + "options=" + joined(jit.opts) + prefix + "cache_file=" +
                jit.cache_file + "\n" + prefix + "aot_id=" + aot_kernel_id(v.kind, v.k) + "\n";
         for (int depth : {16, 32}) {
@@ -1696,6 +1745,13 @@ rtc_status rtc_diag_scene_plan(const rtc_scene* scene, const rtc_camera* camera,
     add("trace_", trace_variant(p), true);
     for (uint32_t k : {2u, 4u}) add("adaptive" + std::to_string(k) + "_", refine_variant(p, k));
     for (uint32_t k : {2u, 4u}) add("ss" + std::to_string(k) + "_", render_variant(p, k));  // (of this camera as the fine one)
+    for (uint32_t k : {2u, 4u}) {  // ... and the lens kernels of a lens context (rtc_ctx_set_scene_lens), likewise
+        ScenePlan lens_plan = p;
+        plan_supersampled(&lens_plan, k);
+        plan_lens(&lens_plan);
+        add("lens" + std::to_string(k) + "_", render_variant(lens_plan), false);
+        out += "lens" + std::to_string(k) + "_args=" + std::to_string(sizes.lens) + "\n";
+    }
     if (out.size() >= cap) return fail(RTC_ERR_INVALID_ARG, "rtc_diag_scene_plan: the text needs %zu bytes", out.size() + 1);
     std::memcpy(text, out.c_str(), out.size() + 1);
     return RTC_OK;
@@ -1724,6 +1780,7 @@ rtc_status rtc_ctx_render_hits(rtc_ctx* c, const rtc_partition* part, const rtc_
     HitPlanes planes;
     if (!hit_planes_view(d_out, &planes)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: no plane requested");
     if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: no scene/camera set");
+    if (c->lens_mode) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_hits: the context renders through a lens (%u x %u rays per pixel): a first hit per output pixel is not defined", c->ss_k, c->ss_k);
     if (c->ss_k != 1u) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_hits: the context is supersampled (%u x %u rays per pixel): a first hit per output pixel is not defined", c->ss_k, c->ss_k);
     const Partition q = resolve(part);
     if (q.part >= q.n_parts) return fail(RTC_ERR_INVALID_ARG, "partition %u of %u", q.part, q.n_parts);
@@ -2138,6 +2195,7 @@ rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float 
     if (depth < 0 || depth > RTC_MAX_DEPTH) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: depth %d outside [0, %d]", depth, RTC_MAX_DEPTH);
     if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: ctx is NULL");
     if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: no scene/camera set");
+    if (c->lens_mode) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_adaptive: a lens context renders every pixel with k x k lens rays already (adaptive lens frames are not defined)");
     if (c->ss_k != 1u) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_adaptive: a supersampled context renders every pixel with k x k rays already");
     rtc_camera fine;
     RTC_TRY(rtc_camera_supersampled(&c->camera, k, &fine));  // (the fine frame's limits: 2^32 pixels, 2^17 rows)

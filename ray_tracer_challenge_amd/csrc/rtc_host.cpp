@@ -605,6 +605,76 @@ void rtc_ray_for_pixel(const rtc_camera* c, uint32_t x, uint32_t y, float origin
     norm4(diff, direction);
 }
 
+// ---- the thin lens (include/rtc.h rtc_lens_rays; the kernel's restatement: rtc_lens.h lens_ray) -------------------------
+// the keyed hash of RTC_JITTER_HASHED lights (rtc_kernel_core.h mix32, jitter_base, jitter_value)
+static inline uint32_t mix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+static inline float lens_jitter(uint32_t seed, uint32_t key, uint32_t path) {
+    const uint32_t h = mix32(mix32(key ^ seed) + path * 0x9E3779B9u);
+    return (float)((h >> 9) + 1u) * 1.1920928955078125e-7f;  // ((h >> 9) + 1) * 2^-23: exact
+}
+
+}  // extern "C"
+rtc_status rtc::check_lens_args(const char* who, const rtc_camera* output_camera, uint32_t k, const rtc_lens* lens, rtc_camera* fine) {
+    if (!lens) return fail(RTC_ERR_INVALID_ARG, "%s: lens is NULL", who);
+    if (!output_camera) return fail(RTC_ERR_INVALID_ARG, "%s: camera is NULL", who);
+    if (k != 2u && k != 4u) return fail(RTC_ERR_INVALID_ARG, "%s: supersampling factor %u: a lens frame takes 2 or 4 rays per pixel side", who, k);
+    if (!(lens->aperture_radius >= 0.0f) || !std::isfinite(lens->aperture_radius))
+        return fail(RTC_ERR_INVALID_ARG, "%s: aperture radius %g: must be finite and >= 0", who, (double)lens->aperture_radius);
+    if (!(lens->focal_distance > 0.0f) || !std::isfinite(lens->focal_distance))
+        return fail(RTC_ERR_INVALID_ARG, "%s: focal distance %g: must be finite and > 0", who, (double)lens->focal_distance);
+    return rtc_camera_supersampled(output_camera, k, fine);
+}
+extern "C" {
+
+rtc_status rtc_lens_rays(const rtc_camera* output_camera, uint32_t k, const rtc_lens* lens, uint32_t y0, uint32_t n_rows, float* origins,
+                         float* directions) {
+    rtc_camera c;
+    const rtc_status st = check_lens_args("rtc_lens_rays", output_camera, k, lens, &c);
+    if (st != RTC_OK) return st;
+    if ((uint64_t)y0 + n_rows > c.height) return fail(RTC_ERR_INVALID_ARG, "rtc_lens_rays: rows [%u, %llu) of a fine frame of %u", y0, (unsigned long long)y0 + n_rows, c.height);
+    const float R = lens->aperture_radius, f = lens->focal_distance, kf = (float)k;
+    const float right[3] = {c.inv[0], c.inv[4], c.inv[8]}, up[3] = {c.inv[1], c.inv[5], c.inv[9]};
+    const float zero[4] = {0.0f, 0.0f, 0.0f, 1.0f};
+    float o[4];
+    mat_vec4(c.inv, zero, o);  // camera.rs:70
+    for (uint32_t row = 0; row < n_rows; row++) {
+        const uint32_t y = y0 + row;
+        for (uint32_t x = 0; x < c.width; x++) {
+            // 1. camera.rs:60-69
+            const float x_offset = ((float)x + 0.5f) * c.pixel_size, y_offset = ((float)y + 0.5f) * c.pixel_size;
+            const float cam_point[4] = {c.half_width - x_offset, c.half_height - y_offset, -1.0f, 1.0f};
+            float p[4];
+            mat_vec4(c.inv, cam_point, p);
+            // 2. - 3.
+            const uint32_t key = y * c.width + x;
+            const float ju = lens_jitter(lens->seed, key, 1u), jv = lens_jitter(lens->seed, key, 2u);
+            const uint32_t i = x % k, j = y % k, ci = j, cj = k - 1u - i;
+            const float u = ((float)ci + ju) / kf, v = ((float)cj + jv) / kf;
+            const float r = R * sqrtf(u), theta = 6.2831855f * v;
+            const float lx = r * cosf(theta), ly = r * cosf(theta - 1.5707964f);
+            // 4. - 5.
+            float lo[3], d[3];
+            for (int a = 0; a < 3; a++) {
+                lo[a] = (o[a] + right[a] * lx) + up[a] * ly;
+                const float focus = o[a] + (p[a] - o[a]) * f;
+                d[a] = focus - lo[a];
+            }
+            const float m = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+            const size_t at = ((size_t)row * c.width + x) * 4u;
+            if (origins) origins[at] = lo[0], origins[at + 1] = lo[1], origins[at + 2] = lo[2], origins[at + 3] = 1.0f;
+            if (directions) directions[at] = d[0] / m, directions[at + 1] = d[1] / m, directions[at + 2] = d[2] / m, directions[at + 3] = 0.0f;
+        }
+    }
+    return RTC_OK;
+}
+
 uint32_t rtc_partition_rows(uint32_t height, const rtc_partition* part) { return partition_rows(height, part); }
 
 // ---- Canvas::to_ppm, canvas.rs:39-96 ------------------------------------------

@@ -82,6 +82,10 @@ inline uint32_t partition_rows(uint32_t height, const rtc_partition* p) {
     return rows;
 }
 
+// The host-side argument checks of a lens frame (rtc_lens_rays, rtc_ctx_set_scene_lens; rtc_host.cpp): the lens, the factor, the
+// fine frame -> *fine = rtc_camera_supersampled(output_camera, k).  `who`: the entry point, for the message.
+rtc_status check_lens_args(const char* who, const rtc_camera* output_camera, uint32_t k, const rtc_lens* lens, rtc_camera* fine);
+
 // Hooks of rtc_device.hip for rtc_render_ex (rtc_oneshot.hip): a frame rendered as several launches, each with a
 // counter slot of its own.  `stream`: a hipStream_t.
 constexpr uint32_t CTX_TOTAL_SLOTS = 64;

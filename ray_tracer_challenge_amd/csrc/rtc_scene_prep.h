@@ -1332,7 +1332,10 @@ struct KernelFamily {
     bool simple;
     // (no code object's address; ss_k: the supersampling instantiations of the family, rtc_supersample.h, are kernels of their own)
     // seam: the family's ss_seam_render_kernel instantiations, the one-call seam's variant of the supersampling kernels
-    const void* key(uint32_t ss_k = 1u, bool seam = false) const { return (const void*)(uintptr_t)(0x1000 + (seam ? 0x800 : 0) + 0x100 * ss_k + 2 * (nobj + 1) + (simple ? 1 : 0)); }
+    // lens: the family's lens_render_kernel instantiations (rtc_lens.h)
+    const void* key(uint32_t ss_k = 1u, bool seam = false, bool lens = false) const {
+        return (const void*)(uintptr_t)(0x1000 + (lens ? 0x2000 : 0) + (seam ? 0x800 : 0) + 0x100 * ss_k + 2 * (nobj + 1) + (simple ? 1 : 0));
+    }
     std::string name(const char* tree_how = "tree") const {
         if (nobj < 0) return std::string("render_kernel<") + tree_how + ">";
         return "render_kernel<" + std::to_string(nobj) + (simple ? ",simple>" : ",general>");
@@ -1468,6 +1471,7 @@ struct ScenePlan {
     std::vector<std::string> spec_defs;
     std::string spec_name;
     uint32_t ss_k = 1u;  // the frame's kernel is the supersampling one of this factor (plan_supersampled)
+    bool lens = false;   // ... or the lens kernel of this factor (plan_lens)
     bool compile_now = false;
     // ... and the policy's two exceptions to "from 2^18 pixels", which rtc_ctx_trace applies to its number of rays: worlds with divided
     // meshes are compiled whatever the size, a mixed list of many objects (and a world without objects) never
@@ -1779,7 +1783,7 @@ inline std::string with_prefix(const std::string& name, const char* from, const 
 // The frame's kernel of a context of factor k (rtc_supersample.h; 1: the plan's own): ss_render_kernel<...;ss=k>.  The
 // supersampling body has neither the loop over blocks nor the rectangle's offsets.
 inline KernelVariant render_variant(const ScenePlan& p, uint32_t k = 1u) {
-    KernelVariant v = {p.spec_defs, p.family_name, p.spec_name, p.ss_k == 1u ? JitKind::RENDER : JitKind::SS, p.ss_k};
+    KernelVariant v = {p.spec_defs, p.family_name, p.spec_name, p.ss_k == 1u ? JitKind::RENDER : p.lens ? JitKind::LENS : JitKind::SS, p.ss_k};
     if (k == 1u) return v;
     v.kind = JitKind::SS, v.k = k;
     for (std::string* name : {&v.family_name, &v.spec_name})
@@ -1845,6 +1849,17 @@ inline void plan_supersampled(ScenePlan* p, uint32_t k, bool seam = false) {
     p->scene_rect[0] = p->scene_rect[1] = p->scene_rect[2] = p->scene_rect[3] = 0u;
     p->spec_blocks_y = p->spec_rect = false;
     p->wf_pays = false;
+}
+// The plan of a lens context (rtc_lens.h; `p`: plan_supersampled of the same k, never the seam's): the supersampled plan with the
+// lens kernel in the supersampling kernel's place -- lens_render_kernel<...;ss=k> / lens_render_kernel_spec[...;ss=k;lens],
+// -DRTC_SPEC_LENS=1 last.  What plan_supersampled declines stays declined.  (The scene-box early-out is switched off in the
+// launch's header, not here: has_scene_box is run-time data.)
+inline void plan_lens(ScenePlan* p) {
+    if (!p->spec_defs.empty()) p->spec_defs.push_back("-DRTC_SPEC_LENS=1");
+    p->family_name = with_prefix(p->family_name, "ss_render_kernel<", "lens_render_kernel<");
+    p->spec_name = with_prefix(p->spec_name, "ss_render_kernel_spec[", "lens_render_kernel_spec[");
+    if (!p->spec_name.empty()) p->spec_name.insert(p->spec_name.size() - 1, ";lens");
+    p->lens = true;
 }
 
 }  // namespace rtc

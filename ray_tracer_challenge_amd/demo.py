@@ -35,7 +35,14 @@ def main(argv=None):
     ap.add_argument("--out", help="write the PPM here instead of stdout")
     ap.add_argument("--supersample", type=int, choices=(1, 2, 4), default=1, metavar="K",
                     help="K x K rays per pixel, reduced in the render kernel (1, 2 or 4; default 1: the demo's own frame)")
+    ap.add_argument("--aperture", type=float, default=None, metavar="R",
+                    help="depth of field: the radius of a thin lens (world units); needs --supersample 2 or 4 and --focus")
+    ap.add_argument("--focus", type=float, default=None, metavar="D", help="... and the distance in front of the camera that is sharp")
     a = ap.parse_args(argv)
+    if (a.aperture is None) != (a.focus is None):
+        ap.error("--aperture and --focus go together")
+    if a.aperture is not None and a.supersample == 1:
+        ap.error("--aperture needs --supersample 2 or 4: the lens is sampled by a pixel's K x K rays")
     fn, size, file_kw = DEMOS[a.demo]
     if a.size:
         size = tuple(int(v) for v in a.size.lower().split("x"))
@@ -48,10 +55,20 @@ def main(argv=None):
     t0 = time.time()
     world, camera, depth = fn(size[0], size[1], **kw)
     t1 = time.time()
-    canvas = camera.render(world, depth) if a.supersample == 1 else camera.render(world, depth, supersample=a.supersample)
+    if a.aperture is not None:  # a lens frame: the persistent context's (the one-call seam has no lens)
+        from .api import Canvas, Lens
+        from .renderer import Renderer
+        r = Renderer(world, camera, supersample=a.supersample, lens=Lens(a.aperture, a.focus))
+        frame = r.render(depth)
+        st = r.stats()
+        canvas = Canvas(camera.width, camera.height)
+        canvas.data[...] = frame.cpu().numpy()
+        r.close()
+    else:
+        canvas = camera.render(world, depth) if a.supersample == 1 else camera.render(world, depth, supersample=a.supersample)
+        st = camera.last_stats
     ppm = canvas.to_ppm()
     t2 = time.time()
-    st = camera.last_stats
     print("scene built in %.3f s; rendered %dx%d (%d rays, kernel %.3f ms) and formatted in %.3f s"
           % (t1 - t0, size[0], size[1], st["rays"], st["kernel_ms"], t2 - t1), file=sys.stderr)
     if a.out:

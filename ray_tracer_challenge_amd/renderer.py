@@ -14,9 +14,11 @@ from . import _lib as L
 
 class Renderer:
     """supersample = k (1, 2 or 4): k x k rays per pixel of `camera`, reduced in the render kernel (rtc_ctx_set_scene_ss).
-    width / height, alloc() and rows() speak of the output frame -- `camera`'s -- whatever k is."""
+    width / height, alloc() and rows() speak of the output frame -- `camera`'s -- whatever k is.
+    lens = api.Lens(...) with supersample = 2 or 4: depth of field -- the k x k rays of a pixel leave from k x k points of the
+    lens (rtc_ctx_set_scene_lens); render_hits and render_adaptive are refused on such a renderer."""
 
-    def __init__(self, world, camera, device=None, supersample=1):
+    def __init__(self, world, camera, device=None, supersample=1, lens=None):
         if not torch.cuda.is_available():
             raise L.RtcError(L.RTC_ERR_NO_DEVICE, "no GPU visible to torch; the render path has no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
@@ -26,26 +28,35 @@ class Renderer:
         L.check(self._lib.rtc_ctx_create(self.device.index, C.byref(self._ctx)))
         self._keep = None
         self.supersample = 1
-        self.set_scene(world, camera, supersample=supersample)
+        self.lens = None
+        self.set_scene(world, camera, supersample=supersample, lens=lens)
 
-    def _set(self, cs, camera, k):
-        if k == 1:
+    def _set(self, cs, camera, k, lens=None):
+        if lens is not None:  # (the library checks the factor: a lens frame takes 2 or 4)
+            L.check(self._lib.rtc_ctx_set_scene_lens(self._ctx, C.byref(cs.scene), C.byref(camera._cam), k, C.byref(lens._c)), self._lib)
+        elif k == 1:
             L.check(self._lib.rtc_ctx_set_scene(self._ctx, C.byref(cs.scene), C.byref(camera._cam)), self._lib)
         else:
             L.check(self._lib.rtc_ctx_set_scene_ss(self._ctx, C.byref(cs.scene), C.byref(camera._cam), k), self._lib)
         self._keep = (cs, camera)
         self.supersample = k
+        self.lens = lens
         self.width, self.height = camera.width, camera.height
 
-    def set_scene(self, world, camera, supersample=1):
-        """supersample=1 (the default) leaves supersampled mode."""
-        self._set(world._c(), camera, int(supersample))
+    def set_scene(self, world, camera, supersample=1, lens=None):
+        """supersample=1 (the default) leaves supersampled mode, lens=None (the default) lens mode."""
+        self._set(world._c(), camera, int(supersample), lens)
 
     def set_camera(self, camera):
         """Another camera on the world that is resident (an animation's usual frame): the world is not flattened again on the
         Python side, and the library, finding the records unchanged, uploads none of them.
-        The supersampling factor stays."""
-        self._set(self._keep[0], camera, self.supersample)
+        The supersampling factor and the lens stay."""
+        self._set(self._keep[0], camera, self.supersample, self.lens)
+
+    def set_lens(self, lens):
+        """Another lens on the resident world and camera (a focus pull): nothing is flattened or uploaded.  The renderer must be
+        supersampled (2 or 4); lens=None leaves lens mode for the plain supersampled frame."""
+        self._set(self._keep[0], self._keep[1], self.supersample, lens)
 
     def close(self):
         if self._ctx:
