@@ -37,7 +37,8 @@ extern "C" {
                              ray reordering: rtc_ctx_ray_order, rtc_ctx_trace_reordered, rtc_ctx_reorder_stats and the struct
                              rtc_reorder_stats, additions likewise; supersampling through the one-call seam: rtc_render_ss, one
                              entry point more -- rtc_opts and rtc_stats are what they were; the thin-lens camera: rtc_lens_rays,
-                             rtc_ctx_set_scene_lens and the struct rtc_lens, additions likewise) */
+                             rtc_ctx_set_scene_lens and the struct rtc_lens, additions likewise; the lens through the one-call
+                             seam: rtc_render_lens, one entry point more, no struct changed) */
 /* reflection_recursion_depth (camera.rs:76: any i16; reference default 5, constants.rs:4; its author renders
  * reflect_refract at 20).  Accepted: 0 .. RTC_MAX_DEPTH.  The kernels keep one frame per suspended shade_hit
  * (world.rs:62-86); up to RTC_STACK_DEPTH_BASE levels every kernel has them, above that the scene's kernel is compiled
@@ -396,7 +397,29 @@ rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32
  * however many chunks its rows leave in; kernel_ms and gather_ms as for rtc_render_ex. */
 rtc_status rtc_render_ss(const rtc_scene* scene, const rtc_camera* output_camera, int32_t depth, uint32_t k,
                          const rtc_opts* opts, void* out, rtc_stats* stats);
-/* Frees everything rtc_render / rtc_render_ex / rtc_render_ss keep between calls (all devices). */
+/* rtc_render_ss through a thin lens: depth of field in one call.  The frame is the one rtc_ctx_set_scene_lens defines (below: the
+ * box filter of the fine frame whose pixel is World::color_at of the ray rtc_lens_rays gives it, jitter key y * k W + x, the fine
+ * frame's last row and column zero), with everything rtc_render_ss offers: `out` is H x W x 3 f32, or bytes with opts->quantize
+ * (scale_color of the reduced colour); pageable, page-locked or device memory (opts->out_on_device); opts->band_rows counts OUTPUT
+ * rows (0 -> 64), the bands are dealt round-robin over opts->devices (an entry may repeat and may own no row: a ray depends only on
+ * its global fine (x, y), so any split assembles to the same frame); the rows leave chunk by chunk while later rows render.
+ * RTC_ERR_INVALID_ARG with a message, decided on the host before any device call, in this order: null `out` or camera, empty
+ * canvas (rtc_render_ss's checks), then a null lens (an error, not rtc_render_ss), k not 2 or 4 (k = 1 with a lens is an error),
+ * aperture_radius negative or not finite, focal_distance <= 0 or not finite, a fine frame rtc_camera_supersampled refuses.  A
+ * valid call on a machine without a device: RTC_ERR_NO_DEVICE.
+ * The per-device state is the seam's own: calls of rtc_render_ex, rtc_render_ss and rtc_render_lens of one scene may alternate,
+ * each gives its own frame, and rtc_render_release frees it.  A second rtc_render_lens of the same scene, camera and k with
+ * another lens is a focus pull: nothing is planned, compiled or uploaded (rtc_ctx_set_scene's rule for the resident scene) -- three words of the
+ * launch's arguments change.  Its contexts launch a variant of the lens kernels of their own (bytes, write-through stores, progress
+ * words; csrc/rtc_lens_seam.h), never the kernels of rtc_ctx_set_scene_lens's contexts: named "lens_seam_render_kernel<...;ss=k>" /
+ * "lens_render_kernel_spec[...;ss=k;lens;seam]", ids "aot_lens<k>_<hash>.seam" -- the hash is the variant's own: it folds in the
+ * text of rtc_lens_seam.h after the two headers the persistent lens kernel's hash folds in -- / "spec_..." (one option more,
+ * -DRTC_SPEC_LENS_SEAM=1, so another cache entry).  Which kernel renders a scene's first frame: as for rtc_render_ex
+ * (RTC_AMD_SPECIALIZE).  A launch drawn from a block list cannot report its rows: its chunks leave when its stream is done.
+ * stats: as for rtc_render_ss -- pixels = (k W - 1)(k H - 1), rows = H, launches = one per entry of opts->devices that owns a row. */
+rtc_status rtc_render_lens(const rtc_scene* scene, const rtc_camera* output_camera, int32_t depth, uint32_t k, const rtc_lens* lens,
+                           const rtc_opts* opts, void* out, rtc_stats* stats);
+/* Frees everything rtc_render / rtc_render_ex / rtc_render_ss / rtc_render_lens keep between calls (all devices). */
 void rtc_render_release(void);
 /* Page-locked host memory (hipHostMalloc): an `out` buffer allocated here is filled by DMA straight from the device. */
 void* rtc_host_alloc(size_t bytes);
@@ -447,7 +470,8 @@ rtc_status rtc_ctx_set_scene_ss(rtc_ctx* ctx, const rtc_scene* scene, const rtc_
  * rtc_ctx_is_shadowed and rtc_ctx_camera_rays are what they are on any context.
  * RTC_ERR_INVALID_ARG with a message, decided on the host before any device call and before the context is looked at: a null lens
  * or camera, k not 2 or 4, aperture_radius negative or not finite, focal_distance <= 0 or not finite, a fine frame
- * rtc_camera_supersampled refuses.  Not offered: lens frames through rtc_render_*, rtc.hpp, several devices. */
+ * rtc_camera_supersampled refuses.  The one-call seam renders through a lens with rtc_render_lens (above): the same frame, f32 or
+ * bytes, host buffer out, several devices.  Not offered: adaptive lens frames, lens frames in dist.py. */
 rtc_status rtc_ctx_set_scene_lens(rtc_ctx* ctx, const rtc_scene* scene, const rtc_camera* output_camera, uint32_t k,
                                   const rtc_lens* lens);
 /* Rows this partition produces (sum of its bands' heights). */

@@ -439,6 +439,13 @@ inline Pattern align_check_cubic_map() {  // get_align_check_cubic_map_pattern, 
 }
 
 // ---- camera.rs ------------------------------------------------------------------------------------
+// A thin lens in front of a camera (rtc_lens; Camera::render_lens): rays leave from a disc of aperture_radius around the camera's
+// origin and meet at focal_distance; seed: of the lens points' jitter.  The library checks it where it is used.
+struct Lens {
+    float aperture_radius = 0.0f, focal_distance = 1.0f;
+    uint32_t seed = 0u;
+};
+
 struct Camera {
     rtc_camera c;
     rtc_stats last_stats{};
@@ -491,6 +498,20 @@ struct Camera {
         rtc_opts opts{devices.data(), (uint32_t)devices.size(), 0u, 0, 0};
         Canvas canvas(c.width, c.height);
         check(rtc_render_ss(&scene, &c, reflection_recursion_depth, k, &opts, canvas.data.data(), &last_stats));
+        return canvas;
+    }
+    // ... and through a thin lens: depth of field (rtc_render_lens) -- k x k rays per pixel (k = 2 or 4) that leave from k x k points
+    // of the lens and meet at its focal distance; the canvas is this camera's width x height
+    Canvas render_lens(World world, int16_t reflection_recursion_depth, uint32_t k, Lens lens, const std::vector<int32_t>& devices = {0}) {
+        std::vector<rtc_object> objs;
+        std::vector<rtc_group> groups;
+        for (Shape& s : world.objects) flatten(s, objs, groups);
+        rtc_scene scene{(uint32_t)objs.size(), objs.data(), world.light ? &world.light->l : nullptr,
+                        (uint32_t)groups.size(), groups.data()};
+        rtc_opts opts{devices.data(), (uint32_t)devices.size(), 0u, 0, 0};
+        rtc_lens l{lens.aperture_radius, lens.focal_distance, lens.seed};
+        Canvas canvas(c.width, c.height);
+        check(rtc_render_lens(&scene, &c, reflection_recursion_depth, k, &l, &opts, canvas.data.data(), &last_stats));
         return canvas;
     }
 };

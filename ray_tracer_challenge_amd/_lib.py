@@ -168,6 +168,8 @@ SIGNATURES = {
                                 C.POINTER(rtc_stats)]),
     "rtc_render_ss": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.c_uint32, C.POINTER(rtc_opts), C.c_void_p,
                                 C.POINTER(rtc_stats)]),
+    "rtc_render_lens": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.c_uint32, C.POINTER(rtc_lens), C.POINTER(rtc_opts),
+                                  C.c_void_p, C.POINTER(rtc_stats)]),
     "rtc_render_release": (None, []),
     "rtc_host_alloc": (C.c_void_p, [C.c_size_t]),
     "rtc_host_free": (None, [C.c_void_p]),

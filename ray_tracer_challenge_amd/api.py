@@ -1022,17 +1022,23 @@ class Camera:
         L.lib().rtc_ray_for_pixel(C.byref(self._cam), int(x), int(y), _p(o), _p(d))
         return o, d
 
-    def render(self, world, reflection_recursion_depth, device=0, devices=None, quantize=False, band_rows=0, out=None, supersample=1):
+    def render(self, world, reflection_recursion_depth, device=0, devices=None, quantize=False, band_rows=0, out=None, supersample=1, lens=None):
         """Camera::render (camera.rs:76-91) on the MI355X -> Canvas.
 
         devices: the GPUs to split the image over (rtc_render_ex; default: [device]).  quantize: return the (h, w, 3) u8
         array of scale_color'd channels (canvas.rs:39-43) instead of a Canvas.  out: a caller-provided array to fill.
         supersample: 1, or k = 2 / 4 for k x k rays per pixel reduced in the kernel (rtc_render_ss): the frame of
         Renderer(world, self, supersample=k), the box filter of self.supersampled(k)'s frame; band_rows counts this camera's
-        rows either way, and last_stats' rays / shaded_hits / pixels are then the fine frame's."""
+        rows either way, and last_stats' rays / shaded_hits / pixels are then the fine frame's.
+        lens: a Lens -- depth of field (rtc_render_lens): the frame of Renderer(world, self, supersample=k, lens=lens); it takes
+        supersample = 2 or 4."""
         k = int(supersample)
         if k not in (1, 2, 4):
             raise ValueError("supersample must be 1, 2 or 4, not %r" % (supersample,))
+        if lens is not None and not isinstance(lens, Lens):
+            raise TypeError("lens must be a Lens, not %r" % (lens,))
+        if lens is not None and k not in (2, 4):
+            raise ValueError("a lens frame takes supersample = 2 or 4, not %r" % (supersample,))
         devs = [int(device)] if devices is None else [int(d) for d in devices]
         dtype = np.uint8 if quantize else f32
         img = np.zeros((self.height, self.width, 3), dtype=dtype) if out is None else out
@@ -1044,7 +1050,10 @@ class Camera:
         _seam_follows_environment()
         arr = (C.c_int32 * len(devs))(*devs)
         opts = L.rtc_opts(arr, len(devs), int(band_rows), 1 if quantize else 0, 0)
-        if k == 1:
+        if lens is not None:
+            L.check(L.lib().rtc_render_lens(C.byref(cs.scene), C.byref(self._cam), int(reflection_recursion_depth), k, C.byref(lens._c),
+                                            C.byref(opts), img.ctypes.data_as(C.c_void_p), C.byref(stats)))
+        elif k == 1:
             L.check(L.lib().rtc_render_ex(C.byref(cs.scene), C.byref(self._cam), int(reflection_recursion_depth), C.byref(opts),
                                           img.ctypes.data_as(C.c_void_p), C.byref(stats)))
         else:

@@ -35,6 +35,7 @@
 #include "rtc_hits.h"
 #include "rtc_supersample.h"
 #include "rtc_lens.h"
+#include "rtc_lens_seam.h"
 #include "rtc_trace.h"
 #include "rtc_adaptive.h"
 #include "rtc_reorder.h"
@@ -167,7 +168,8 @@ struct rtc_ctx {
     int tree_waves = 6;  // waves per SIMD the scene's tree kernel was compiled for (rtc_ctx_set_scene)
     bool lazy_jit = false;      // a context of the one-call seam (rtc::ctx_mark_one_shot): see jit_get
     // ... and what else such a context is: supersampled, its kernels are the variant that stores bytes and reports its rows
-    // (rtc_supersample.h SEAM: ss_seam_render_kernel<...>, -DRTC_SPEC_SS_SEAM=1), and ctx_render_slot accepts out_u8 / progress
+    // (rtc_supersample.h SEAM: ss_seam_render_kernel<...>, -DRTC_SPEC_SS_SEAM=1; with a lens rtc_lens_seam.h: lens_seam_render_kernel<...>,
+    // -DRTC_SPEC_LENS_SEAM=1), and ctx_render_slot accepts out_u8 / progress
     bool seam_kernels = false;
     bool jit_deferred = false;  // the resident scene's kernel was left uncompiled by its first sighting: the next render of this scene compiles it
     std::vector<uint8_t> heavy_tiles;
@@ -380,9 +382,11 @@ std::string jit_cache_dir(const Policy& P) {  // RTC_AMD_JIT_CACHE=<dir>, or 0 /
 }
 
 // The text of the header beside the core that a kind's kernel includes ("" for the frame's own) -- the lens kernel's: of the two,
-// rtc_supersample.h and then rtc_lens.h, which includes it (rtc_jit.h: what a hash folds in)
+// rtc_supersample.h and then rtc_lens.h, which includes it; the seam's lens kernel's: of the three, rtc_lens_seam.h last
+// (rtc_jit.h: what a hash folds in)
 std::string beside_text(JitKind kind) {
     if (kind == JitKind::LENS) return std::string(k_ss_src) + k_lens_src;
+    if (kind == JitKind::LENS_SEAM) return std::string(k_ss_src) + k_lens_src + k_lens_seam_src;
     return kind == JitKind::SS ? k_ss_src : kind == JitKind::TRACE ? k_trace_src : kind == JitKind::ADAPTIVE ? k_adaptive_src : "";
 }
 // The sizes of the kernels' argument blocks, which a key carries
@@ -410,8 +414,11 @@ rtc_status jit_get(const Policy& P, int device, const KernelVariant& v, hipFunct
         return RTC_OK;
     }
     const JitKindFacts& kind = jit_kind_facts(v.kind);
-    // (`beside`: the header the kind's kernel includes; `below`: the header that one includes -- the lens kernel's rtc_supersample.h)
-    std::string core = k_core_src, beside = v.kind == JitKind::LENS ? k_lens_src : beside_text(v.kind), below = *kind.header_below ? k_ss_src : "";
+    // (`beside`: the header the kind's kernel includes; `below`: the header that one includes -- the lens kernel's rtc_supersample.h;
+    // the seam's lens kernel: rtc_lens_seam.h, rtc_lens.h below it and rtc_supersample.h below that, `below2`)
+    const bool lens_seam = v.kind == JitKind::LENS_SEAM;
+    std::string core = k_core_src, beside = lens_seam ? k_lens_seam_src : v.kind == JitKind::LENS ? k_lens_src : beside_text(v.kind);
+    std::string below = lens_seam ? k_lens_src : *kind.header_below ? k_ss_src : "", below2 = *kind.header_below2 ? k_ss_src : "";
     if (!P.jit_source.empty()) {  // development builds only (Policy)
         if (!read_file(P.jit_source, &core)) return fail(RTC_ERR_DEVICE, "scene specialisation: cannot read the kernel source %s", P.jit_source.c_str());
         // (... and the headers beside it from the same directory, when they are there: an experiment in any of them needs no rebuild)
@@ -420,10 +427,11 @@ rtc_status jit_get(const Policy& P, int device, const KernelVariant& v, hipFunct
         std::string text;
         if (*kind.header && read_file(dir + kind.header, &text)) beside = text;
         if (*kind.header_below && read_file(dir + kind.header_below, &text)) below = text;
+        if (*kind.header_below2 && read_file(dir + kind.header_below2, &text)) below2 = text;
     }
     int rtc_major = 0, rtc_minor = 0;
     (void)hiprtcVersion(&rtc_major, &rtc_minor);
-    const JitPlan plan = plan_jit(v.defs, v.kind, P.jit_flags, rtc_major, rtc_minor, k_jit_arg_sizes, core, below + beside);
+    const JitPlan plan = plan_jit(v.defs, v.kind, P.jit_flags, rtc_major, rtc_minor, k_jit_arg_sizes, core, below2 + below + beside);
     if (P.jit_print) {  // development: the options, one line, as tools/spec_asm.sh takes them
         std::string line;
         for (size_t i = 5; i < plan.opts.size(); i++) line += " " + plan.opts[i];
@@ -432,9 +440,9 @@ rtc_status jit_get(const Policy& P, int device, const KernelVariant& v, hipFunct
     const std::string cache_dir = jit_cache_dir(P), cache_path = cache_dir + "/" + plan.cache_file;
     auto compile = [&](std::string* code) -> rtc_status {
         hiprtcProgram prog;
-        const char* headers[] = {core.c_str(), beside.c_str(), below.c_str()};
-        const char* header_names[] = {"rtc_kernel_core.h", kind.header, kind.header_below};
-        if (hiprtcCreateProgram(&prog, kind.program, "rtc_scene_spec.hip", *kind.header_below ? 3 : *kind.header ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
+        const char* headers[] = {core.c_str(), beside.c_str(), below.c_str(), below2.c_str()};
+        const char* header_names[] = {"rtc_kernel_core.h", kind.header, kind.header_below, kind.header_below2};
+        if (hiprtcCreateProgram(&prog, kind.program, "rtc_scene_spec.hip", *kind.header_below2 ? 4 : *kind.header_below ? 3 : *kind.header ? 2 : 1, headers, header_names) != HIPRTC_SUCCESS)
             return fail(RTC_ERR_DEVICE, "hiprtcCreateProgram failed");
         std::vector<const char*> copts;
         for (const auto& o : plan.opts) copts.push_back(o.c_str());
@@ -774,7 +782,10 @@ static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hi
             la.aperture_radius = c->lens.aperture_radius, la.focal_distance = c->lens.focal_distance, la.seed = c->lens.seed;
             return launch_scene_kernel(spec_fn, grid, stream, la, [&] {
                 dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
-                    if (c->ss_k == 2u) hipLaunchKernelGGL((lens_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, la);
+                    // (a context of the one-call seam launches the variant that stores bytes and reports its rows: rtc_lens_seam.h)
+                    if (c->seam_kernels && c->ss_k == 2u) hipLaunchKernelGGL((lens_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, la);
+                    else if (c->seam_kernels) hipLaunchKernelGGL((lens_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, la);
+                    else if (c->ss_k == 2u) hipLaunchKernelGGL((lens_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, la);
                     else hipLaunchKernelGGL((lens_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, la);
                 });
             });
@@ -844,9 +855,10 @@ static rtc_status scene_kernel_for(rtc_ctx* c, rtc_ctx::SceneKernel& s, int32_t 
 
 // The frame's kernel: compiled when the scene is set (or, lazy, when it comes again: compile_deferred), not by the first frame.
 // RTC_AMD_SPECIALIZE=1 and no kernel: the context has no scene.
-// (the one-call seam's variant of the supersampling kernels is a code object of its own: "aot_ss<k>_<hash>.seam")
+// (the one-call seam's variant of the supersampling kernels is a code object of its own: "aot_ss<k>_<hash>.seam"; its variant of the
+// lens kernels is a kind of its own, JitKind::LENS_SEAM, whose id says so itself: "aot_lens<k>_<hash of its own>.seam")
 static std::string ctx_aot_id(const rtc_ctx* c) {
-    return aot_kernel_id(c->render.variant.kind, c->render.variant.k) + (c->seam_kernels && c->render.variant.kind == JitKind::SS ? ".seam" : "");  // (a lens kernel has no such variant)
+    return aot_kernel_id(c->render.variant.kind, c->render.variant.k) + (c->seam_kernels && c->render.variant.kind == JitKind::SS ? ".seam" : "");
 }
 static rtc_status compile_render_kernel(rtc_ctx* c, bool lazy) {
     rtc_ctx::SceneKernel& r = c->render;
@@ -932,8 +944,8 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     // that wants the scene's kernel compiles it
     c->trace.kernel.reset(trace_variant(plan));
     for (uint32_t i = 0; i < 2u; i++) c->adaptive.kernel[i].reset(refine_variant(plan, i ? 4u : 2u));
-    if (k != 1u) plan_supersampled(&plan, k, c->seam_kernels && !lens);
-    if (lens) plan_lens(&plan);
+    if (k != 1u) plan_supersampled(&plan, k, c->seam_kernels && !lens);  // (the lens kernel's seam variant is derived from the non-seam plan)
+    if (lens) plan_lens(&plan, c->seam_kernels);
     c->hdr = hdr;
     c->camera = *camera;
     c->ss_k = k;
@@ -1430,8 +1442,8 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     rtc_partition fine_part;
     if (ss_k != 1u) {
         // progress words and the u8 canvas (rtc_render_ss): the plain grid reports, a block-list launch is finished when its stream
-        // is.  Only the kernels of the one-call seam's contexts have those paths (rtc_supersample.h SEAM).
-        if ((progress || out_u8) && (!c->seam_kernels || c->lens_mode))
+        // is.  Only the kernels of the one-call seam's contexts have those paths (rtc_supersample.h SEAM, rtc_lens_seam.h).
+        if ((progress || out_u8) && !c->seam_kernels)
             return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render: a supersampled context renders f32 frames without progress words (bytes and progress words: rtc_render_ss)");
         const Partition o = resolve(part);
         if (o.band_rows > 0xffffffffu / ss_k) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: band_rows %u times the supersampling factor %u", o.band_rows, ss_k);
@@ -1502,7 +1514,7 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     // ---- warm up, time, launch, sum
     std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
     HIP_TRY(next_event_pair(c, &ev));
-    RTC_TRY(warm_up(c->render, spec_fn ? (const void*)spec_fn : aot_family(c).key(ss_k, ss_k != 1u && c->seam_kernels && !c->lens_mode, c->lens_mode), stream, [&] {
+    RTC_TRY(warm_up(c->render, spec_fn ? (const void*)spec_fn : aot_family(c).key(ss_k, ss_k != 1u && c->seam_kernels, c->lens_mode), stream, [&] {
         RenderArgs w = a;
         w.rows = 0u, w.tiles = nullptr, w.wave_ticks = nullptr, w.progress = nullptr, w.done = nullptr, w.fill_wg_rows = 0u, w.swizzle = 0u, w.blocks_y = 1u;
         return launch_render(c, spec_fn, dim3(1, 1), stream, w);
@@ -1730,6 +1742,7 @@ rtc_status rtc_diag_scene_plan(const rtc_scene* scene, const rtc_camera* camera,
         out += prefix + "family_name=" + v.family_name + "\n" + prefix + "spec_name=" + v.spec_name + "\n" + prefix + "spec_defs=" + joined(v.defs);
         const JitPlan jit = plan_jit(v.defs, v.kind, P.jit_flags, major, minor, sizes, k_core_src, beside_text(v.kind));
         if (*kind.header_below) out += prefix + "header_below=" + kind.header_below + "\n";
+        if (*kind.header_below2) out += prefix + "header_below2=" + kind.header_below2 + "\n";
         out += prefix + "entry=" + jit.entry + "\n" + prefix + "header=" + kind.header + "\n" + prefix + "options=" + joined(jit.opts) + prefix + "cache_file=" +
                jit.cache_file + "\n" + prefix + "aot_id=" + aot_kernel_id(v.kind, v.k) + "\n";
         for (int depth : {16, 32}) {
@@ -1751,6 +1764,13 @@ rtc_status rtc_diag_scene_plan(const rtc_scene* scene, const rtc_camera* camera,
         plan_lens(&lens_plan);
         add("lens" + std::to_string(k) + "_", render_variant(lens_plan), false);
         out += "lens" + std::to_string(k) + "_args=" + std::to_string(sizes.lens) + "\n";
+    }
+    for (uint32_t k : {2u, 4u}) {  // ... and the lens kernels of the one-call seam's contexts (rtc_render_lens; rtc_lens_seam.h)
+        ScenePlan lens_plan = p;
+        plan_supersampled(&lens_plan, k);
+        plan_lens(&lens_plan, true);
+        add("lens" + std::to_string(k) + "_seam_", render_variant(lens_plan), false);
+        out += "lens" + std::to_string(k) + "_seam_args=" + std::to_string(sizes.lens) + "\n";
     }
     if (out.size() >= cap) return fail(RTC_ERR_INVALID_ARG, "rtc_diag_scene_plan: the text needs %zu bytes", out.size() + 1);
     std::memcpy(text, out.c_str(), out.size() + 1);

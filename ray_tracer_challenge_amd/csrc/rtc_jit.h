@@ -1,4 +1,4 @@
-// rtc_jit.h -- the scene-kernel JIT's host side: which of the five scene kernels a variant is (JitKind: entry point, the header
+// rtc_jit.h -- the scene-kernel JIT's host side: which of the six scene kernels a variant is (JitKind: entry point, the header
 // beside the core, the argument block in the key), what a compile is made of (plan_jit: hiprtc's option list, the key text, the
 // source hash and the cache file's name) and the disk cache's entries (read_cache_entry / publish_cache_entry: the only host code
 // that reads files it did not write).  No device, no HIP header, nothing of rtc_kernel_core.h: rtc_device.hip's jit_get compiles,
@@ -26,35 +26,40 @@ namespace rtc {
 
 inline uint64_t fnv1a(const std::string& s, uint64_t h = 1469598103934665603ull) { return fnv1a(s.data(), s.size(), h); }
 
-// The five kernels a scene can have compiled for it: the frame's (rtc_kernel_core.h alone), the supersampled frame's, the ray
-// streams', the adaptive refinement's (rtc_supersample.h / rtc_trace.h / rtc_adaptive.h beside the core) and the lens frame's
+// The six kernels a scene can have compiled for it: the frame's (rtc_kernel_core.h alone), the supersampled frame's, the ray
+// streams', the adaptive refinement's (rtc_supersample.h / rtc_trace.h / rtc_adaptive.h beside the core), the lens frame's
 // (rtc_lens.h, which includes rtc_supersample.h: two headers beside the core, and `beside` -- the text a hash folds in -- is the
-// two texts one after the other, rtc_supersample.h first).
-enum class JitKind { RENDER, SS, TRACE, ADAPTIVE, LENS };
+// two texts one after the other, rtc_supersample.h first) and the lens frame's of the one-call seam (rtc_lens_seam.h, which
+// includes rtc_lens.h: three headers, their texts in the same order -- rtc_supersample.h, rtc_lens.h, rtc_lens_seam.h).
+enum class JitKind { RENDER, SS, TRACE, ADAPTIVE, LENS, LENS_SEAM };
 struct JitKindFacts {
     const char *entry, *header, *program;  // entry point; the header beside the core ("": none); the program text handed to hiprtc
     const char *aot_prefix, *args_line;    // of the ahead-of-time id (SS, ADAPTIVE, LENS: the factor follows); of the key's argument-size line
     const char* header_below = "";         // the header that `header` includes beside the core ("": none)
+    const char* header_below2 = "";        // ... and the one that one includes ("": none)
+    const char* aot_suffix = "";           // of the ahead-of-time id, after the hash
 };
 inline const JitKindFacts& jit_kind_facts(JitKind kind) {
-    static const JitKindFacts facts[5] = {
+    static const JitKindFacts facts[6] = {
         {"render_kernel_spec", "", "#include \"rtc_kernel_core.h\"\n", "aot_", nullptr},
         {"ss_render_kernel_spec", "rtc_supersample.h", "#include \"rtc_supersample.h\"\n", "aot_ss", nullptr},
         {"trace_kernel_spec", "rtc_trace.h", "#include \"rtc_trace.h\"\n", "aot_trace_", "trace args "},
         {"adaptive_refine_kernel_spec", "rtc_adaptive.h", "#include \"rtc_adaptive.h\"\n", "aot_adaptive", "adaptive args "},
-        {"lens_render_kernel_spec", "rtc_lens.h", "#include \"rtc_lens.h\"\n", "aot_lens", "lens args ", "rtc_supersample.h"}};
+        {"lens_render_kernel_spec", "rtc_lens.h", "#include \"rtc_lens.h\"\n", "aot_lens", "lens args ", "rtc_supersample.h"},
+        {"lens_render_kernel_spec", "rtc_lens_seam.h", "#include \"rtc_lens_seam.h\"\n", "aot_lens", "lens args ", "rtc_lens.h", "rtc_supersample.h", ".seam"}};
     return facts[(int)kind];
 }
 // (the plain kernels' names do not move: only the other four fold their headers' text into a hash)
 inline uint64_t source_hash_of(JitKind kind, uint64_t h, const std::string& beside) { return kind == JitKind::RENDER ? h : fnv1a(beside, h); }
 
 // Identifies the ahead-of-time kernels of this build by the source they were compiled from: "aot_<hash>", "aot_ss<k>_<hash>",
-// "aot_trace_<hash>", "aot_adaptive<k>_<hash>", "aot_lens<k>_<hash>".
+// "aot_trace_<hash>", "aot_adaptive<k>_<hash>", "aot_lens<k>_<hash>" -- and "aot_lens<k>_<hash>.seam", the one-call seam's lens
+// kernel, whose hash is its own: it folds rtc_lens_seam.h in as well.
 inline std::string aot_kernel_id(JitKind kind, uint32_t k, const std::string& core, const std::string& beside) {
     char hash[24];
     snprintf(hash, sizeof(hash), "%016llx", (unsigned long long)source_hash_of(kind, fnv1a(core), beside));
-    const bool factor = kind == JitKind::SS || kind == JitKind::ADAPTIVE || kind == JitKind::LENS;
-    return jit_kind_facts(kind).aot_prefix + (factor ? std::to_string(k) + "_" : std::string()) + hash;
+    const bool factor = kind == JitKind::SS || kind == JitKind::ADAPTIVE || kind == JitKind::LENS || kind == JitKind::LENS_SEAM;
+    return jit_kind_facts(kind).aot_prefix + (factor ? std::to_string(k) + "_" : std::string()) + hash + jit_kind_facts(kind).aot_suffix;
 }
 
 // The sizes of the argument blocks, which the key carries (a kernel compiled for another layout must not be found).
@@ -68,7 +73,7 @@ inline std::string jit_key_tail(JitKind kind, int hiprtc_major, int hiprtc_minor
     std::string t = "hiprtc " + std::to_string(hiprtc_major) + "." + std::to_string(hiprtc_minor) + " abi " + std::to_string(RTC_ABI_VERSION) + " args " +
                     std::to_string(sizes.render) + "\n";
     if (const char* line = jit_kind_facts(kind).args_line)
-        t += line + std::to_string(kind == JitKind::TRACE ? sizes.trace : kind == JitKind::LENS ? sizes.lens : sizes.adaptive) + "\n";
+        t += line + std::to_string(kind == JitKind::TRACE ? sizes.trace : kind == JitKind::LENS || kind == JitKind::LENS_SEAM ? sizes.lens : sizes.adaptive) + "\n";
     return t;
 }
 

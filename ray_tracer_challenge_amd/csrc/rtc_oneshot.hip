@@ -1,5 +1,6 @@
 // rtc_oneshot.hip -- Camera::render (camera.rs:76-91) in ONE call, host buffer out: rtc_render / rtc_render_ex, and rtc_render_ss,
-// the same call with k x k rays per pixel (the frame rtc_ctx_set_scene_ss defines; bands, chunks and staging count output rows).
+// the same call with k x k rays per pixel (the frame rtc_ctx_set_scene_ss defines; bands, chunks and staging count output rows),
+// and rtc_render_lens, that call with the k x k rays leaving from a thin lens (the frame rtc_ctx_set_scene_lens defines).
 //
 // What a caller of the reference's seam pays for is the whole call, not the kernel: context, scene upload, kernel
 // compile, output allocation, the kernel, and 201 MB (4096^2 f32) back over PCIe.  Everything that can be kept between
@@ -251,12 +252,16 @@ int32_t rtc_diag_seam_progress(uint32_t k, uint32_t out[2]) {
 
 // rtc_render_ex (ss = 1) and rtc_render_ss (ss = 2, 4: `camera` is the OUTPUT camera; W, H, rows, bands, chunks and staging below
 // are the output's -- the fine frame exists only inside the contexts, rtc_ctx_set_scene_ss).
+// rtc_render_lens (`lens_call`: ss = 2, 4 and a lens, both checked here): the same, the contexts being lens contexts
+// (rtc_ctx_set_scene_lens) -- a ray depends only on its global fine (x, y), so bands, chunks and staging need nothing new.
 static rtc_status render_seam(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, uint32_t ss, const rtc_opts* opts, void* out,
-                              rtc_stats* stats) {
-    if (!out || !camera) return fail(RTC_ERR_INVALID_ARG, "rtc_render: null argument");
+                              rtc_stats* stats, bool lens_call = false, const rtc_lens* lens = nullptr) {
+    if (!out || !camera) return fail(RTC_ERR_INVALID_ARG, "%s: null argument", lens_call ? "rtc_render_lens" : "rtc_render");
     if (camera->width == 0 || camera->height == 0) return fail(RTC_ERR_INVALID_ARG, "empty canvas");
     rtc_camera fine = *camera;
-    if (ss != 1u) {  // host only: answered on a machine without a device
+    if (lens_call) {  // host only, in check_lens_args' order: the lens (null: an error, not a frame without one), the factor, the fine frame
+        RTC_TRY(check_lens_args("rtc_render_lens", camera, ss, lens, &fine));
+    } else if (ss != 1u) {  // host only: answered on a machine without a device
         if (ss != 2u && ss != 4u) return fail(RTC_ERR_INVALID_ARG, "rtc_render_ss: supersampling factor %u: 1, 2 or 4 rays per pixel side", ss);
         RTC_TRY(rtc_camera_supersampled(camera, ss, &fine));
     }
@@ -331,8 +336,9 @@ static rtc_status render_seam(const rtc_scene* scene, const rtc_camera* camera, 
             std::memset(S.h_done, 0, PROGRESS_MAX_CHUNKS * sizeof(uint32_t));
             S.epoch = 1u;
         }
-        // (a no-op when this very scene is resident already, at this factor)
-        RTC_TRY(ss == 1u ? rtc_ctx_set_scene(S.ctx, scene, camera) : rtc_ctx_set_scene_ss(S.ctx, scene, camera, ss));
+        // (a no-op when this very scene is resident already, at this factor -- with a lens: whatever lens it was, a focus pull)
+        RTC_TRY(lens_call ? rtc_ctx_set_scene_lens(S.ctx, scene, camera, ss, lens)
+                          : ss == 1u ? rtc_ctx_set_scene(S.ctx, scene, camera) : rtc_ctx_set_scene_ss(S.ctx, scene, camera, ss));
         rtc_partition part = {band_rows, D, k};
         sh.rows = rtc_partition_rows(H, &part);
         for_each_band(H, resolve(&part), [&](uint32_t y0, uint32_t y1, uint32_t local0) {
@@ -540,6 +546,11 @@ rtc_status rtc_render_ex(const rtc_scene* scene, const rtc_camera* camera, int32
 rtc_status rtc_render_ss(const rtc_scene* scene, const rtc_camera* output_camera, int32_t depth, uint32_t k, const rtc_opts* opts,
                          void* out, rtc_stats* stats) {
     return render_seam(scene, output_camera, depth, k, opts, out, stats);
+}
+
+rtc_status rtc_render_lens(const rtc_scene* scene, const rtc_camera* output_camera, int32_t depth, uint32_t k, const rtc_lens* lens,
+                           const rtc_opts* opts, void* out, rtc_stats* stats) {
+    return render_seam(scene, output_camera, depth, k, opts, out, stats, true, lens);
 }
 
 rtc_status rtc_render(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, int32_t device, float* out_rgb,

@@ -1472,6 +1472,7 @@ struct ScenePlan {
     std::string spec_name;
     uint32_t ss_k = 1u;  // the frame's kernel is the supersampling one of this factor (plan_supersampled)
     bool lens = false;   // ... or the lens kernel of this factor (plan_lens)
+    bool lens_seam = false;  // ... in the one-call seam's variant (rtc_lens_seam.h)
     bool compile_now = false;
     // ... and the policy's two exceptions to "from 2^18 pixels", which rtc_ctx_trace applies to its number of rays: worlds with divided
     // meshes are compiled whatever the size, a mixed list of many objects (and a world without objects) never
@@ -1783,7 +1784,7 @@ inline std::string with_prefix(const std::string& name, const char* from, const 
 // The frame's kernel of a context of factor k (rtc_supersample.h; 1: the plan's own): ss_render_kernel<...;ss=k>.  The
 // supersampling body has neither the loop over blocks nor the rectangle's offsets.
 inline KernelVariant render_variant(const ScenePlan& p, uint32_t k = 1u) {
-    KernelVariant v = {p.spec_defs, p.family_name, p.spec_name, p.ss_k == 1u ? JitKind::RENDER : p.lens ? JitKind::LENS : JitKind::SS, p.ss_k};
+    KernelVariant v = {p.spec_defs, p.family_name, p.spec_name, p.ss_k == 1u ? JitKind::RENDER : p.lens_seam ? JitKind::LENS_SEAM : p.lens ? JitKind::LENS : JitKind::SS, p.ss_k};
     if (k == 1u) return v;
     v.kind = JitKind::SS, v.k = k;
     for (std::string* name : {&v.family_name, &v.spec_name})
@@ -1854,12 +1855,18 @@ inline void plan_supersampled(ScenePlan* p, uint32_t k, bool seam = false) {
 // lens kernel in the supersampling kernel's place -- lens_render_kernel<...;ss=k> / lens_render_kernel_spec[...;ss=k;lens],
 // -DRTC_SPEC_LENS=1 last.  What plan_supersampled declines stays declined.  (The scene-box early-out is switched off in the
 // launch's header, not here: has_scene_box is run-time data.)
-inline void plan_lens(ScenePlan* p) {
+// `seam`: a context of the one-call seam (rtc_render_lens) -- the variant of the lens kernel that stores bytes and reports its rows
+// (rtc_lens_seam.h), derived from the same non-seam supersampled plan: -DRTC_SPEC_LENS_SEAM=1 after -DRTC_SPEC_LENS=1, so another
+// kernel id and cache entry than the persistent context's, and names that say so -- "lens_seam_render_kernel<...;ss=k>" is the
+// ahead-of-time kernel launched, "lens_render_kernel_spec[...;ss=k;lens;seam]" the scene's own (its entry point keeps its name).
+inline void plan_lens(ScenePlan* p, bool seam = false) {
     if (!p->spec_defs.empty()) p->spec_defs.push_back("-DRTC_SPEC_LENS=1");
-    p->family_name = with_prefix(p->family_name, "ss_render_kernel<", "lens_render_kernel<");
+    p->family_name = with_prefix(p->family_name, "ss_render_kernel<", seam ? "lens_seam_render_kernel<" : "lens_render_kernel<");
     p->spec_name = with_prefix(p->spec_name, "ss_render_kernel_spec[", "lens_render_kernel_spec[");
-    if (!p->spec_name.empty()) p->spec_name.insert(p->spec_name.size() - 1, ";lens");
+    if (!p->spec_name.empty()) p->spec_name.insert(p->spec_name.size() - 1, seam ? ";lens;seam" : ";lens");
+    if (seam && !p->spec_defs.empty()) p->spec_defs.push_back("-DRTC_SPEC_LENS_SEAM=1");
     p->lens = true;
+    p->lens_seam = seam;
 }
 
 }  // namespace rtc

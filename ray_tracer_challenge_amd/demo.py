@@ -55,18 +55,12 @@ def main(argv=None):
     t0 = time.time()
     world, camera, depth = fn(size[0], size[1], **kw)
     t1 = time.time()
-    if a.aperture is not None:  # a lens frame: the persistent context's (the one-call seam has no lens)
-        from .api import Canvas, Lens
-        from .renderer import Renderer
-        r = Renderer(world, camera, supersample=a.supersample, lens=Lens(a.aperture, a.focus))
-        frame = r.render(depth)
-        st = r.stats()
-        canvas = Canvas(camera.width, camera.height)
-        canvas.data[...] = frame.cpu().numpy()
-        r.close()
+    if a.aperture is not None:  # a lens frame, through the one-call seam like every other frame here (rtc_render_lens)
+        from .api import Lens
+        canvas = camera.render(world, depth, supersample=a.supersample, lens=Lens(a.aperture, a.focus))
     else:
         canvas = camera.render(world, depth) if a.supersample == 1 else camera.render(world, depth, supersample=a.supersample)
-        st = camera.last_stats
+    st = camera.last_stats
     ppm = canvas.to_ppm()
     t2 = time.time()
     print("scene built in %.3f s; rendered %dx%d (%d rays, kernel %.3f ms) and formatted in %.3f s"
