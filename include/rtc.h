@@ -38,7 +38,9 @@ extern "C" {
                              rtc_reorder_stats, additions likewise; supersampling through the one-call seam: rtc_render_ss, one
                              entry point more -- rtc_opts and rtc_stats are what they were; the thin-lens camera: rtc_lens_rays,
                              rtc_ctx_set_scene_lens and the struct rtc_lens, additions likewise; the lens through the one-call
-                             seam: rtc_render_lens, one entry point more, no struct changed) */
+                             seam: rtc_render_lens, one entry point more, no struct changed;
+                             adaptive supersampling through the one-call seam: rtc_render_adaptive and the struct
+                             rtc_seam_adaptive_stats are additions, rtc_adaptive_stats keeps its layout) */
 /* reflection_recursion_depth (camera.rs:76: any i16; reference default 5, constants.rs:4; its author renders
  * reflect_refract at 20).  Accepted: 0 .. RTC_MAX_DEPTH.  The kernels keep one frame per suspended shade_hit
  * (world.rs:62-86); up to RTC_STACK_DEPTH_BASE levels every kernel has them, above that the scene's kernel is compiled
@@ -419,7 +421,43 @@ rtc_status rtc_render_ss(const rtc_scene* scene, const rtc_camera* output_camera
  * stats: as for rtc_render_ss -- pixels = (k W - 1)(k H - 1), rows = H, launches = one per entry of opts->devices that owns a row. */
 rtc_status rtc_render_lens(const rtc_scene* scene, const rtc_camera* output_camera, int32_t depth, uint32_t k, const rtc_lens* lens,
                            const rtc_opts* opts, void* out, rtc_stats* stats);
-/* Frees everything rtc_render / rtc_render_ex / rtc_render_ss / rtc_render_lens keep between calls (all devices). */
+/* Adaptive supersampling in one call (DESIGN.md 8e "one-call seam"): k x k rays only where neighbouring pixels of the base frame
+ * differ.  The frame is exactly rtc_ctx_render_adaptive's O, items (1)-(4) of its comment below -- base frame B, mask M over the
+ * WHOLE frame's four neighbours, supersampled frame S, O = S where M and B elsewhere -- for every value of `opts`: any devices
+ * list (entries may repeat and may own no row), any band_rows (0 -> 64, counted in output rows), f32 or bytes.  A band's first and
+ * last row have a neighbour in a band another entry renders: every entry traces those rows of B itself -- its halo rows, at most
+ * two per band, each pixel exactly B's pixel -- so any split assembles to the same frame and the same mask.
+ * `out`: H x W x 3 f32, or with opts->quantize H x W x 3 bytes, scale_color of O per channel (the threshold always compares the
+ * f32 B).  mask_u8: H x W bytes, 1 = refined, 0 = not; may be NULL.  Both in the memory opts->out_on_device names: host memory,
+ * pageable or page-locked, or device memory on devices[0].
+ * RTC_ERR_INVALID_ARG with a message, decided on the host before any device call, in this order: null `out` or camera, empty
+ * canvas (rtc_render_ss's checks), a threshold that is not finite or is negative, k other than 2 or 4, a fine frame
+ * rtc_camera_supersampled refuses.  A valid call on a machine without a device: RTC_ERR_NO_DEVICE.
+ * stats: rays, shaded_hits and pixels are the BASE frame's, summed over the entries -- rtc_render_ex's for the same scene whatever
+ * the split --, rows = H; launches, kernel_ms (the base pass's kernels) and gather_ms (the whole call) as for rtc_render_ss.
+ * `ad` (may be NULL): what the other passes did.  halo_pixels counts every pixel of every halo row, W per row; it is 0 when
+ * consecutive bands of an entry are adjacent (one entry).  mask_ms covers the halo pass and the mask kernel.
+ * Kernels (csrc/rtc_adaptive_seam.h): the base pass is rtc_render_ex's, without progress words -- a share's rows leave, chunk by
+ * chunk, when its stream is done; the halo pass and the refinement are "adaptive_seam_kernel<...;halo>" / "<...;ss=k>", ids
+ * "aot_adaptive_seam<1|k>_<hash>" -- the hash folds in rtc_adaptive.h and rtc_adaptive_seam.h -- or the scene's own,
+ * "adaptive_seam_kernel_spec[...]" / "spec_..." (-DRTC_SPEC_ADAPTIVE_SEAM=1|k).  Which runs: the seam's rule -- ahead-of-time at
+ * a scene's first sighting unless the disk cache has its kernel, compiled from the second on; RTC_AMD_SPECIALIZE=0|1 as for
+ * rtc_render_ex; depth above 8 takes the deep-stack variant.  rtc_ctx_render_adaptive's kernels are not touched.
+ * Calls of rtc_render_ex, rtc_render_ss, rtc_render_lens and rtc_render_adaptive of one scene may alternate, each gives its own
+ * frame; rtc_render_release frees what this call keeps.
+ * Not offered: adaptive lens frames, adaptive frames in dist.py, a partitioned rtc_ctx_render_adaptive. */
+typedef struct rtc_seam_adaptive_stats {
+    uint64_t refined_pixels; /* flagged pixels, summed over the entries: the mask's sum                                    */
+    uint64_t refine_rays;    /* rays of the refinement passes, counted as rtc_ctx_trace counts them                        */
+    uint64_t halo_pixels;    /* pixels of the halo rows the entries traced beside their shares                             */
+    uint64_t halo_rays;      /* ... and the rays that took                                                                 */
+    float mask_ms;           /* HIP-event time of an entry's halo pass and mask kernel, the maximum over the entries       */
+    float refine_ms;         /* ... and of its refinement kernel                                                           */
+} rtc_seam_adaptive_stats;
+rtc_status rtc_render_adaptive(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, uint32_t k, float threshold,
+                               const rtc_opts* opts, void* out, void* mask_u8, rtc_stats* stats,
+                               rtc_seam_adaptive_stats* ad);
+/* Frees everything rtc_render / rtc_render_ex / rtc_render_ss / rtc_render_lens / rtc_render_adaptive keep between calls (all devices). */
 void rtc_render_release(void);
 /* Page-locked host memory (hipHostMalloc): an `out` buffer allocated here is filled by DMA straight from the device. */
 void* rtc_host_alloc(size_t bytes);
@@ -471,7 +509,8 @@ rtc_status rtc_ctx_set_scene_ss(rtc_ctx* ctx, const rtc_scene* scene, const rtc_
  * RTC_ERR_INVALID_ARG with a message, decided on the host before any device call and before the context is looked at: a null lens
  * or camera, k not 2 or 4, aperture_radius negative or not finite, focal_distance <= 0 or not finite, a fine frame
  * rtc_camera_supersampled refuses.  The one-call seam renders through a lens with rtc_render_lens (above): the same frame, f32 or
- * bytes, host buffer out, several devices.  Not offered: adaptive lens frames, lens frames in dist.py. */
+ * bytes, host buffer out, several devices.  Not offered: adaptive lens frames, lens frames in dist.py.  (Nor, DESIGN.md
+ * 8e: adaptive frames in dist.py, a partitioned rtc_ctx_render_adaptive -- adaptive frames over several devices are rtc_render_adaptive's.) */
 rtc_status rtc_ctx_set_scene_lens(rtc_ctx* ctx, const rtc_scene* scene, const rtc_camera* output_camera, uint32_t k,
                                   const rtc_lens* lens);
 /* Rows this partition produces (sum of its bands' heights). */
@@ -668,7 +707,8 @@ rtc_status rtc_ctx_reorder_stats(rtc_ctx* ctx, rtc_reorder_stats* out);
  *      threshold so large that nothing is flagged O is rtc_ctx_render's frame bit for bit.  The picture does not depend on
  *      the order in which flagged pixels are processed.
  * d_out_rgb: DEVICE pointer to H x W x 3 f32.  d_mask_u8: DEVICE pointer to H x W bytes, 1 = refined, 0 = not; may be NULL.
- * The whole frame only: the mask needs neighbours across band edges, so there is no partition; the f32 canvas only.
+ * The whole frame only: the mask needs neighbours across band edges, so there is no partition; the f32 canvas only (bands over
+ * several devices, bytes and host output: rtc_render_adaptive above, whose entries trace the rows across their band edges themselves).
  * Asynchronous on `stream`; nothing comes back to the host between the three passes, the number of flagged pixels included.
  * The base pass IS rtc_ctx_render -- tiles, rectangle, block lists, feedback and its occasional read-back of measurements --
  * so rtc_ctx_stats and rtc_ctx_kernel_name / _id afterwards report it as after rtc_ctx_render, and the schedule moves as a

@@ -514,6 +514,23 @@ struct Camera {
         check(rtc_render_lens(&scene, &c, reflection_recursion_depth, k, &l, &opts, canvas.data.data(), &last_stats));
         return canvas;
     }
+    // ... and adaptively: k x k rays (k = 2 or 4) only for the pixels one of whose four neighbours in the plain frame differs from
+    // them by more than `threshold` in some channel (rtc_render_adaptive); what the passes did: last_adaptive_stats
+    rtc_seam_adaptive_stats last_adaptive_stats{};
+    Canvas render_adaptive(World world, int16_t reflection_recursion_depth, uint32_t k, float threshold, const std::vector<int32_t>& devices = {0},
+                           uint32_t band_rows = 0u, std::vector<uint8_t>* mask = nullptr) {
+        std::vector<rtc_object> objs;
+        std::vector<rtc_group> groups;
+        for (Shape& s : world.objects) flatten(s, objs, groups);
+        rtc_scene scene{(uint32_t)objs.size(), objs.data(), world.light ? &world.light->l : nullptr,
+                        (uint32_t)groups.size(), groups.data()};
+        rtc_opts opts{devices.data(), (uint32_t)devices.size(), band_rows, 0, 0};
+        Canvas canvas(c.width, c.height);
+        if (mask) mask->assign((size_t)c.width * c.height, 0);
+        check(rtc_render_adaptive(&scene, &c, reflection_recursion_depth, k, threshold, &opts, canvas.data.data(), mask ? mask->data() : nullptr,
+                                  &last_stats, &last_adaptive_stats));
+        return canvas;
+    }
 };
 
 constexpr float PI = 3.14159265358979323846264338327950288f;  // std::f32::consts::PI

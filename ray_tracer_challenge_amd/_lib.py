@@ -92,6 +92,11 @@ class rtc_stats(C.Structure):
 RTC_STATS_JIT_FALLBACK = 1
 
 
+class rtc_seam_adaptive_stats(C.Structure):
+    _fields_ = [("refined_pixels", C.c_uint64), ("refine_rays", C.c_uint64), ("halo_pixels", C.c_uint64), ("halo_rays", C.c_uint64),
+                ("mask_ms", C.c_float), ("refine_ms", C.c_float)]
+
+
 class rtc_adaptive_stats(C.Structure):
     _fields_ = [("refined_pixels", C.c_uint64), ("rays", C.c_uint64), ("shaded_hits", C.c_uint64), ("culled_shadow_rays", C.c_uint64),
                 ("mask_ms", C.c_float), ("refine_ms", C.c_float)]
@@ -170,6 +175,8 @@ SIGNATURES = {
                                 C.POINTER(rtc_stats)]),
     "rtc_render_lens": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.c_uint32, C.POINTER(rtc_lens), C.POINTER(rtc_opts),
                                   C.c_void_p, C.POINTER(rtc_stats)]),
+    "rtc_render_adaptive": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_int32, C.c_uint32, C.c_float, C.POINTER(rtc_opts),
+                                      C.c_void_p, C.c_void_p, C.POINTER(rtc_stats), C.POINTER(rtc_seam_adaptive_stats)]),
     "rtc_render_release": (None, []),
     "rtc_host_alloc": (C.c_void_p, [C.c_size_t]),
     "rtc_host_free": (None, [C.c_void_p]),
@@ -251,6 +258,11 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
          # adaptive supersampling: the refinement's slot -> (entry, sx, sy, lane) mapping and its grid (tests/test_adaptive_boundary.py)
          "rtc_diag_adaptive_plan": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+         # the one-call seam's adaptive frames: a part's compact-row map and halo rows (tests/test_seam_adaptive_boundary.py), and the
+         # kernels a seam context's last rtc_render_adaptive ran (tests/test_gpu_seam_adaptive.py)
+         "rtc_diag_adaptive_bands": (C.c_int32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                                                 C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
+         "rtc_diag_ctx_adaptive_seam_kernel": (C.c_char_p, [C.c_void_p, C.c_uint32]),
          # ray reordering: rtc_reorder.h's key function on host buffers, and the sort's plan {grid, segment, sub-tile} (tests/test_reorder_boundary.py)
          "rtc_diag_ray_keys": (None, [FP, FP, C.c_uint32, FP, C.POINTER(C.c_uint32)]),
          "rtc_diag_reorder_plan": (C.c_uint32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -972,6 +972,7 @@ class Camera:
         self.field_of_view = f32(field_of_view)
         self.transform = np.asarray(transform, dtype=f32).reshape(4, 4).copy()
         self.last_stats = None
+        self.last_adaptive_stats = None
 
     @property
     def pixel_size(self):
@@ -1000,6 +1001,7 @@ class Camera:
         cam.field_of_view = self.field_of_view
         cam.transform = self.transform.copy()
         cam.last_stats = None
+        cam.last_adaptive_stats = None
         return cam
 
     def lens_rays(self, k, lens, y0=0, n_rows=None):
@@ -1022,7 +1024,8 @@ class Camera:
         L.lib().rtc_ray_for_pixel(C.byref(self._cam), int(x), int(y), _p(o), _p(d))
         return o, d
 
-    def render(self, world, reflection_recursion_depth, device=0, devices=None, quantize=False, band_rows=0, out=None, supersample=1, lens=None):
+    def render(self, world, reflection_recursion_depth, device=0, devices=None, quantize=False, band_rows=0, out=None, supersample=1, lens=None,
+               adaptive=None, mask=None):
         """Camera::render (camera.rs:76-91) on the MI355X -> Canvas.
 
         devices: the GPUs to split the image over (rtc_render_ex; default: [device]).  quantize: return the (h, w, 3) u8
@@ -1031,7 +1034,11 @@ class Camera:
         Renderer(world, self, supersample=k), the box filter of self.supersampled(k)'s frame; band_rows counts this camera's
         rows either way, and last_stats' rays / shaded_hits / pixels are then the fine frame's.
         lens: a Lens -- depth of field (rtc_render_lens): the frame of Renderer(world, self, supersample=k, lens=lens); it takes
-        supersample = 2 or 4."""
+        supersample = 2 or 4.
+        adaptive: a threshold -- adaptive supersampling (rtc_render_adaptive): the frame of Renderer(world, self).render_adaptive(k,
+        threshold), k x k rays only where neighbouring pixels of the plain frame differ by more than it; it takes supersample = 2
+        or 4 and no lens.  mask: an (h, w) u8 array to receive the refined pixels (1 = refined).  last_stats is then the base
+        frame's and last_adaptive_stats the other passes' (rtc_seam_adaptive_stats)."""
         k = int(supersample)
         if k not in (1, 2, 4):
             raise ValueError("supersample must be 1, 2 or 4, not %r" % (supersample,))
@@ -1039,6 +1046,15 @@ class Camera:
             raise TypeError("lens must be a Lens, not %r" % (lens,))
         if lens is not None and k not in (2, 4):
             raise ValueError("a lens frame takes supersample = 2 or 4, not %r" % (supersample,))
+        if adaptive is not None and lens is not None:
+            raise ValueError("adaptive lens frames are not offered: adaptive takes no lens")
+        if adaptive is not None and k not in (2, 4):
+            raise ValueError("an adaptive frame takes supersample = 2 or 4, not %r" % (supersample,))
+        if mask is not None and adaptive is None:
+            raise ValueError("mask goes with adaptive")
+        if mask is not None and (not isinstance(mask, np.ndarray) or mask.dtype != np.uint8 or mask.shape != (self.height, self.width)
+                                 or not mask.flags["C_CONTIGUOUS"]):
+            raise ValueError("mask must be a C-contiguous (%d, %d) array of uint8" % (self.height, self.width))
         devs = [int(device)] if devices is None else [int(d) for d in devices]
         dtype = np.uint8 if quantize else f32
         img = np.zeros((self.height, self.width, 3), dtype=dtype) if out is None else out
@@ -1050,7 +1066,14 @@ class Camera:
         _seam_follows_environment()
         arr = (C.c_int32 * len(devs))(*devs)
         opts = L.rtc_opts(arr, len(devs), int(band_rows), 1 if quantize else 0, 0)
-        if lens is not None:
+        self.last_adaptive_stats = None
+        if adaptive is not None:
+            ad = L.rtc_seam_adaptive_stats()
+            L.check(L.lib().rtc_render_adaptive(C.byref(cs.scene), C.byref(self._cam), int(reflection_recursion_depth), k, f32(adaptive), C.byref(opts),
+                                                img.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p) if mask is not None else None,
+                                                C.byref(stats), C.byref(ad)))
+            self.last_adaptive_stats = {name: (float if name.endswith("_ms") else int)(getattr(ad, name)) for name, _ in L.rtc_seam_adaptive_stats._fields_}
+        elif lens is not None:
             L.check(L.lib().rtc_render_lens(C.byref(cs.scene), C.byref(self._cam), int(reflection_recursion_depth), k, C.byref(lens._c),
                                             C.byref(opts), img.ctypes.data_as(C.c_void_p), C.byref(stats)))
         elif k == 1:

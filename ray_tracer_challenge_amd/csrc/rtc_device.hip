@@ -38,6 +38,7 @@
 #include "rtc_lens_seam.h"
 #include "rtc_trace.h"
 #include "rtc_adaptive.h"
+#include "rtc_adaptive_seam.h"
 #include "rtc_reorder.h"
 #include "rtc_wavefront.h"
 #include "rtc_scene_prep.h"
@@ -259,6 +260,26 @@ struct rtc_ctx {
         bool ran = false;                 // the events have been recorded
         std::map<const void*, int> wgs_per_cu;  // occupancy of a refinement kernel, asked once
     } adaptive;
+    // Adaptive supersampling of the one-call seam (rtc_render_adaptive; rtc_adaptive_seam.h): one part's halo pass, banded mask and
+    // refinement behind a base pass that is ctx_render_slot's.  Everything of its own, as above; kept between calls.
+    struct AdaptiveSeam {
+        SceneKernel kernel[3];            // seam_refine_variant's of k = 1 (the halo pass), 2, 4
+        bool failed = false;              // hiprtc did not deliver one of them: the ahead-of-time kernels from then on, for all (note says why)
+        std::string note;
+        std::string name, id;             // of the last call's refinement kernel ("" before the first of the current scene)
+        std::string halo_name, halo_id;   // ... and of its halo pass ("": the last call had no halo row)
+        uint32_t* d_list = nullptr;       // flagged pixels of the share, share-local indices
+        size_t list_cap = 0;
+        float* d_halo = nullptr;          // [halo rows][W][3]
+        size_t halo_cap = 0;
+        uint8_t* d_mask = nullptr;        // [rows][W]
+        size_t mask_cap = 0;
+        AdaptiveQueue* d_queue = nullptr; // [2]: the refinement's (with the list's length) and the halo pass's
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // before the halo pass, after the mask kernel, after the refinement
+        bool ran = false;
+        uint64_t halo_pixels = 0;         // of the last call: halo rows x W
+        std::map<const void*, int> wgs_per_cu;
+    } adaptive_seam;
     // Ray reordering (rtc_ctx_ray_order, rtc_ctx_trace_reordered; rtc_reorder.h).  The sort's and the gather's buffers, events of
     // its own; the trace in the middle is rtc_ctx_trace's and is reported as one.
     struct Reorder {
@@ -387,10 +408,11 @@ std::string jit_cache_dir(const Policy& P) {  // RTC_AMD_JIT_CACHE=<dir>, or 0 /
 std::string beside_text(JitKind kind) {
     if (kind == JitKind::LENS) return std::string(k_ss_src) + k_lens_src;
     if (kind == JitKind::LENS_SEAM) return std::string(k_ss_src) + k_lens_src + k_lens_seam_src;
+    if (kind == JitKind::ADAPTIVE_SEAM) return std::string(k_adaptive_src) + k_adaptive_seam_src;
     return kind == JitKind::SS ? k_ss_src : kind == JitKind::TRACE ? k_trace_src : kind == JitKind::ADAPTIVE ? k_adaptive_src : "";
 }
 // The sizes of the kernels' argument blocks, which a key carries
-constexpr JitArgSizes k_jit_arg_sizes = {sizeof(RenderArgs), sizeof(TraceArgs), sizeof(AdaptiveRefineArgs), sizeof(LensRenderArgs)};
+constexpr JitArgSizes k_jit_arg_sizes = {sizeof(RenderArgs), sizeof(TraceArgs), sizeof(AdaptiveRefineArgs), sizeof(LensRenderArgs), sizeof(AdaptiveSeamArgs)};
 // identifies the ahead-of-time kernels of this build: the source they were compiled from
 std::string aot_kernel_id(JitKind kind, uint32_t k = 1u) { return rtc::aot_kernel_id(kind, k, k_core_src, beside_text(kind)); }
 
@@ -415,10 +437,11 @@ rtc_status jit_get(const Policy& P, int device, const KernelVariant& v, hipFunct
     }
     const JitKindFacts& kind = jit_kind_facts(v.kind);
     // (`beside`: the header the kind's kernel includes; `below`: the header that one includes -- the lens kernel's rtc_supersample.h;
-    // the seam's lens kernel: rtc_lens_seam.h, rtc_lens.h below it and rtc_supersample.h below that, `below2`)
-    const bool lens_seam = v.kind == JitKind::LENS_SEAM;
-    std::string core = k_core_src, beside = lens_seam ? k_lens_seam_src : v.kind == JitKind::LENS ? k_lens_src : beside_text(v.kind);
-    std::string below = lens_seam ? k_lens_src : *kind.header_below ? k_ss_src : "", below2 = *kind.header_below2 ? k_ss_src : "";
+    // the seam's lens kernel: rtc_lens_seam.h, rtc_lens.h below it and rtc_supersample.h below that, `below2`;
+    // the seam's adaptive kernels: rtc_adaptive_seam.h, rtc_adaptive.h below it)
+    const bool lens_seam = v.kind == JitKind::LENS_SEAM, adaptive_seam = v.kind == JitKind::ADAPTIVE_SEAM;
+    std::string core = k_core_src, beside = lens_seam ? k_lens_seam_src : adaptive_seam ? k_adaptive_seam_src : v.kind == JitKind::LENS ? k_lens_src : beside_text(v.kind);
+    std::string below = lens_seam ? k_lens_src : adaptive_seam ? k_adaptive_src : *kind.header_below ? k_ss_src : "", below2 = *kind.header_below2 ? k_ss_src : "";
     if (!P.jit_source.empty()) {  // development builds only (Policy)
         if (!read_file(P.jit_source, &core)) return fail(RTC_ERR_DEVICE, "scene specialisation: cannot read the kernel source %s", P.jit_source.c_str());
         // (... and the headers beside it from the same directory, when they are there: an experiment in any of them needs no rebuild)
@@ -616,6 +639,12 @@ void rtc_ctx_destroy(rtc_ctx* c) {
     if (c->adaptive.d_list) (void)hipFree(c->adaptive.d_list);
     if (c->adaptive.d_queue) (void)hipFree(c->adaptive.d_queue);
     for (hipEvent_t e : c->adaptive.ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->adaptive_seam.d_list) (void)hipFree(c->adaptive_seam.d_list);
+    if (c->adaptive_seam.d_halo) (void)hipFree(c->adaptive_seam.d_halo);
+    if (c->adaptive_seam.d_mask) (void)hipFree(c->adaptive_seam.d_mask);
+    if (c->adaptive_seam.d_queue) (void)hipFree(c->adaptive_seam.d_queue);
+    for (hipEvent_t e : c->adaptive_seam.ev)
         if (e) (void)hipEventDestroy(e);
     if (c->reorder.d_scratch) (void)hipFree(c->reorder.d_scratch);
     if (c->reorder.d_table) (void)hipFree(c->reorder.d_table);
@@ -944,6 +973,7 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     // that wants the scene's kernel compiles it
     c->trace.kernel.reset(trace_variant(plan));
     for (uint32_t i = 0; i < 2u; i++) c->adaptive.kernel[i].reset(refine_variant(plan, i ? 4u : 2u));
+    for (uint32_t i = 0; i < 3u; i++) c->adaptive_seam.kernel[i].reset(seam_refine_variant(plan, 1u << i));
     if (k != 1u) plan_supersampled(&plan, k, c->seam_kernels && !lens);  // (the lens kernel's seam variant is derived from the non-seam plan)
     if (lens) plan_lens(&plan, c->seam_kernels);
     c->hdr = hdr;
@@ -977,6 +1007,8 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     c->trace.name.clear(), c->trace.id.clear();
     c->adaptive.failed = false;
     c->adaptive.note.clear(), c->adaptive.name.clear(), c->adaptive.id.clear();
+    c->adaptive_seam.failed = false;
+    c->adaptive_seam.note.clear(), c->adaptive_seam.name.clear(), c->adaptive_seam.id.clear(), c->adaptive_seam.halo_name.clear(), c->adaptive_seam.halo_id.clear();
     c->render.reset(render_variant(plan));
     c->kernel_name = plan.family_name;
     c->kernel_id = ctx_aot_id(c);
@@ -1765,6 +1797,12 @@ rtc_status rtc_diag_scene_plan(const rtc_scene* scene, const rtc_camera* camera,
         add("lens" + std::to_string(k) + "_", render_variant(lens_plan), false);
         out += "lens" + std::to_string(k) + "_args=" + std::to_string(sizes.lens) + "\n";
     }
+    // ... and the adaptive kernels of the one-call seam's contexts (rtc_render_adaptive; rtc_adaptive_seam.h): the halo pass, then the
+    // refinements.  (In front of the seam's lens kernels, which tests/test_seam_lens_boundary.py pins as the text's last lines.)
+    for (uint32_t k : {1u, 2u, 4u}) {
+        add("adaptive_seam" + std::to_string(k) + "_", seam_refine_variant(p, k));
+        out += "adaptive_seam" + std::to_string(k) + "_args=" + std::to_string(sizes.adaptive_seam) + "\n";
+    }
     for (uint32_t k : {2u, 4u}) {  // ... and the lens kernels of the one-call seam's contexts (rtc_render_lens; rtc_lens_seam.h)
         ScenePlan lens_plan = p;
         plan_supersampled(&lens_plan, k);
@@ -2311,6 +2349,186 @@ uint32_t rtc_diag_adaptive_plan(uint32_t k, uint32_t width, uint32_t height, uin
 }
 
 }  // extern "C"
+
+// ---- adaptive supersampling of the one-call seam (rtc_adaptive_seam.h; rtc_render_adaptive) ---------------------
+// The host-only plan of one part: its share, and how many halo rows it has -- counted band by band, not from seam_halo_row's closed
+// form, which the kernels use and rtc_diag_adaptive_bands lists beside it.  One part: consecutive bands are adjacent, no halo.
+static AdaptiveShare adaptive_seam_share(uint32_t width, uint32_t height, const Partition& q, uint32_t* n_halo) {
+    AdaptiveShare s = {width, height, 0u, q.band_rows, q.n_parts, q.part};
+    uint32_t halo = 0u;
+    for_each_band(height, q, [&](uint32_t y0, uint32_t y1, uint32_t) {
+        s.rows += y1 - y0;
+        if (q.n_parts > 1u) halo += (y0 > 0u ? 1u : 0u) + (y1 < height ? 1u : 0u);
+    });
+    *n_halo = halo;
+    return s;
+}
+// f(the ahead-of-time seam kernel of the context's family: k = 2, 4 the refinement, 1 the halo pass)
+template <class F>
+static void dispatch_adaptive_seam(rtc_ctx* c, uint32_t k, F&& f) {
+    dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
+        if (k == 4u) f(adaptive_seam_kernel<decltype(nobj)::value, decltype(simple)::value, 4>);
+        else if (k == 2u) f(adaptive_seam_kernel<decltype(nobj)::value, decltype(simple)::value, 2>);
+        else f(adaptive_seam_kernel<decltype(nobj)::value, decltype(simple)::value, 1>);
+    });
+}
+static hipError_t launch_adaptive_seam(rtc_ctx* c, hipFunction_t fn, uint32_t k, uint32_t n_workgroups, hipStream_t stream, AdaptiveSeamArgs& a) {
+    return launch_scene_kernel(fn, dim3(n_workgroups), stream, a, [&] {
+        dispatch_adaptive_seam(c, k, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_workgroups), dim3(256), 0, stream, a); });
+    });
+}
+static int adaptive_seam_wgs_per_cu(rtc_ctx* c, hipFunction_t fn, uint32_t k, const void* key) {
+    auto it = c->adaptive_seam.wgs_per_cu.find(key);
+    if (it != c->adaptive_seam.wgs_per_cu.end()) return it->second;
+    int n = 0;
+    hipError_t e = hipSuccess;
+    if (fn) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, 0);
+    else dispatch_adaptive_seam(c, k, [&](auto kernel) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0); });
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || n < 1) n = 1;
+    if (n > 8) n = 8;
+    c->adaptive_seam.wgs_per_cu[key] = n;
+    return n;
+}
+
+static std::string adaptive_seam_aot_id(uint32_t k) { return aot_kernel_id(JitKind::ADAPTIVE_SEAM, k); }  // (rtc::ctx_adaptive_seam sees rtc::aot_kernel_id first)
+
+// Behind a base pass that ctx_render_slot has queued on `stream` for the same partition into d_share_f32: halo pass, banded mask,
+// refinement, nothing coming back to the host in between.  d_out_u8 (byte mode): the share's bytes, every one of them written by the
+// mask kernel or the refinement; null: the refinement writes f32 over d_share_f32.  *d_mask: the share's mask, compact like the share
+// (null when not wanted or the part owns no row).  The checks of k, the threshold and the fine frame are the caller's (rtc_oneshot.hip).
+rtc_status rtc::ctx_adaptive_seam(rtc_ctx* c, int32_t depth, uint32_t k, float threshold, const rtc_partition* part, void* d_share_f32, void* d_out_u8,
+                                  bool want_mask, void* stream_, void** d_mask) {
+    if (d_mask) *d_mask = nullptr;
+    if (!c || !c->has_scene || c->ss_k != 1u || c->lens_mode) return fail(RTC_ERR_INVALID_ARG, "rtc_render_adaptive: the context holds no plain scene");
+    if (k != 2u && k != 4u) return fail(RTC_ERR_INVALID_ARG, "rtc_render_adaptive: supersampling factor %u: 2 or 4 rays per pixel side", k);
+    rtc_camera fine;
+    RTC_TRY(rtc_camera_supersampled(&c->camera, k, &fine));
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    rtc_ctx::AdaptiveSeam& ad = c->adaptive_seam;
+    const Policy& P = c->policy;
+    const Partition q = resolve(part);
+    const uint32_t width = c->hdr.width, height = c->hdr.height;
+    uint32_t n_halo = 0u;
+    const AdaptiveShare share = adaptive_seam_share(width, height, q, &n_halo);
+    ad.ran = false;
+    ad.halo_pixels = 0u;
+    if (share.rows == 0u) return RTC_OK;  // (a part that owns no row: nothing to launch, its statistics read zero)
+    if (!d_share_f32) return fail(RTC_ERR_INVALID_ARG, "rtc_render_adaptive: null share buffer");
+    const size_t n_share = (size_t)width * share.rows, n_halo_px = (size_t)width * n_halo;
+    // ---- the kernels: the policy's question is asked with the whole frame's pixels, as the base pass asks it; the seam's rule for a
+    // scene's first sighting (jit_get, lazy) as for its frame kernel
+    int32_t refine_depth = depth;
+    if (refine_depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) refine_depth = RTC_STACK_DEPTH_BASE;
+    rtc_ctx::SceneKernel& slot = ad.kernel[k == 4u ? 2 : 1];
+    rtc_ctx::SceneKernel& halo_slot = ad.kernel[0];
+    const bool want = !slot.variant.defs.empty() && wants_scene_kernel(P, (uint64_t)width * height, c->trace.compile_any_size, c->trace.compile_never);
+    const bool lazy = c->lazy_jit && P.specialise == 2;
+    hipFunction_t fn = nullptr, halo_fn = nullptr;
+    std::string id, halo_id;
+    RTC_TRY(scene_kernel_for(c, slot, refine_depth, want, lazy, ad.failed, ad.note, "refining with", false, &fn, &id));
+    if (n_halo) RTC_TRY(scene_kernel_for(c, halo_slot, refine_depth, want, lazy, ad.failed, ad.note, "refining with", false, &halo_fn, &halo_id));
+    // ---- workspaces (grow-only; the caller's stream is the only one that has used them, and it is ordered)
+    HIP_TRY(grow(&ad.d_list, &ad.list_cap, n_share));
+    if (n_halo) HIP_TRY(grow(&ad.d_halo, &ad.halo_cap, n_halo_px * 3));
+    if (want_mask) HIP_TRY(grow(&ad.d_mask, &ad.mask_cap, n_share));
+    if (!ad.d_queue) HIP_TRY(hipMalloc((void**)&ad.d_queue, 2 * sizeof(AdaptiveQueue)));
+    for (hipEvent_t& e : ad.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const void* const kernel_key = fn ? (const void*)fn : aot_family(c).key(k);
+    const void* const halo_key = halo_fn ? (const void*)halo_fn : aot_family(c).key(1u);
+    const uint32_t n_cus = (uint32_t)compute_units(c);
+    AdaptiveSeamArgs a;
+    a.hdr = launch_hdr(c, refine_depth, 1u);
+    a.hdr.has_scene_box = 0u;  // (rtc_adaptive.h)
+    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.share = share;
+    a.depth = refine_depth;
+    a.warm = 0u;
+    AdaptiveSeamArgs h = a;  // the halo pass: the plain camera's header
+    h.list = nullptr, h.queue = ad.d_queue + 1, h.out = ad.d_halo, h.out_u8 = nullptr, h.n_halo = n_halo;
+    a.hdr.width = fine.width, a.hdr.height = fine.height, a.hdr.pixel_size = fine.pixel_size;
+    a.list = ad.d_list, a.queue = ad.d_queue, a.out = (float*)d_share_f32, a.out_u8 = (uint8_t*)d_out_u8, a.n_halo = 0u;
+    // ---- warm up (in front of the events), halo, mask, refinement
+    RTC_TRY(warm_up(slot, kernel_key, stream, [&] {
+        AdaptiveSeamArgs w = a;
+        w.warm = 1u;
+        return launch_adaptive_seam(c, fn, k, 1u, stream, w);
+    }));
+    if (n_halo)
+        RTC_TRY(warm_up(halo_slot, halo_key, stream, [&] {
+            AdaptiveSeamArgs w = h;
+            w.warm = 1u;
+            return launch_adaptive_seam(c, halo_fn, 1u, 1u, stream, w);
+        }));
+    HIP_TRY(hipMemsetAsync(ad.d_queue, 0, 2 * sizeof(AdaptiveQueue), stream));
+    HIP_TRY(hipEventRecord(ad.ev[0], stream));
+    if (n_halo)
+        HIP_TRY(launch_adaptive_seam(c, halo_fn, 1u, adaptive_grid(n_cus, (uint32_t)adaptive_seam_wgs_per_cu(c, halo_fn, 1u, halo_key), width, n_halo, 1u), stream, h));
+    AdaptiveSeamMaskArgs m;
+    m.frame = (const float*)d_share_f32, m.halo = ad.d_halo, m.mask = want_mask ? ad.d_mask : nullptr, m.out_u8 = (uint8_t*)d_out_u8;
+    m.list = ad.d_list, m.queue = ad.d_queue, m.share = share, m.threshold = threshold;
+    m.blocks_x = (width + 15u) / 16u, m.n_blocks = m.blocks_x * ((share.rows + 15u) / 16u);
+    hipLaunchKernelGGL(adaptive_seam_mask_kernel, dim3(adaptive_mask_grid(n_cus, m.n_blocks)), dim3(256), 0, stream, m);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ad.ev[1], stream));
+    HIP_TRY(launch_adaptive_seam(c, fn, k, adaptive_grid(n_cus, (uint32_t)adaptive_seam_wgs_per_cu(c, fn, k, kernel_key), width, share.rows, k), stream, a));
+    HIP_TRY(hipEventRecord(ad.ev[2], stream));
+    ad.name = fn ? slot.variant.spec_name : slot.variant.family_name;
+    ad.id = fn ? id : adaptive_seam_aot_id(k);
+    ad.halo_name = !n_halo ? std::string() : halo_fn ? halo_slot.variant.spec_name : halo_slot.variant.family_name;
+    ad.halo_id = !n_halo ? std::string() : halo_fn ? halo_id : adaptive_seam_aot_id(1u);
+    ad.halo_pixels = n_halo_px;
+    ad.ran = true;
+    if (d_mask && want_mask) *d_mask = ad.d_mask;
+    return RTC_OK;
+}
+
+// After the caller has synchronised with the stream: what the last ctx_adaptive_seam of this context did (all zero: its part owned no row).
+rtc_status rtc::ctx_adaptive_seam_collect(rtc_ctx* c, rtc_seam_adaptive_stats* out) {
+    std::memset(out, 0, sizeof(*out));
+    const rtc_ctx::AdaptiveSeam& ad = c->adaptive_seam;
+    if (!ad.ran) return RTC_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    AdaptiveQueue q[2];
+    HIP_TRY(hipMemcpy(q, ad.d_queue, sizeof(q), hipMemcpyDeviceToHost));
+    out->refined_pixels = q[0].n_flagged;
+    out->refine_rays = q[0].total[0];
+    out->halo_pixels = ad.halo_pixels;
+    out->halo_rays = q[1].total[0];
+    HIP_TRY(hipEventElapsedTime(&out->mask_ms, ad.ev[0], ad.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&out->refine_ms, ad.ev[1], ad.ev[2]));
+    return RTC_OK;
+}
+
+extern "C" {
+// Diagnostics (not in rtc.h): the seam's adaptive kernels of a context's last rtc_render_adaptive -- what = 0, 1: the refinement's
+// name and id; 2, 3: the halo pass's ("": no halo row) -- tests/test_gpu_seam_adaptive.py, through rtc_diag_seam_ctx.
+const char* rtc_diag_ctx_adaptive_seam_kernel(rtc_ctx* c, uint32_t what) {
+    if (!c) return "";
+    const rtc_ctx::AdaptiveSeam& ad = c->adaptive_seam;
+    return what == 0u ? ad.name.c_str() : what == 1u ? ad.id.c_str() : what == 2u ? ad.halo_name.c_str() : what == 3u ? ad.halo_id.c_str() : "";
+}
+// ... and the host-only plan of a part (tests/test_seam_adaptive_boundary.py, no device needed): the compact-row -> frame-row map
+// (seam_global_row, what the kernels call) into rows_out and the frame rows of its halo rows (seam_halo_row) into halo_out, as
+// far as the caps go; counts = {rows, halo rows}, the halo rows counted band by band as the launch counts them.  band_rows 0 -> 64,
+// n_parts 0 -> 1.  -> 1; 0: no such part, or an empty frame.
+int32_t rtc_diag_adaptive_bands(uint32_t height, uint32_t band_rows, uint32_t n_parts, uint32_t part, uint32_t* rows_out, uint32_t rows_cap,
+                                uint32_t* halo_out, uint32_t halo_cap, uint32_t counts[2]) {
+    if (counts) counts[0] = counts[1] = 0u;
+    const rtc_partition p = {band_rows, n_parts, part};
+    const Partition q = resolve(&p);
+    if (height == 0u || q.part >= q.n_parts || !counts) return 0;
+    uint32_t n_halo = 0u;
+    const AdaptiveShare s = adaptive_seam_share(1u, height, q, &n_halo);
+    counts[0] = s.rows, counts[1] = n_halo;
+    for (uint32_t i = 0; rows_out && i < s.rows && i < rows_cap; i++) rows_out[i] = seam_global_row(s, i);
+    for (uint32_t i = 0; halo_out && i < n_halo && i < halo_cap; i++) halo_out[i] = seam_halo_row(s, i);
+    return 1;
+}
+}  // extern "C"
+
 // rtc_ctx_stats' read-out, of the renders or of the traces: waits for the device, the last launch's counters (`total`), the mean
 // kernel time of the launches since the last read-out (`events`, which start over)
 static rtc_status read_launch_stats(rtc_ctx* c, const unsigned long long* d_total, const EventPairs& events, size_t& events_used, const std::string& note,

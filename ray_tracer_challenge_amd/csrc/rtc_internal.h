@@ -107,6 +107,13 @@ rtc_status ctx_collect(rtc_ctx* c, uint32_t n_slots, rtc_stats* out);
 // A context of the one-call seam (rtc_render_ex): a scene whose kernel is neither in memory nor in the disk cache is rendered by the
 // ahead-of-time kernels the first time this process sees it and compiled when it is rendered again (rtc_device.hip jit_get).
 void ctx_mark_one_shot(rtc_ctx* c);
+// rtc_render_adaptive's passes behind the base pass of one part (rtc_device.hip; csrc/rtc_adaptive_seam.h): halo rows, banded mask,
+// refinement, queued on `stream` behind a ctx_render_slot of the same partition into d_share_f32 (compact f32 rows).  d_out_u8: the
+// share as bytes (byte mode), or null: f32 over d_share_f32.  *d_mask: the share's compact mask (want_mask), the context's buffer.
+rtc_status ctx_adaptive_seam(rtc_ctx* c, int32_t depth, uint32_t k, float threshold, const rtc_partition* part, void* d_share_f32, void* d_out_u8,
+                             bool want_mask, void* stream, void** d_mask);
+// ... and its statistics, once the caller has synchronised with `stream` (all zero: the part owned no row)
+rtc_status ctx_adaptive_seam_collect(rtc_ctx* c, rtc_seam_adaptive_stats* out);
 
 }  // namespace rtc
 

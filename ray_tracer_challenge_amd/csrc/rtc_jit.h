@@ -1,4 +1,4 @@
-// rtc_jit.h -- the scene-kernel JIT's host side: which of the six scene kernels a variant is (JitKind: entry point, the header
+// rtc_jit.h -- the scene-kernel JIT's host side: which of the seven scene kernels a variant is (JitKind: entry point, the header
 // beside the core, the argument block in the key), what a compile is made of (plan_jit: hiprtc's option list, the key text, the
 // source hash and the cache file's name) and the disk cache's entries (read_cache_entry / publish_cache_entry: the only host code
 // that reads files it did not write).  No device, no HIP header, nothing of rtc_kernel_core.h: rtc_device.hip's jit_get compiles,
@@ -31,7 +31,9 @@ inline uint64_t fnv1a(const std::string& s, uint64_t h = 1469598103934665603ull)
 // (rtc_lens.h, which includes rtc_supersample.h: two headers beside the core, and `beside` -- the text a hash folds in -- is the
 // two texts one after the other, rtc_supersample.h first) and the lens frame's of the one-call seam (rtc_lens_seam.h, which
 // includes rtc_lens.h: three headers, their texts in the same order -- rtc_supersample.h, rtc_lens.h, rtc_lens_seam.h).
-enum class JitKind { RENDER, SS, TRACE, ADAPTIVE, LENS, LENS_SEAM };
+// The seventh: the one-call seam's adaptive kernels (rtc_adaptive_seam.h, which includes rtc_adaptive.h: two headers, rtc_adaptive.h
+// first) -- factor 2 or 4: the refinement of a part's share; factor 1: its halo pass.
+enum class JitKind { RENDER, SS, TRACE, ADAPTIVE, LENS, LENS_SEAM, ADAPTIVE_SEAM };
 struct JitKindFacts {
     const char *entry, *header, *program;  // entry point; the header beside the core ("": none); the program text handed to hiprtc
     const char *aot_prefix, *args_line;    // of the ahead-of-time id (SS, ADAPTIVE, LENS: the factor follows); of the key's argument-size line
@@ -40,13 +42,14 @@ struct JitKindFacts {
     const char* aot_suffix = "";           // of the ahead-of-time id, after the hash
 };
 inline const JitKindFacts& jit_kind_facts(JitKind kind) {
-    static const JitKindFacts facts[6] = {
+    static const JitKindFacts facts[7] = {
         {"render_kernel_spec", "", "#include \"rtc_kernel_core.h\"\n", "aot_", nullptr},
         {"ss_render_kernel_spec", "rtc_supersample.h", "#include \"rtc_supersample.h\"\n", "aot_ss", nullptr},
         {"trace_kernel_spec", "rtc_trace.h", "#include \"rtc_trace.h\"\n", "aot_trace_", "trace args "},
         {"adaptive_refine_kernel_spec", "rtc_adaptive.h", "#include \"rtc_adaptive.h\"\n", "aot_adaptive", "adaptive args "},
         {"lens_render_kernel_spec", "rtc_lens.h", "#include \"rtc_lens.h\"\n", "aot_lens", "lens args ", "rtc_supersample.h"},
-        {"lens_render_kernel_spec", "rtc_lens_seam.h", "#include \"rtc_lens_seam.h\"\n", "aot_lens", "lens args ", "rtc_lens.h", "rtc_supersample.h", ".seam"}};
+        {"lens_render_kernel_spec", "rtc_lens_seam.h", "#include \"rtc_lens_seam.h\"\n", "aot_lens", "lens args ", "rtc_lens.h", "rtc_supersample.h", ".seam"},
+        {"adaptive_seam_kernel_spec", "rtc_adaptive_seam.h", "#include \"rtc_adaptive_seam.h\"\n", "aot_adaptive_seam", "adaptive seam args ", "rtc_adaptive.h"}};
     return facts[(int)kind];
 }
 // (the plain kernels' names do not move: only the other four fold their headers' text into a hash)
@@ -54,11 +57,12 @@ inline uint64_t source_hash_of(JitKind kind, uint64_t h, const std::string& besi
 
 // Identifies the ahead-of-time kernels of this build by the source they were compiled from: "aot_<hash>", "aot_ss<k>_<hash>",
 // "aot_trace_<hash>", "aot_adaptive<k>_<hash>", "aot_lens<k>_<hash>" -- and "aot_lens<k>_<hash>.seam", the one-call seam's lens
-// kernel, whose hash is its own: it folds rtc_lens_seam.h in as well.
+// kernel, whose hash is its own: it folds rtc_lens_seam.h in as well -- and "aot_adaptive_seam<k>_<hash>", the seam's adaptive kernels
+// (k = 1: the halo pass), whose hash folds in rtc_adaptive.h and then rtc_adaptive_seam.h.
 inline std::string aot_kernel_id(JitKind kind, uint32_t k, const std::string& core, const std::string& beside) {
     char hash[24];
     snprintf(hash, sizeof(hash), "%016llx", (unsigned long long)source_hash_of(kind, fnv1a(core), beside));
-    const bool factor = kind == JitKind::SS || kind == JitKind::ADAPTIVE || kind == JitKind::LENS || kind == JitKind::LENS_SEAM;
+    const bool factor = kind == JitKind::SS || kind == JitKind::ADAPTIVE || kind == JitKind::LENS || kind == JitKind::LENS_SEAM || kind == JitKind::ADAPTIVE_SEAM;
     return jit_kind_facts(kind).aot_prefix + (factor ? std::to_string(k) + "_" : std::string()) + hash + jit_kind_facts(kind).aot_suffix;
 }
 
@@ -66,6 +70,7 @@ inline std::string aot_kernel_id(JitKind kind, uint32_t k, const std::string& co
 struct JitArgSizes {
     size_t render, trace, adaptive;  // sizeof RenderArgs, TraceArgs, AdaptiveRefineArgs
     size_t lens = 0;                 // sizeof LensRenderArgs
+    size_t adaptive_seam = 0;        // sizeof AdaptiveSeamArgs
 };
 // The key's text after the options: compiler version, ABI, the size of RenderArgs -- and of the kind's own argument block (its
 // layout is its header's text, hashed as well).
@@ -73,7 +78,8 @@ inline std::string jit_key_tail(JitKind kind, int hiprtc_major, int hiprtc_minor
     std::string t = "hiprtc " + std::to_string(hiprtc_major) + "." + std::to_string(hiprtc_minor) + " abi " + std::to_string(RTC_ABI_VERSION) + " args " +
                     std::to_string(sizes.render) + "\n";
     if (const char* line = jit_kind_facts(kind).args_line)
-        t += line + std::to_string(kind == JitKind::TRACE ? sizes.trace : kind == JitKind::LENS || kind == JitKind::LENS_SEAM ? sizes.lens : sizes.adaptive) + "\n";
+        t += line + std::to_string(kind == JitKind::TRACE ? sizes.trace : kind == JitKind::LENS || kind == JitKind::LENS_SEAM ? sizes.lens
+                                   : kind == JitKind::ADAPTIVE_SEAM ? sizes.adaptive_seam : sizes.adaptive) + "\n";
     return t;
 }
 

@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -134,6 +135,8 @@ struct DevState {
     rtc_ctx* ctx = nullptr;
     char* d_out = nullptr;  // this device's rows, band after band: f32 RGB, or bytes (opts->quantize)
     size_t d_out_cap = 0;
+    char* d_base = nullptr;  // rtc_render_adaptive, byte mode: this device's rows of the f32 base frame B (f32 mode: d_out holds them)
+    size_t d_base_cap = 0;
     char* h_stage[2] = {nullptr, nullptr};  // pinned
     size_t stage_cap = 0;
     hipStream_t s_render = nullptr, s_copy2[2] = {nullptr, nullptr};  // chunks alternate between two copy streams: two DMA engines
@@ -150,6 +153,7 @@ struct DevState {
         (void)hipDeviceSynchronize();
         if (ctx) rtc_ctx_destroy(ctx);
         if (d_out) (void)hipFree(d_out);
+        if (d_base) (void)hipFree(d_base);
         for (char*& h : h_stage)
             if (h) (void)hipHostFree(h), h = nullptr;
         if (h_done) (void)hipHostFree(h_done);
@@ -206,8 +210,17 @@ struct Share {
     std::vector<Band> bands;     // all bands of the device, in compact order
     uint32_t next_copy = 0;      // chunks [0, next_copy) have their transfer queued
     uint32_t next_unstage = 0;   // pageable output: chunks [0, next_unstage) are in `out`
+    void* d_mask = nullptr;      // rtc_render_adaptive with a mask: the share's mask, compact like the share (the context's buffer)
     uint32_t chunk_row0(uint32_t j) const { return std::min(rows, j * chunk_rows); }
     uint32_t chunk_row1(uint32_t j) const { return std::min(rows, (j + 1) * chunk_rows); }
+};
+
+// rtc_render_adaptive's own arguments
+struct AdaptiveCall {
+    uint32_t k;
+    float threshold;
+    void* mask_u8;
+    rtc_seam_adaptive_stats* out;
 };
 
 }  // namespace
@@ -254,11 +267,21 @@ int32_t rtc_diag_seam_progress(uint32_t k, uint32_t out[2]) {
 // are the output's -- the fine frame exists only inside the contexts, rtc_ctx_set_scene_ss).
 // rtc_render_lens (`lens_call`: ss = 2, 4 and a lens, both checked here): the same, the contexts being lens contexts
 // (rtc_ctx_set_scene_lens) -- a ray depends only on its global fine (x, y), so bands, chunks and staging need nothing new.
+// rtc_render_adaptive (`ad`; ss = 1: the contexts are plain ones): an entry's base pass is rtc_render_ex's launch without progress
+// words, into its compact f32 share; behind it on the same stream, with no host read in between, the halo pass, the banded mask and
+// the refinement (rtc::ctx_adaptive_seam; csrc/rtc_adaptive_seam.h); the share then leaves as a launch that cannot report does, chunk
+// by chunk once its stream is done, and the mask after it.
 static rtc_status render_seam(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, uint32_t ss, const rtc_opts* opts, void* out,
-                              rtc_stats* stats, bool lens_call = false, const rtc_lens* lens = nullptr) {
-    if (!out || !camera) return fail(RTC_ERR_INVALID_ARG, "%s: null argument", lens_call ? "rtc_render_lens" : "rtc_render");
+                              rtc_stats* stats, bool lens_call = false, const rtc_lens* lens = nullptr, const AdaptiveCall* ad = nullptr) {
+    if (!out || !camera) return fail(RTC_ERR_INVALID_ARG, "%s: null argument", ad ? "rtc_render_adaptive" : lens_call ? "rtc_render_lens" : "rtc_render");
     if (camera->width == 0 || camera->height == 0) return fail(RTC_ERR_INVALID_ARG, "empty canvas");
     rtc_camera fine = *camera;
+    if (ad) {  // host only, in this order: the threshold, the factor, the fine frame (`fine` stays the camera: the statistics are the base frame's)
+        if (!(ad->threshold >= 0.0f) || !std::isfinite(ad->threshold)) return fail(RTC_ERR_INVALID_ARG, "rtc_render_adaptive: the threshold must be finite and >= 0");
+        if (ad->k != 2u && ad->k != 4u) return fail(RTC_ERR_INVALID_ARG, "rtc_render_adaptive: supersampling factor %u: 2 or 4 rays per pixel side", ad->k);
+        rtc_camera refined;
+        RTC_TRY(rtc_camera_supersampled(camera, ad->k, &refined));
+    }
     if (lens_call) {  // host only, in check_lens_args' order: the lens (null: an error, not a frame without one), the factor, the fine frame
         RTC_TRY(check_lens_args("rtc_render_lens", camera, ss, lens, &fine));
     } else if (ss != 1u) {  // host only: answered on a machine without a device
@@ -354,7 +377,17 @@ static rtc_status render_seam(const rtc_scene* scene, const rtc_camera* camera, 
         plan.epoch = S.epoch;
         plan.want_chunks = (uint32_t)std::min<size_t>(24, std::max<size_t>(1, ((size_t)sh.rows * row_out + (4u << 20) - 1) / (4u << 20)));
         plan.n_chunks = plan.chunk_rows = 0u;
-        RTC_TRY(ctx_render_slot(S.ctx, depth, &part, S.d_out, S.s_render, 0u, &plan, quantize));
+        if (ad) {
+            char* base = S.d_out;
+            if (quantize) {
+                RTC_TRY(grow_device(&S.d_base, &S.d_base_cap, std::max<size_t>(1, (size_t)sh.rows * W * 12)));
+                base = S.d_base;
+            }
+            RTC_TRY(ctx_render_slot(S.ctx, depth, &part, base, S.s_render, 0u, nullptr, false));
+            RTC_TRY(ctx_adaptive_seam(S.ctx, depth, ad->k, ad->threshold, &part, base, quantize ? S.d_out : nullptr, ad->mask_u8 != nullptr, S.s_render, &sh.d_mask));
+        } else {
+            RTC_TRY(ctx_render_slot(S.ctx, depth, &part, S.d_out, S.s_render, 0u, &plan, quantize));
+        }
         sh.reports = plan.n_chunks != 0u;
         S.last_reported = sh.reports, S.last_chunks = 0u;
         if (sh.reports) {
@@ -505,6 +538,22 @@ static rtc_status render_seam(const rtc_scene* scene, const rtc_camera* camera, 
         HIP_TRY(hipSetDevice(g_state[k].device));
         for (hipStream_t c : g_state[k].s_copy2) HIP_TRY(hipStreamSynchronize(c));
     }
+    // rtc_render_adaptive's mask: every share's stream is done; band by band to where the rows belong (a plain copy into host memory,
+    // pageable or page-locked: a byte a pixel, behind a frame of three or twelve)
+    for (uint32_t k = 0; ad && k < D; k++) {
+        DevState& S = g_state[k];
+        if (!shares[k].d_mask) continue;
+        HIP_TRY(hipSetDevice(S.device));
+        for (const Band& b : shares[k].bands) {
+            char* dst = (char*)ad->mask_u8 + (size_t)b.y0 * W;
+            const char* src = (const char*)shares[k].d_mask + b.src_row * W;
+            const size_t n = (size_t)b.rows * W;
+            if (!on_device) HIP_TRY(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
+            else if (S.device == devices[0]) HIP_TRY(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, S.s_copy2[0]));
+            else HIP_TRY(hipMemcpyPeerAsync(dst, devices[0], src, S.device, n, S.s_copy2[0]));
+        }
+        if (on_device) HIP_TRY(hipStreamSynchronize(S.s_copy2[0]));
+    }
     const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
 #ifdef RTC_DEV_SWITCHES
     t_copied = since();
@@ -512,6 +561,8 @@ static rtc_status render_seam(const rtc_scene* scene, const rtc_camera* camera, 
     // ---- statistics -------------------------------------------------------------------------------------------------
     rtc_stats total;
     std::memset(&total, 0, sizeof(total));
+    rtc_seam_adaptive_stats ad_total;
+    std::memset(&ad_total, 0, sizeof(ad_total));
     for (uint32_t k = 0; k < D; k++) {
         DevState& S = g_state[k];
         HIP_TRY(hipSetDevice(S.device));
@@ -524,7 +575,15 @@ static rtc_status render_seam(const rtc_scene* scene, const rtc_camera* camera, 
         total.kernel_ms = std::max(total.kernel_ms, s.kernel_ms);
         total.launches += s.launches;
         total.flags |= s.flags;
+        if (ad) {
+            rtc_seam_adaptive_stats a;
+            RTC_TRY(ctx_adaptive_seam_collect(S.ctx, &a));
+            ad_total.refined_pixels += a.refined_pixels, ad_total.refine_rays += a.refine_rays;
+            ad_total.halo_pixels += a.halo_pixels, ad_total.halo_rays += a.halo_rays;
+            ad_total.mask_ms = std::max(ad_total.mask_ms, a.mask_ms), ad_total.refine_ms = std::max(ad_total.refine_ms, a.refine_ms);
+        }
     }
+    if (ad && ad->out) *ad->out = ad_total;
     total.pixels = (uint64_t)(fine.width - 1) * (fine.height - 1);  // (supersampled: the fine frame's, as rays and shaded_hits are)
     total.rows = H;
     total.gather_ms = (float)wall_ms;
@@ -551,6 +610,12 @@ rtc_status rtc_render_ss(const rtc_scene* scene, const rtc_camera* output_camera
 rtc_status rtc_render_lens(const rtc_scene* scene, const rtc_camera* output_camera, int32_t depth, uint32_t k, const rtc_lens* lens,
                            const rtc_opts* opts, void* out, rtc_stats* stats) {
     return render_seam(scene, output_camera, depth, k, opts, out, stats, true, lens);
+}
+
+rtc_status rtc_render_adaptive(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, uint32_t k, float threshold, const rtc_opts* opts,
+                               void* out, void* mask_u8, rtc_stats* stats, rtc_seam_adaptive_stats* ad) {
+    const AdaptiveCall call = {k, threshold, mask_u8, ad};
+    return render_seam(scene, camera, depth, 1u, opts, out, stats, false, nullptr, &call);
 }
 
 rtc_status rtc_render(const rtc_scene* scene, const rtc_camera* camera, int32_t depth, int32_t device, float* out_rgb,

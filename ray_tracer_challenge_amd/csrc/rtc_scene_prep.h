@@ -1814,6 +1814,20 @@ inline KernelVariant refine_variant(const ScenePlan& p, uint32_t k) {
     v.kind = JitKind::ADAPTIVE, v.k = k;
     return v;
 }
+// The adaptive kernels of the one-call seam (rtc_adaptive_seam.h; rtc_render_adaptive), k = 2, 4: the refinement of a part's share,
+// adaptive_seam_kernel<...;ss=k>; k = 1: its halo pass, adaptive_seam_kernel<...;halo>.  A ray stream's options with
+// -DRTC_SPEC_ADAPTIVE_SEAM=k in the place of -DRTC_SPEC_TRACE=1: another kind, so other ids and cache entries than the persistent
+// context's refinement kernels, which keep theirs.
+inline KernelVariant seam_refine_variant(const ScenePlan& p, uint32_t k) {
+    KernelVariant v = trace_variant(p);
+    for (std::string* name : {&v.family_name, &v.spec_name}) {
+        *name = with_prefix(*name, "trace_", "adaptive_seam_");
+        if (!name->empty()) name->insert(name->size() - 1, k == 1u ? std::string(";halo") : ";ss=" + std::to_string(k));
+    }
+    if (!v.defs.empty()) v.defs.back() = "-DRTC_SPEC_ADAPTIVE_SEAM=" + std::to_string(k);
+    v.kind = JitKind::ADAPTIVE_SEAM, v.k = k;
+    return v;
+}
 // A variant with a frame stack of at least `depth` levels, for recursion deeper than RTC_STACK_DEPTH_BASE: 16, 32, ... up to
 // RTC_MAX_DEPTH (deep_stack_cap), -DRTC_SPEC_MAX_DEPTH=<cap> last.  The recursion frames of such a kernel all live in per-lane
 // scratch -- the LDS placement of the first levels (a tuning of the depth-5 glass-and-mirror frame) is not carried over.

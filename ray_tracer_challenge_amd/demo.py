@@ -38,7 +38,13 @@ def main(argv=None):
     ap.add_argument("--aperture", type=float, default=None, metavar="R",
                     help="depth of field: the radius of a thin lens (world units); needs --supersample 2 or 4 and --focus")
     ap.add_argument("--focus", type=float, default=None, metavar="D", help="... and the distance in front of the camera that is sharp")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="T",
+                    help="adaptive supersampling: K x K rays only where neighbouring pixels differ by more than T; needs --supersample 2 or 4")
     a = ap.parse_args(argv)
+    if a.adaptive is not None and a.supersample == 1:
+        ap.error("--adaptive needs --supersample 2 or 4: the factor of the refined pixels")
+    if a.adaptive is not None and a.aperture is not None:
+        ap.error("--adaptive takes no lens: adaptive lens frames are not offered")
     if (a.aperture is None) != (a.focus is None):
         ap.error("--aperture and --focus go together")
     if a.aperture is not None and a.supersample == 1:
@@ -58,6 +64,8 @@ def main(argv=None):
     if a.aperture is not None:  # a lens frame, through the one-call seam like every other frame here (rtc_render_lens)
         from .api import Lens
         canvas = camera.render(world, depth, supersample=a.supersample, lens=Lens(a.aperture, a.focus))
+    elif a.adaptive is not None:  # adaptive supersampling, through the seam as well (rtc_render_adaptive)
+        canvas = camera.render(world, depth, supersample=a.supersample, adaptive=a.adaptive)
     else:
         canvas = camera.render(world, depth) if a.supersample == 1 else camera.render(world, depth, supersample=a.supersample)
     st = camera.last_stats
