@@ -607,6 +607,11 @@ rtc_status rtc_ctx_render_hits(rtc_ctx* ctx, const rtc_partition* part, const rt
  * gives pixel y*W+x; d_out_rgb n x 3 f32.  Asynchronous on `stream`.  depth 0 .. RTC_MAX_DEPTH as rtc_ctx_render.
  * The direction is used as given (the reference's color_at does not normalise it either).  Rays with non-finite
  * components are the caller's error: their colour is unspecified.
+ * Origins may lie anywhere: no shortcut of the scene's preparation is argued from where the context's camera stands without
+ * a guard that each ray carries itself -- a ray that starts beyond the reach of the library's own hierarchy over a flat world
+ * (more than 100 of the world's smallest half-axis across, or a coordinate beyond 2 500 of it) is traced against every object
+ * in turn, as are the rays of its wave.  The same holds for rtc_ctx_trace_reordered, rtc_ctx_trace_hits and both ends of an
+ * rtc_ctx_is_shadowed pair.
  * One lane per ray, ray i in thread i: a wave is 64 consecutive rays, and rays that are neighbours in space trace fastest
  * as neighbours in the buffers.  The kernel is the context's ahead-of-time family or, where rtc_ctx_set_scene's
  * specialisation policy -- with n in the place of the frame's pixel count; RTC_AMD_SPECIALIZE=0|1 as there -- asks for

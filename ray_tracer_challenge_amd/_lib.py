@@ -268,6 +268,8 @@ EXTRA = {"rtc_powf_host": (None, [FP, FP, C.c_uint32, FP]),
          "rtc_diag_reorder_plan": (C.c_uint32, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
          # rtc_scene_prep.h on the host: digests of what flatten packs and the text of plan_scene's choice (tests/test_scene_prep.py)
          "rtc_diag_scene_plan": (C.c_int, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.c_char_p, C.c_uint32, C.POINTER(C.c_uint64)]),
+         # ... and whether a context of the scene gets the library's own hierarchy, with or without a lens (tests/test_lens_boundary.py)
+         "rtc_diag_flat_bvh": (C.c_int32, [C.POINTER(rtc_scene), C.POINTER(rtc_camera), C.POINTER(rtc_lens)]),
          # rtc_jit.h's disk-cache entries and rtc_scene_prep.h's deep-recursion stack cap (tests/test_jit_plan.py)
          "rtc_diag_jit_cache_publish": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64]),
          "rtc_diag_jit_cache_read": (C.c_int64, [C.c_char_p, C.c_char_p, C.c_uint64]),

@@ -131,6 +131,11 @@ struct rtc_ctx {
     rtc_lens lens = {0.0f, 1.0f, 0u};
     float4* d_soa = nullptr;
     size_t soa_cap = 0;  // float4 entries
+    // Ray streams on a flat world with a hierarchy of the library's own (rtc_trace.h StreamGuard, ERROR_BUDGET.md B9): the entry list
+    // with every box opened (grow-only) and what tells a ray that needs it; stream_guard.open_trav is null for every other scene
+    float4* d_open_trav = nullptr;
+    size_t open_trav_cap = 0;  // float4 entries
+    StreamGuard stream_guard = {nullptr, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f};
     float* d_texels = nullptr;  // UVImage canvases (RGB f32), grow-only
     size_t texel_cap = 0;       // floats
     uint32_t n_objects = 0;
@@ -610,6 +615,7 @@ void rtc_ctx_destroy(rtc_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->d_soa) (void)hipFree(c->d_soa);
+    if (c->d_open_trav) (void)hipFree(c->d_open_trav);
     if (c->d_texels) (void)hipFree(c->d_texels);
     if (c->d_block_counts) (void)hipFree(c->d_block_counts);
     if (c->d_progress) (void)hipFree(c->d_progress);
@@ -936,7 +942,8 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     std::vector<float> heavy_boxes;
     SceneRegion region;
     const Policy& P = c->policy;
-    rtc_status st = flatten(P, scene, camera, &hdr, &soa, &texels, &heavy_boxes, &region);
+    FlatHull flat_hull;
+    rtc_status st = flatten(P, scene, camera, &hdr, &soa, &texels, &heavy_boxes, &region, false, &flat_hull, lens ? lens->aperture_radius : 0.0f);
     if (st != RTC_OK) return st;
     HIP_TRY(hipSetDevice(c->device));
     const bool resident = same_records(c, soa, texels);
@@ -967,6 +974,16 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
         }
         if (!soa.empty()) HIP_TRY(grow(&c->d_soa, &c->soa_cap, soa.size()));
         HIP_TRY(hipMemcpy(c->d_soa, soa.data(), soa.size() * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    // the stream kernels' guard (nothing is in flight: the synchronisation above)
+    c->stream_guard.open_trav = nullptr;
+    if (hdr.internal_boxes && hdr.n_trav) {
+        const std::vector<float4> open = open_flat_bvh(soa.data() + soa_index(SOA_COLUMNS, padded_count(hdr.n_objects), 0), hdr.n_trav);
+        HIP_TRY(grow(&c->d_open_trav, &c->open_trav_cap, open.size()));
+        HIP_TRY(hipMemcpy(c->d_open_trav, open.data(), open.size() * sizeof(float4), hipMemcpyHostToDevice));
+        for (int a = 0; a < 3; a++) c->stream_guard.lo[a] = flat_hull.lo[a], c->stream_guard.hi[a] = flat_hull.hi[a];
+        c->stream_guard.r_min = flat_hull.r_min;
+        c->stream_guard.open_trav = c->d_open_trav;
     }
     ScenePlan plan = plan_scene(P, hdr, soa, scene, camera, heavy_boxes, region);  // which kernel will render this scene
     // Ray streams (rtc_ctx_trace) and the refinement of an adaptive frame: kernels of their own, none compiled yet -- the first call
@@ -1815,6 +1832,16 @@ rtc_status rtc_diag_scene_plan(const rtc_scene* scene, const rtc_camera* camera,
     return RTC_OK;
 }
 
+// Does a context of this scene and camera -- under this lens, or none (null) -- get a hierarchy of the library's own (build_flat_bvh)?
+// Host only, under the environment's policy: 1 / 0, or -1 where the scene is refused.  (A lens widens where primary rays start.)
+int32_t rtc_diag_flat_bvh(const rtc_scene* scene, const rtc_camera* camera, const rtc_lens* lens) {
+    SceneHdr hdr;
+    std::vector<float4> soa;
+    std::vector<float> texels;
+    if (flatten(Policy::from_env(), scene, camera, &hdr, &soa, &texels, nullptr, nullptr, false, nullptr, lens ? lens->aperture_radius : 0.0f) != RTC_OK) return -1;
+    return hdr.internal_boxes ? 1 : 0;
+}
+
 // rtc_jit.h's cache entries and rtc_scene_prep.h's stack cap, as they are (tests/test_jit_plan.py).  _read: the code's length, or -1.
 int32_t rtc_diag_jit_cache_publish(const char* dir, const char* file, const void* bytes, uint64_t n) {
     return publish_cache_entry(dir, std::string(dir) + "/" + file, std::string((const char*)bytes, (size_t)n)) ? 1 : 0;
@@ -1925,6 +1952,7 @@ static rtc_status trace_launch(rtc_ctx* c, int32_t depth, const void* d_origins,
     TraceArgs a;
     a.hdr = launch_hdr(c, depth, 1u);
     a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.guard = c->stream_guard;
     a.origins = (const float4*)d_origins, a.directions = (const float4*)d_directions, a.keys = (const uint32_t*)d_keys;
     a.out = (float*)d_out_rgb;
     a.wave_counts = t.d_counts;
@@ -2164,6 +2192,7 @@ rtc_status rtc_ctx_trace_hits(rtc_ctx* c, const void* d_origins, const void* d_d
     TraceHitsArgs a;
     a.hdr = c->hdr;
     a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.guard = c->stream_guard;
     a.origins = (const float4*)d_origins, a.directions = (const float4*)d_directions, a.keys = (const uint32_t*)d_keys;
     a.planes = planes;
     a.n = n;
@@ -2193,6 +2222,7 @@ rtc_status rtc_ctx_is_shadowed(rtc_ctx* c, const void* d_light_positions, const 
     ShadowedArgs a;
     a.hdr = c->hdr;
     a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.guard = c->stream_guard;
     a.light_positions = (const float4*)d_light_positions, a.points = (const float4*)d_points;
     a.out = (int32_t*)d_out_i32;
     a.n = n;

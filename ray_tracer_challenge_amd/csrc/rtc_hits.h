@@ -13,6 +13,7 @@
 #define RTC_HITS_H
 
 #include "rtc_kernel_core.h"
+#include "rtc_trace.h"
 
 namespace rtc {
 
@@ -171,9 +172,11 @@ __global__ __launch_bounds__(256, LIGHT ? RTC_HITS_LIGHT_WAVES : 1) void hits_ke
 // of made from the camera, one lane per ray, ray i in thread i of a 1-D grid, so a wave is whichever 64 rays the caller put
 // side by side.  Everything behind the loads is first_hit / is_shadowed as the resident scene's SceneHdr switches them.
 // Not here, because a stream has no frame: tiles, the scene-box early-out of primary_ray, block lists, lane sharing.
+// `guard` (rtc_trace.h StreamGuard): ERROR_BUDGET.md B9 for rays that start where the caller says.
 struct TraceHitsArgs {
     SceneHdr hdr;
     SceneSoA soa;
+    StreamGuard guard;
     const float4* origins;     // [n] x, y, z read; w ignored (as trace_body)
     const float4* directions;  // [n] likewise; used as given
     const uint32_t* keys;      // [n] jitter keys, or nullptr: ray i draws as pixel i (wave-uniform: a kernel argument)
@@ -188,12 +191,19 @@ __global__ __launch_bounds__(256, LIGHT ? RTC_HITS_LIGHT_WAVES : 1) void trace_h
     if (i >= A.n) return;
     const float4 o4 = A.origins[i], d4 = A.directions[i];
     const uint32_t key = A.keys != nullptr ? A.keys[i] : i;
-    first_hit<NOBJ, SIMPLE, LIGHT>(A.hdr, A.soa, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), key, A.planes, i);
+    const V3 origin = v3(o4.x, o4.y, o4.z);
+    if constexpr (NOBJ < 0) {
+        const SceneSoA soa = guarded_soa(A.guard, A.soa, within_flat_bvh_reach(A.guard, origin));
+        first_hit<NOBJ, SIMPLE, LIGHT>(A.hdr, soa, origin, v3(d4.x, d4.y, d4.z), key, A.planes, i);
+    } else {
+        first_hit<NOBJ, SIMPLE, LIGHT>(A.hdr, A.soa, origin, v3(d4.x, d4.y, d4.z), key, A.planes, i);
+    }
 }
 
 struct ShadowedArgs {
     SceneHdr hdr;
     SceneSoA soa;
+    StreamGuard guard;              // for both ends of a pair: either may be anywhere
     const float4* light_positions;  // [n] x, y, z read
     const float4* points;           // [n] likewise
     int32_t* out;                   // [n] 0 / 1
@@ -207,7 +217,13 @@ __global__ __launch_bounds__(256) void shadowed_kernel(ShadowedArgs A) {
     if (i >= A.n) return;
     const float4 l = A.light_positions[i], p = A.points[i];
     Counters cnt = {0u, 0u, 0u, 0u};
-    A.out[i] = is_shadowed<NOBJ>(A.hdr, A.soa, v3(l.x, l.y, l.z), v3(p.x, p.y, p.z), cnt) ? 1 : 0;
+    const V3 light = v3(l.x, l.y, l.z), point = v3(p.x, p.y, p.z);
+    if constexpr (NOBJ < 0) {
+        const SceneSoA soa = guarded_soa(A.guard, A.soa, within_flat_bvh_reach(A.guard, light) && within_flat_bvh_reach(A.guard, point));
+        A.out[i] = is_shadowed<NOBJ>(A.hdr, soa, light, point, cnt) ? 1 : 0;
+    } else {
+        A.out[i] = is_shadowed<NOBJ>(A.hdr, A.soa, light, point, cnt) ? 1 : 0;
+    }
 }
 
 }  // namespace rtc

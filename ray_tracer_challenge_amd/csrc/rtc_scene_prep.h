@@ -347,16 +347,24 @@ inline uint32_t choose_share_log2(const SceneHdr& hdr, uint32_t rows, const Poli
 // least 0.1 radius away from every object inside, where the exact intersection test reports a miss with a margin far
 // above its rounding error -- the same argument, and the same proviso, as for light-cone culling: the
 // quadratic's cancellation error grows with the ray origin's distance in radii, so the hierarchy is only built when
-// no ray can start more than 100 radii from any object (origins are the camera or points on the objects).  Ties in
+// no PRIMARY ray of the frame can start more than 100 radii from any object: the hull below holds the objects and the
+// camera -- and, under a thin lens, the lens disc (`lens_radius` along the camera's two axes, `cam_inv` the camera's
+// inverse transform).  Secondary rays start on the objects, inside the hull.  Rays that a caller brings (ray streams)
+// start anywhere: the stream kernels test this very condition for each ray and open every box for a ray that fails it
+// (`hull`: what they need for that -- the objects' own hull and the smallest half-axis; rtc_trace.h StreamGuard).  Ties in
 // hit distance go by object index in the tree kernels, so the visiting order does not matter either.
 // Eligible: scale+translate-only spheres and cubes, all of them (a plane's bounds are infinite).
-inline bool build_flat_bvh(const rtc_scene* scene, const float cam_origin[4], std::vector<float4>* trav) {
+struct FlatHull {
+    float lo[3], hi[3], r_min;
+};
+inline bool build_flat_bvh(const rtc_scene* scene, const float cam_origin[4], std::vector<float4>* trav, FlatHull* hull = nullptr,
+                           float lens_radius = 0.0f, const float* cam_inv = nullptr) {
     const uint32_t n = scene->n_objects;
     struct Box {
         float lo[3], hi[3];
     };
     std::vector<Box> box(n);
-    float all_lo[3] = {cam_origin[0], cam_origin[1], cam_origin[2]}, all_hi[3] = {cam_origin[0], cam_origin[1], cam_origin[2]};
+    float obj_lo[3] = {INFINITY, INFINITY, INFINITY}, obj_hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     float r_min = INFINITY;
     for (uint32_t i = 0; i < n; i++) {
         const rtc_object& o = scene->objects[i];
@@ -370,10 +378,23 @@ inline bool build_flat_bvh(const rtc_scene* scene, const float cam_origin[4], st
             const float pad = 0.1f * h + 1e-4f * (std::fabs(c) + h);
             box[i].lo[a] = c - h - pad;
             box[i].hi[a] = c + h + pad;
-            all_lo[a] = std::fmin(all_lo[a], c - h);
-            all_hi[a] = std::fmax(all_hi[a], c + h);
+            obj_lo[a] = std::fmin(obj_lo[a], c - h);
+            obj_hi[a] = std::fmax(obj_hi[a], c + h);
             r_min = std::fmin(r_min, h);
         }
+    }
+    if (hull) {
+        for (int a = 0; a < 3; a++) hull->lo[a] = obj_lo[a], hull->hi[a] = obj_hi[a];
+        hull->r_min = r_min;
+    }
+    float all_lo[3], all_hi[3];
+    for (int a = 0; a < 3; a++) {
+        // where primary rays start: the camera, or the four points of the lens's rim on its axes (a NaN or infinite radius: no hierarchy)
+        float reach = 0.0f;
+        if (lens_radius != 0.0f && cam_inv) reach = std::fabs(lens_radius) * std::fmax(std::fabs(cam_inv[4 * a]), std::fabs(cam_inv[4 * a + 1]));
+        if (!std::isfinite(reach)) return false;
+        all_lo[a] = std::fmin(obj_lo[a], cam_origin[a] - reach);
+        all_hi[a] = std::fmax(obj_hi[a], cam_origin[a] + reach);
     }
     float diag2 = 0.0f;
     for (int a = 0; a < 3; a++) diag2 += (all_hi[a] - all_lo[a]) * (all_hi[a] - all_lo[a]);
@@ -423,6 +444,23 @@ inline bool build_flat_bvh(const rtc_scene* scene, const float cam_origin[4], st
     };
     Rec::go(order, 0, n, box, trav);
     return true;
+}
+
+// build_flat_bvh's entry list with every box opened, for the rays of a stream that start beyond the hierarchy's reach (rtc_trace.h
+// StreamGuard): infinite bounds -- aabb_hit holds for every ray of finite origin and direction, +-inf times a reciprocal that may
+// itself be infinite keeps its sign -- an infinite slack and no q, so that nothing is pruned by distance either.  Skip indices, leaf
+// entries and their run lengths stay: the same walk, every leaf visited.  `trav`: the list as it stands in the scene's records.
+inline std::vector<float4> open_flat_bvh(const float4* trav, uint32_t n_trav) {
+    std::vector<float4> open(trav, trav + (size_t)n_trav * TRAV_STRIDE);
+    for (uint32_t k = 0; k < n_trav; k++) {
+        float4* e = &open[(size_t)k * TRAV_STRIDE];
+        if (e[1].w < 0.0f) continue;  // a leaf
+        e[0].x = e[0].y = e[0].z = -INFINITY;
+        e[1].x = e[1].y = e[1].z = INFINITY;
+        e[1].w = INFINITY;
+        e[2].x = 0.0f;
+    }
+    return open;
 }
 
 // A hierarchy of the library's own over every long run of boxed triangle leaves (the rings divide() leaves behind, group.rs:
@@ -723,7 +761,9 @@ struct Flatten {
     std::vector<float>* heavy_boxes;  // optional, see flatten
     SceneRegion* region;              // optional
     bool allow_sequence;
-    // (flatten fills the nine above, in the order of its own parameters, and the next three)
+    FlatHull* flat_hull;  // optional: filled where the world gets a hierarchy of the library's own (build_flat_bvh)
+    float lens_radius;    // of the frame's thin lens, 0 without one: primary rays start on its disc (build_flat_bvh)
+    // (flatten fills the eleven above, in the order of its own parameters, and the next three)
     uint32_t n = 0, np = 0;  // objects, and the stride of each column
     float cam_origin[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // camera.rs:70: origin = transform_inverse * point(0,0,0) (only with a camera)
     std::vector<Extent> extent;
@@ -830,7 +870,7 @@ struct Flatten {
     void flat_bvh_stream() {
         if (!(cam && n >= 16 && P.bvh)) return;
         std::vector<float4> trav;
-        if (build_flat_bvh(scene, cam_origin, &trav)) {
+        if (build_flat_bvh(scene, cam_origin, &trav, flat_hull, lens_radius, cam->inv)) {
             hdr->max_leaf_run = mark_leaf_runs(&trav, scene);
             hdr->internal_boxes = 1;
             hdr->n_trav = (uint32_t)(trav.size() / TRAV_STRIDE);
@@ -1301,13 +1341,13 @@ struct Flatten {
 // An error leaves *hdr half filled: callers discard it.
 inline rtc_status flatten(const Policy& P, const rtc_scene* scene, const rtc_camera* cam, SceneHdr* hdr, std::vector<float4>* soa,
                           std::vector<float>* texels, std::vector<float>* heavy_boxes = nullptr, SceneRegion* region = nullptr,
-                          bool allow_sequence = false) {
+                          bool allow_sequence = false, FlatHull* flat_hull = nullptr, float lens_radius = 0.0f) {
     if (!scene) return fail(RTC_ERR_INVALID_ARG, "scene is NULL");
     if (!scene->light) return fail(RTC_ERR_NO_LIGHT, "World light should be set");  // world.rs:66
     if (scene->n_objects && !scene->objects) return fail(RTC_ERR_INVALID_ARG, "scene.objects is NULL");
     std::memset(hdr, 0, sizeof(*hdr));
     hdr->n_objects = scene->n_objects;
-    Flatten f = {P, scene, cam, hdr, soa, texels, heavy_boxes, region, allow_sequence};
+    Flatten f = {P, scene, cam, hdr, soa, texels, heavy_boxes, region, allow_sequence, flat_hull, lens_radius};
     f.n = scene->n_objects;
     f.np = padded_count(f.n);
     soa->assign(soa_index(SOA_COLUMNS, f.np, 0), make_float4(0, 0, 0, 0));

@@ -20,9 +20,40 @@
 
 namespace rtc {
 
+// ERROR_BUDGET.md B9, per ray.  The library's own hierarchy over a flat world (rtc_scene_prep.h build_flat_bvh) turns a ray away
+// from a box padded by 10 % of the object, which is safe while the ray starts within 100 of the smallest half-axis of everything
+// (E2(i)) and no coordinate exceeds 2.5e3 of it (E1).  The host checks that for the camera; a stream's rays start where the caller
+// says.  So the stream kernels check it for the ray they trace: a wave one of whose origins fails walks `open_trav` instead -- the
+// same entry list with every box of the library's own opened (infinite bounds, infinite slack: aabb_hit holds for every finite
+// ray, nothing is pruned), i.e. every object in turn, the flat list's answer.  Rays that start on the objects -- the secondary
+// rays of such a lane -- would not need it and walk the open list too: correct, only slower.  A wave's choice, not a lane's: the
+// walk's entry index and records are wave-uniform.  GroupShape boxes are the reference's semantics and are never opened
+// (open_trav is null for every scene but a flat one with a hierarchy).
+struct StreamGuard {
+    const float4* open_trav;  // nullptr: nothing to guard
+    float lo[3], hi[3];       // the hull of the objects' bounds, as build_flat_bvh takes it
+    float r_min;              // the smallest half-axis
+};
+// build_flat_bvh's own condition with `p` in the camera's place, in its arithmetic; false for a NaN coordinate's comparison
+DI bool within_flat_bvh_reach(const StreamGuard& G, V3 p) {
+    const float lx = fminf(G.lo[0], p.x), ly = fminf(G.lo[1], p.y), lz = fminf(G.lo[2], p.z);
+    const float hx = fmaxf(G.hi[0], p.x), hy = fmaxf(G.hi[1], p.y), hz = fmaxf(G.hi[2], p.z);
+    const float diag2 = (hx - lx) * (hx - lx) + (hy - ly) * (hy - ly) + (hz - lz) * (hz - lz);
+    const float far_coord = fmaxf(fmaxf(fmaxf(fabsf(lx), fabsf(hx)), fmaxf(fabsf(ly), fabsf(hy))), fmaxf(fabsf(lz), fabsf(hz)));
+    const bool finite = p.x - p.x == 0.0f && p.y - p.y == 0.0f && p.z - p.z == 0.0f;
+    return finite && sqrtf(diag2) < 100.0f * G.r_min && far_coord <= 2.5e3f * G.r_min;
+}
+// The scene's records as this wave walks them.  Call it where every lane that will trace is active.
+DI SceneSoA guarded_soa(const StreamGuard& G, const SceneSoA& S, bool within_reach) {
+    SceneSoA s = S;
+    if (G.open_trav != nullptr && __any(!within_reach)) s.trav = G.open_trav;  // wave-uniform
+    return s;
+}
+
 struct TraceArgs {
     SceneHdr hdr;
     SceneSoA soa;
+    StreamGuard guard;
     const float4* origins;     // [n] x, y, z read; w ignored
     const float4* directions;  // [n] likewise; used as given (world.rs:88 does not normalise either)
     const uint32_t* keys;      // [n] jitter keys, or nullptr: ray i draws as pixel i (wave-uniform: a kernel argument)
@@ -52,7 +83,14 @@ DI void trace_body(const TraceArgs& A) {
     if (i < A.n) {
         const float4 o4 = A.origins[i], d4 = A.directions[i];
         const uint32_t key = A.keys != nullptr ? A.keys[i] : i;
-        const V3 col = color_at<NOBJ, SIMPLE>(H, A.soa, v3(o4.x, o4.y, o4.z), v3(d4.x, d4.y, d4.z), A.depth, key, cnt, stash);
+        const V3 origin = v3(o4.x, o4.y, o4.z);
+        V3 col;
+        if constexpr (NOBJ < 0) {  // (the other families walk no boxes of the library's own)
+            const SceneSoA soa = guarded_soa(A.guard, A.soa, within_flat_bvh_reach(A.guard, origin));
+            col = color_at<NOBJ, SIMPLE>(H, soa, origin, v3(d4.x, d4.y, d4.z), A.depth, key, cnt, stash);
+        } else {
+            col = color_at<NOBJ, SIMPLE>(H, A.soa, origin, v3(d4.x, d4.y, d4.z), A.depth, key, cnt, stash);
+        }
         float* dst = A.out + (size_t)i * 3;
         dst[0] = col.x;
         dst[1] = col.y;

@@ -338,3 +338,48 @@ def test_the_lens_kernels_are_planned_by_the_formula(name, _library_defaults):
         assert plan[lens + "aot_id"] == "aot_lens%d_%016x" % (k, source_hash("rtc_lens.h", source_hash("rtc_supersample.h", core)))
         seen |= {plan[lens + "cache_file"], plan[ss + "cache_file"], plan[lens + "aot_id"], plan[ss + "aot_id"]}
     assert len(seen) == 8 and plan["cache_file"] not in seen and plan["aot_id"] not in seen
+
+
+# ---------------------------------------------------------------- the lens and the library's own hierarchy (ERROR_BUDGET.md B9)
+def test_a_lens_too_wide_for_the_flat_hierarchy_drops_it(monkeypatch):
+    """build_flat_bvh pads its boxes for rays that start within 100 of the smallest half-axis of everything, and a lens frame's
+    primary rays start on the lens disc: cam_origin +- R along the camera's two axes belongs to the hull the plan tests.  Restated
+    here in double precision for tests/test_flat_bvh.py's cloud, and asked of the library a tenth below and above the radius at
+    which the restatement turns."""
+    from tests.test_flat_bvh import _cloud
+    for name in list(os.environ):
+        if name.startswith("RTC_AMD_"):
+            monkeypatch.delenv(name)
+    monkeypatch.setenv("RTC_AMD_SPECIALIZE", "0")
+    world, camera = _cloud(7, 20)
+    assert "bvh" in world.scene_plan(camera)[1]["family_name"]
+    cs = world._c()
+
+    def library(lens):
+        return L.lib().rtc_diag_flat_bvh(C.byref(cs.scene), C.byref(camera._cam), C.byref(lens._c) if lens is not None else None)
+
+    lo, hi, r_min = np.full(3, np.inf), np.full(3, -np.inf), np.inf
+    for ob in world.objects:
+        m = np.asarray(ob.transform, dtype=np.float64).reshape(4, 4)
+        c, h = m[:3, 3], np.abs(np.diag(m[:3, :3]))
+        lo, hi, r_min = np.minimum(lo, c - h), np.maximum(hi, c + h), min(r_min, float(h.min()))
+    inv = camera.transform_inverse.astype(np.float64)
+    origin, axes = inv[:3, 3], np.abs(inv[:3, :2]).max(axis=1)  # per world axis: the larger of the two camera axes' components
+
+    def restated(R):
+        l, h = np.minimum(lo, origin - R * axes), np.maximum(hi, origin + R * axes)
+        return bool(np.linalg.norm(h - l) < 100.0 * r_min and max(np.abs(l).max(), np.abs(h).max()) <= 2.5e3 * r_min)
+
+    assert restated(0.0) and not restated(1e3)
+    a, b = 0.0, 1e3
+    for _ in range(60):
+        mid = 0.5 * (a + b)
+        a, b = (mid, b) if restated(mid) else (a, mid)
+    assert 0.5 < a < 100.0, a  # (a lens of a useful size keeps the hierarchy; one as wide as the scene does not)
+    assert library(None) == 1
+    assert library(P.Lens(0.0, 14.0)) == 1
+    assert library(P.Lens(0.9 * a, 14.0)) == 1
+    assert library(P.Lens(1.1 * a, 14.0)) == 0
+    assert library(P.Lens(1e3, 14.0)) == 0
+    monkeypatch.setenv("RTC_AMD_BVH", "0")
+    assert library(None) == 0

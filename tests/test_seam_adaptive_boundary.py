@@ -283,7 +283,10 @@ def test_the_seams_adaptive_kernels_are_planned_by_the_formula(name, _library_de
 
 
 def test_every_earlier_entry_keeps_its_bytes(_library_defaults):
-    """The plan's text without its adaptive_seam<k>_ lines is, line by line, what the commit before printed -- for five scenes."""
+    """The plan's text without its adaptive_seam<k>_ lines is, line by line, what the commit before printed -- for five scenes.
+    (The ray-stream kernel's own five lines -- trace_args, trace_cache_file, trace_aot_id, trace_deep16_ / trace_deep32_cache_file --
+    stand in the stored text as they are since rtc_trace.h's per-ray guard of the flat hierarchy gave TraceArgs its StreamGuard;
+    every other kernel's lines, the render kernels' ids among them, are still that commit's.)"""
     with open(os.path.join(ROOT, "tests", "golden", "scene_plan_before_adaptive_seam.json")) as f:
         golden = json.load(f)
     assert len(golden["plans"]) == 5
