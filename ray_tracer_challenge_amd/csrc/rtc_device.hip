@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -30,6 +31,7 @@
 #include <vector>
 
 #include "rtc_internal.h"
+#include "rtc_owned.h"
 #include "rtc_launch_plan.h"
 #include "rtc_kernel_core.h"
 #include "rtc_hits.h"
@@ -97,13 +99,13 @@ static rtc_status select_device(int32_t device) {
 
 using namespace rtc;
 
+namespace {  // (the context's parts: this file's alone)
 struct BlockList {  // RenderArgs::tiles of one partition (build_block_list), resident on the device
-    uint32_t* d = nullptr;
+    DeviceArray<uint32_t> d;     // grown, never shrunk (hipMalloc / hipFree cost the animation's frames milliseconds)
     size_t n = 0, n_listed = 0;  // (n_listed: a grid's list leaves the padding out)
     // feedback (refine_block_list): the list as built, where its first launch leaves its waves' running times, and how far it is
     std::vector<uint32_t> host;
-    size_t d_cap = 0, ticks_cap = 0;  // dwords behind d / d_ticks: grown, never shrunk (hipMalloc / hipFree cost the animation's frames milliseconds)
-    uint32_t* d_ticks = nullptr;  // [4 n] wave times -- or, for kernels that do not time their waves, [4 n] uint4 work counts (a copy of block_counts)
+    DeviceArray<uint32_t> d_ticks;  // [4 n] wave times -- or, for kernels that do not time their waves, [4 n] uint4 work counts (a copy of block_counts)
     bool counts = false, swizzled = false, listed = false;  // (listed: a grid whose frames run from `d`, its blocks in order)
     // IDLE (regular grids): a scene's first frame -- nothing is measured before a second frame of the SAME scene shows that frames repeat
     enum { FRESH, TIMED, REFINED, IDLE } state = FRESH;
@@ -114,192 +116,208 @@ struct BlockList {  // RenderArgs::tiles of one partition (build_block_list), re
     // the times of the frame before it -- at the latest after sixteen scenes.
     uint32_t scene_changes = 0;
     bool animated = false, ev_recorded = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     double best_ms = 0.0, loss_ms = 0.0, recut_host_ms = 0.5;
 };
+// Scene tiles: the 16 x 16 tiles in which a primary ray can see anything (ScenePlan::scene_tile_mask) -- those some bounded entry's
+// padded box projects to (C5: 64 spheres, 7 % of 8192^2) and the near side of every top-level plane's horizon (C3: two thirds of the
+// frame).  Frames of such a scene are a zero-fill of the other tiles and one workgroup per listed tile (ctx_render_slot).
+struct SceneTileList {
+    DeviceArray<uint32_t> d;
+    size_t n = 0;
+    unsigned long long traced_pixels = 0ull;  // traced pixels (x < w - 1, y < h - 1) inside the listed tiles
+    DeviceArray<uint2> d_fill;  // the runs of tiles that are NOT listed, at most 64 tiles each: {x0 | n << 16, local row} (fill_tiles_kernel)
+    size_t n_fill = 0;
+    // feedback (order_scene_tiles): the list as launched, and where its first frame leaves its waves' work counts ([4 n] uint4, a
+    // copy of block_counts).  IDLE: a scene's first frame -- as for a regular grid, nothing is measured (or allocated) before a
+    // second frame of the same scene shows that frames repeat; FRESH: the next frame leaves its counts; TIMED: they are on the
+    // device; SETTLED: ordered, or left as it is
+    std::vector<uint32_t> host;
+    DeviceArray<uint4> d_counts;
+    enum { IDLE, FRESH, TIMED, SETTLED } state = IDLE;
+    bool ordered = false;  // SETTLED, and the list was re-ordered
+};
+// One kernel of the resident scene as the context keeps it -- the frame's, the ray streams', the refinement's of one factor:
+// what rtc_scene_prep.h planned for it, the scene-compiled kernel (scene_kernel_for) and, for recursion deeper than
+// RTC_STACK_DEPTH_BASE, the same kernel compiled once more with a longer frame stack on first use (deep_kernel).
+struct SceneKernel {
+    KernelVariant variant;        // options (written down whatever the policy says: deep_kernel may need them) and the two names
+    hipFunction_t fn = nullptr;   // scene-specialised kernel (hiprtc), or null: the ahead-of-time family
+    std::string fn_id;
+    std::map<int, std::pair<hipFunction_t, std::string>> deep;  // by stack depth: the kernel and its id
+    bool failed = false;          // hiprtc did not deliver fn: the ahead-of-time family from then on (note says why)
+    std::string note;
+};
+// ... and what outlives the scene beside it: the (kernel, stream) pairs launched once (warm_up).  One set per slot:
+// KernelFamily::key() is one value for the render and the ray-stream kernel of a family.
+typedef std::set<std::pair<const void*, const void*>> Warmed;
+typedef std::vector<std::pair<Event, Event>> EventPairs;
+}  // namespace
+
+// The context.  Its fields are two groups, and which group a field is in says how long it lives:
+//
+// (a) `scene`, the resident scene: replaced WHOLE, by one assignment, when rtc_ctx_set_scene* takes another scene, camera, factor
+//     or lens, and filled from the new plan.  `ready` is false from that assignment until the new scene is fully resident, and again
+//     when its kernel could not be compiled under RTC_AMD_SPECIALIZE=1.  Setting the very scene that is resident replaces nothing
+//     (a focus pull writes `lens`, a deferred compile `render` and the names).
+//       hdr, camera, ss_k, lens_mode, lens, stream_guard          what the launches take
+//       plan                                                      ScenePlan as plan_scene / plan_supersampled / plan_lens left it
+//                                                                 (spec_shares is cleared in it when the compile fails)
+//       render, kernel_name, kernel_id, jit_deferred              the frame's kernel slot and what is reported of it
+//       wf_disabled                                               a frame of this scene overflowed the level-by-level pools
+//       trace.{kernel, name, id, last}                            the ray streams' slot, the last trace's names, "the last launch was
+//                                                                 a trace" (a new scene reports renders again)
+//       adaptive.{kernel[2], failed, note, name, id}              the refinement's slots and names
+//       adaptive_seam.{kernel[3], failed, note, name, id, halo_*} ... and the one-call seam's
+//
+// (b) everything else, kept for the context's life.  Set once: device, policy, n_cus, lazy_jit, seam_kernels, reorder.dir_major.
+//     Grow-only memory and lazily made events and streams (rtc_owned.h), freed by the destructor: every d_* array, h_feedback, the
+//     event pairs, fill_stream, ev_fork / ev_join, the refinement's and the reordering's ev[].
+//     The records' host mirror (soa_host, texels_host) lives with d_soa / d_texels: a camera-only change keeps all four.
+//     Bookkeeping about the PROCESS, not the scene: the warmed sets (code objects launched once per queue), wgs_per_cu (occupancy of a
+//     code object).
+//     The lists: block_lists survive a scene of the same frame, factor and mode under restart_block_lists' rule and are dropped
+//     otherwise; scene_tile_lists are dropped by every scene; both are dropped when a deferred compile delivers the scene's kernel.
+//     And the record of the last launches, which a new scene does NOT reset -- each is written by the call it describes and read by
+//     the statistics, whatever scene has been set in between (tests/test_gpu_ctx_lifetime.py pins what they report):
+//       tree_waves        the last TREE scene's waves per SIMD: recut_block_list reads it for the area-light lists of flat scenes too
+//       rendered, events_used, last_rows, last_pixels, last_share_log2, wf_last
+//                         rtc_ctx_stats / rtc_ctx_kernel_name / rtc_diag_ctx_share_log2 after a set_scene still report the frame before
+//       trace.last_n, trace.events_used
+//                         likewise for the traces (trace.last itself is the scene's)
+//       adaptive.ran, adaptive_seam.ran, adaptive_seam.halo_pixels, reorder.ran, reorder.last_n
+//                         rtc_ctx_adaptive_stats / rtc_ctx_reorder_stats after a set_scene report the last call under the scene before
 struct rtc_ctx {
+    // ---- (a) the resident scene
+    struct Scene {
+        bool ready = false;  // fully resident: the render paths may use it
+        SceneHdr hdr = {};
+        rtc_camera camera = {};  // as rtc_ctx_set_scene took it
+        // Supersampling (rtc_ctx_set_scene_ss; rtc_supersample.h): 1, or k = 2 / 4 -- `hdr` is then the FINE camera's, and everything that
+        // plans, schedules and feeds back does so in fine space; only the canvas and rtc_stats.rows speak of the output frame
+        uint32_t ss_k = 1u;
+        // A thin lens (rtc_ctx_set_scene_lens; rtc_lens.h): the context is a supersampled one in every respect but its kernel -- the
+        // lens kernel of the same factor -- and the three words that kernel takes; a focus pull replaces the words and nothing else
+        bool lens_mode = false;
+        rtc_lens lens = {0.0f, 1.0f, 0u};
+        // Ray streams on a flat world with a hierarchy of the library's own (rtc_trace.h StreamGuard, ERROR_BUDGET.md B9): what tells a
+        // ray that needs the entry list with every box opened (d_open_trav); open_trav is null for every other scene
+        StreamGuard stream_guard = {nullptr, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f};
+        // Which kernel renders the scene and how its frames are cut (rtc_scene_prep.h): the block-list bitmap (heavy_tiles), the scene
+        // box's coverage, the scene rectangle, the scene-tile mask, what the scene's kernel was compiled with (spec_*)
+        ScenePlan plan;
+        SceneKernel render;               // compiled by rtc_ctx_set_scene (or deferred: lazy_jit); note: rtc_ctx_jit_status
+        std::string kernel_name;          // what rtc_ctx_render launches, for rtc_ctx_kernel_name()
+        std::string kernel_id;            // rtc_ctx_kernel_id(): names the code object (source + options + compiler), not the scene
+        bool jit_deferred = false;  // the kernel was left uncompiled by the scene's first sighting: the next render of this scene compiles it
+        bool wf_disabled = false;   // a frame overflowed the level-by-level renderer's pools: per-pixel kernels from then on
+        struct Trace {
+            SceneKernel kernel;    // trace_variant's, compiled by the first trace that asks for it
+            std::string name, id;  // of the last trace's kernel ("" before the first trace of the current scene)
+            bool last = false;     // the context's last launch was a trace: rtc_ctx_stats reports it
+        } trace;
+        struct Refine {
+            bool failed = false;   // hiprtc did not deliver one of the path's kernels: the ahead-of-time ones from then on, for all (note says why)
+            std::string note;
+            std::string name, id;  // of the last call's refinement kernel ("" before the first of the current scene)
+        };
+        struct Adaptive : Refine {
+            SceneKernel kernel[2];  // refine_variant's of k = 2, 4, compiled by the first call that asks for it
+        } adaptive;
+        struct AdaptiveSeam : Refine {
+            SceneKernel kernel[3];           // seam_refine_variant's of k = 1 (the halo pass), 2, 4
+            std::string halo_name, halo_id;  // of the last call's halo pass ("": the last call had no halo row)
+        } adaptive_seam;
+    } scene;
+
+    // ---- (b) kept for life
     int device = 0;
     Policy policy;  // the environment's switches as they were when the context was created
-    SceneHdr hdr;
-    bool has_scene = false;
-    // Supersampling (rtc_ctx_set_scene_ss; rtc_supersample.h): 1, or k = 2 / 4 -- `hdr` is then the FINE camera's, and everything that
-    // plans, schedules and feeds back does so in fine space; only the canvas and rtc_stats.rows speak of the output frame
-    uint32_t ss_k = 1u;
-    // A thin lens (rtc_ctx_set_scene_lens; rtc_lens.h): the context is a supersampled one in every respect but its kernel -- the
-    // lens kernel of the same factor -- and the three words that kernel takes; a focus pull replaces the words and nothing else
-    bool lens_mode = false;
-    rtc_lens lens = {0.0f, 1.0f, 0u};
-    float4* d_soa = nullptr;
-    size_t soa_cap = 0;  // float4 entries
-    // Ray streams on a flat world with a hierarchy of the library's own (rtc_trace.h StreamGuard, ERROR_BUDGET.md B9): the entry list
-    // with every box opened (grow-only) and what tells a ray that needs it; stream_guard.open_trav is null for every other scene
-    float4* d_open_trav = nullptr;
-    size_t open_trav_cap = 0;  // float4 entries
-    StreamGuard stream_guard = {nullptr, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f};
-    float* d_texels = nullptr;  // UVImage canvases (RGB f32), grow-only
-    size_t texel_cap = 0;       // floats
-    uint32_t n_objects = 0;
-    bool simple = false;  // every object scale+translate-only, no cylinder / cone, no patterns
-    // workspace of rtc_ctx_to_ppm (grow-only)
-    unsigned long long* d_ppm_rows = nullptr;  // per-row length, then offset; [h] is the total
-    uint32_t* d_ppm_bits = nullptr;
-    size_t ppm_rows_cap = 0, ppm_bits_cap = 0;
-    int n_cus = 0;                    // compute_units()
-    bool spec_shares = false;         // render.fn was compiled with -DRTC_SPEC_SHARE=1
-    bool spec_blocks_y = false;       // ... with -DRTC_SPEC_BLOCKS_Y=1 (several blocks per workgroup)
-    bool spec_rect = false;           // ... with -DRTC_SPEC_RECT=1 (scene rectangle launches: block offsets, zero-filling workgroups)
-    // One kernel of the resident scene as the context keeps it -- the frame's, the ray streams', the refinement's of one factor:
-    // what rtc_scene_prep.h planned for it, the scene-compiled kernel (scene_kernel_for) and, for recursion deeper than
-    // RTC_STACK_DEPTH_BASE, the same kernel compiled once more with a longer frame stack on first use (deep_kernel).
-    struct SceneKernel {
-        KernelVariant variant;        // options (written down whatever the policy says: deep_kernel may need them) and the two names
-        hipFunction_t fn = nullptr;   // scene-specialised kernel (hiprtc), or null: the ahead-of-time family
-        std::string fn_id;
-        std::map<int, std::pair<hipFunction_t, std::string>> deep;  // by stack depth: the kernel and its id
-        bool failed = false;          // hiprtc did not deliver fn: the ahead-of-time family from then on (note says why)
-        std::string note;
-        // (kernel, stream) pairs launched once (warm_up).  One set per slot: KernelFamily::key() is one value for the render and the
-        // ray-stream kernel of a family.  It outlives the scene.
-        std::set<std::pair<const void*, const void*>> warmed;
-        void reset(const KernelVariant& v) {  // another scene
-            variant = v;
-            fn = nullptr, failed = false;
-            fn_id.clear(), note.clear(), deep.clear();
-        }
-    };
-    SceneKernel render;               // compiled by rtc_ctx_set_scene (or deferred: lazy_jit); note: rtc_ctx_jit_status
-    std::string kernel_name;          // what rtc_ctx_render launches, for rtc_ctx_kernel_name()
-    // Block list of the current scene (RenderArgs::tiles): which 16 x 16 pixel tiles of the image a mesh projects to
-    // (row-major bitmap, empty: no block list), and the list last built -- for the partition it was built for
-    int tree_waves = 6;  // waves per SIMD the scene's tree kernel was compiled for (rtc_ctx_set_scene)
+    int n_cus = 0;  // compute_units()
     bool lazy_jit = false;      // a context of the one-call seam (rtc::ctx_mark_one_shot): see jit_get
     // ... and what else such a context is: supersampled, its kernels are the variant that stores bytes and reports its rows
     // (rtc_supersample.h SEAM: ss_seam_render_kernel<...>, -DRTC_SPEC_SS_SEAM=1; with a lens rtc_lens_seam.h: lens_seam_render_kernel<...>,
     // -DRTC_SPEC_LENS_SEAM=1), and ctx_render_slot accepts out_u8 / progress
     bool seam_kernels = false;
-    bool jit_deferred = false;  // the resident scene's kernel was left uncompiled by its first sighting: the next render of this scene compiles it
-    std::vector<uint8_t> heavy_tiles;
-    uint32_t heavy_w = 0, heavy_h = 0;
-    // key: band_rows, n_parts, part, lanes per pixel (log2; ~0: a regular grid's order), depth (what a block costs depends on it)
-    std::map<std::array<uint32_t, 5>, BlockList> block_lists;
-    float scene_box_coverage = 1.0f;  // share of the image the scene's box projects to (1: unknown / all of it)
-    uint32_t scene_rect[4] = {0u, 0u, 0u, 0u};  // the 16 x 16 tiles outside which no primary ray sees anything: [x0, x1) x [y0, y1); empty: unknown
-    // Scene tiles: the 16 x 16 tiles in which a primary ray can see anything -- those some bounded entry's padded box projects to (C5:
-    // 64 spheres, 7 % of 8192^2) and the near side of every top-level plane's horizon (C3: two thirds of the frame).  Frames of such a
-    // scene are a zero-fill of the other tiles and one workgroup per listed tile (ctx_render_slot).  Empty: not known / not worth it.
-    std::vector<uint8_t> scene_tile_mask;
-    uint32_t scene_tiles_w = 0u, scene_tiles_h = 0u;
-    bool scene_tiles_sparse = false;  // ScenePlan's: the list also serves frames whose rows are reported chunk by chunk
-    struct SceneTileList {
-        uint32_t* d = nullptr;
-        size_t n = 0;
-        unsigned long long traced_pixels = 0ull;  // traced pixels (x < w - 1, y < h - 1) inside the listed tiles
-        uint2* d_fill = nullptr;  // the runs of tiles that are NOT listed, at most 64 tiles each: {x0 | n << 16, local row} (fill_tiles_kernel)
-        size_t n_fill = 0;
-        // feedback (order_scene_tiles): the list as launched, and where its first frame leaves its waves' work counts ([4 n] uint4, a
-        // copy of block_counts).  IDLE: a scene's first frame -- as for a regular grid, nothing is measured (or allocated) before a
-        // second frame of the same scene shows that frames repeat; FRESH: the next frame leaves its counts; TIMED: they are on the
-        // device; SETTLED: ordered, or left as it is
-        std::vector<uint32_t> host;
-        uint4* d_counts = nullptr;
-        enum { IDLE, FRESH, TIMED, SETTLED } state = IDLE;
-        bool ordered = false;  // SETTLED, and the list was re-ordered
-    };
-    hipStream_t fill_stream = nullptr;  // the zero-fill of a tile launch runs beside the render kernel (fork / join by events)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    std::map<std::array<uint32_t, 3>, SceneTileList> scene_tile_lists;  // per partition {band_rows, n_parts, part}
-    float scene_rect_coverage = 1.0f;           // ... and its share of the frame
-    std::string kernel_id;            // rtc_ctx_kernel_id(): names the code object (source + options + compiler), not the scene
-    // the scene as last uploaded: an identical one (rtc_render_ex called again for the next frame) is not uploaded twice
+    // the records on the device, and as last uploaded: an identical scene (rtc_render_ex called again for the next frame) is not uploaded twice
+    DeviceArray<float4> d_soa;
+    DeviceArray<float> d_texels;        // UVImage canvases (RGB f32)
+    DeviceArray<float4> d_open_trav;    // Scene::stream_guard's entry list
     std::vector<float4> soa_host;
     std::vector<float> texels_host;
-    uint4* d_block_counts = nullptr;
-    size_t block_cap = 0;
-    // pinned host memory through which the feedback reads wave times back and sends lists out (grow-only: through pageable vectors
-    // the two copies of a 2048^2 frame's re-cut took longer than the frame)
-    void* h_feedback = nullptr;
-    size_t h_feedback_cap = 0;
-    // the level-by-level renderer (rtc_wavefront.h): ray lists (two levels x reflection / refraction), the node pool, counters
-    WfRay* d_wf_rays[4] = {nullptr, nullptr, nullptr, nullptr};
-    WfNode* d_wf_nodes = nullptr;
-    uint32_t* d_wf_ctr = nullptr;
-    size_t wf_cap_rays = 0, wf_cap_nodes = 0;
-    bool wf_pays = false;      // this scene: a tree world with long leaf runs whose materials both reflect and transmit
-    bool wf_disabled = false;  // ... but a frame overflowed the pools: per-pixel kernels from then on
+    Warmed render_warmed;
+    int tree_waves = 6;  // waves per SIMD the last tree scene's kernel was compiled for (a flat scene leaves it: see above)
+    // Block lists (RenderArgs::tiles) -- key: band_rows, n_parts, part, lanes per pixel (log2; ~0: a regular grid's order), depth (what
+    // a block costs depends on it) -- and scene-tile lists per partition {band_rows, n_parts, part}
+    std::map<std::array<uint32_t, 5>, BlockList> block_lists;
+    std::map<std::array<uint32_t, 3>, SceneTileList> scene_tile_lists;
+    Stream fill_stream;  // the zero-fill of a tile launch runs beside the render kernel (fork / join by events)
+    Event ev_fork, ev_join;
+    DeviceArray<uint4> d_block_counts;
+    // pinned host memory through which the feedback reads wave times back and sends lists out (through pageable vectors the two
+    // copies of a 2048^2 frame's re-cut took longer than the frame)
+    PinnedBuffer h_feedback;
+    // workspace of rtc_ctx_to_ppm
+    DeviceArray<unsigned long long> d_ppm_rows;  // per-row length, then offset; [h] is the total
+    DeviceArray<uint32_t> d_ppm_bits;
+    // the level-by-level renderer (rtc_wavefront.h): ray lists (two levels x reflection / refraction, one capacity), the node pool, counters
+    DeviceArray<WfRay> d_wf_rays[4];
+    DeviceArray<WfNode> d_wf_nodes;
+    DeviceArray<uint32_t> d_wf_ctr;
     bool wf_last = false;      // the last frame was rendered level by level (rtc_ctx_kernel_name says so)
     std::string wf_name;
-    uint32_t* d_progress = nullptr;  // RenderArgs::progress counters (rtc_render_ex), grow-only
-    size_t progress_cap = 0;         // dwords
+    DeviceArray<uint32_t> d_progress;  // RenderArgs::progress counters (rtc_render_ex)
     // {rays, shaded hits, culled shadow rays} per counter slot: slot 0 = the last rtc_ctx_render launch; rtc_render_ex
     // renders a frame in several launches (row chunks in flight while earlier ones travel) and gives each its own
-    unsigned long long* d_total = nullptr;
+    DeviceArray<unsigned long long> d_total;
     // HIP-event pairs around the render kernel, one per launch since the last rtc_ctx_stats
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    EventPairs events;
     size_t events_used = 0;
     bool rendered = false;
+    uint32_t last_rows = 0;
+    uint32_t last_share_log2 = 0;  // lanes per pixel (log2) the last launch was planned with (rtc_diag_ctx_share_log2)
+    uint64_t last_pixels = 0;
     // Ray streams (rtc_ctx_trace; rtc_trace.h).  Everything a trace needs it has of its own -- kernel, names, counters, events,
     // warm-up bookkeeping -- so that the frame schedule and what rtc_ctx_render reports never see it.
     struct Trace {
-        SceneKernel kernel;               // trace_variant's, compiled by the first trace that asks for it
-        bool compile_any_size = false, compile_never = false;  // ScenePlan's: what wants_scene_kernel takes beside the number of rays
-        std::string name, id;             // of the last trace's kernel ("" before the first trace of the current scene)
-        uint4* d_counts = nullptr;        // one partial per wave
-        size_t counts_cap = 0;
-        unsigned long long* d_total = nullptr;  // {rays, shaded hits, culled shadow rays} of the last trace
-        std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // around the trace kernels since the last rtc_ctx_stats that reported a trace
+        Warmed warmed;
+        DeviceArray<uint4> d_counts;              // one partial per wave
+        DeviceArray<unsigned long long> d_total;  // {rays, shaded hits, culled shadow rays} of the last trace
+        EventPairs events;                        // around the trace kernels since the last rtc_ctx_stats that reported a trace
         size_t events_used = 0;
         uint64_t last_n = 0;
-        bool last = false;                // the context's last launch was a trace: rtc_ctx_stats reports it
     } trace;
-    // Adaptive supersampling (rtc_ctx_render_adaptive; rtc_adaptive.h).  The base frame is the context's normal render; the mask
-    // and the refinement have everything of their own, as a trace has, so that the frame schedule and rtc_ctx_stats never see them.
-    struct Adaptive {
-        SceneKernel kernel[2];            // refine_variant's of k = 2, 4, compiled by the first call that asks for it
-        bool failed = false;              // hiprtc did not deliver one of them: the ahead-of-time kernels from then on, for both (note says why)
-        std::string note;
-        std::string name, id;             // of the last call's refinement kernel ("" before the first of the current scene)
-        uint32_t* d_list = nullptr;       // flagged pixel indices: width * height words, allocated by the first call
-        size_t list_cap = 0;
-        AdaptiveQueue* d_queue = nullptr; // the list's length and the last refinement's {rays, shaded hits, culled shadow rays}
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // before the mask kernel, between the two, after the refinement
-        bool ran = false;                 // the events have been recorded
+    // What the two refinement paths keep: the mask and the refinement have everything of their own, as a trace has, so that the
+    // frame schedule and rtc_ctx_stats never see them.
+    struct Refine {
+        DeviceArray<uint32_t> d_list;        // flagged pixel indices (the seam's: of the share, share-local)
+        DeviceArray<AdaptiveQueue> d_queue;  // the list's length and the last refinement's {rays, shaded hits, culled shadow rays}; the seam's [2]: ... and the halo pass's
+        Event ev[3];                         // before the mask kernel (the seam's: the halo pass), between the two, after the refinement
+        bool ran = false;                    // the events have been recorded
         std::map<const void*, int> wgs_per_cu;  // occupancy of a refinement kernel, asked once
+    };
+    // Adaptive supersampling (rtc_ctx_render_adaptive; rtc_adaptive.h).  The base frame is the context's normal render.
+    struct Adaptive : Refine {
+        Warmed warmed[2];  // by Scene::Adaptive::kernel
     } adaptive;
     // Adaptive supersampling of the one-call seam (rtc_render_adaptive; rtc_adaptive_seam.h): one part's halo pass, banded mask and
-    // refinement behind a base pass that is ctx_render_slot's.  Everything of its own, as above; kept between calls.
-    struct AdaptiveSeam {
-        SceneKernel kernel[3];            // seam_refine_variant's of k = 1 (the halo pass), 2, 4
-        bool failed = false;              // hiprtc did not deliver one of them: the ahead-of-time kernels from then on, for all (note says why)
-        std::string note;
-        std::string name, id;             // of the last call's refinement kernel ("" before the first of the current scene)
-        std::string halo_name, halo_id;   // ... and of its halo pass ("": the last call had no halo row)
-        uint32_t* d_list = nullptr;       // flagged pixels of the share, share-local indices
-        size_t list_cap = 0;
-        float* d_halo = nullptr;          // [halo rows][W][3]
-        size_t halo_cap = 0;
-        uint8_t* d_mask = nullptr;        // [rows][W]
-        size_t mask_cap = 0;
-        AdaptiveQueue* d_queue = nullptr; // [2]: the refinement's (with the list's length) and the halo pass's
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // before the halo pass, after the mask kernel, after the refinement
-        bool ran = false;
-        uint64_t halo_pixels = 0;         // of the last call: halo rows x W
-        std::map<const void*, int> wgs_per_cu;
+    // refinement behind a base pass that is ctx_render_slot's.
+    struct AdaptiveSeam : Refine {
+        Warmed warmed[3];
+        DeviceArray<float> d_halo;    // [halo rows][W][3]
+        DeviceArray<uint8_t> d_mask;  // [rows][W]
+        uint64_t halo_pixels = 0;     // of the last call: halo rows x W
     } adaptive_seam;
     // Ray reordering (rtc_ctx_ray_order, rtc_ctx_trace_reordered; rtc_reorder.h).  The sort's and the gather's buffers, events of
     // its own; the trace in the middle is rtc_ctx_trace's and is reported as one.
     struct Reorder {
         bool dir_major = !REORDER_ORIGIN_MAJOR;  // RTC_AMD_REORDER_DIR_MAJOR (development): the direction in the key's top bits
-        uint8_t* d_scratch = nullptr;    // sort ping-pong (16 B a ray; the colours reuse 12 of them) + gathered rays and keys (36 B a ray)
-        size_t scratch_cap = 0;          // bytes
-        uint32_t* d_table = nullptr;     // the sort's [digit][workgroup] table, then the stream box (REORDER_TABLE_WORDS, allocated once)
-        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // around keys + box, sort, gather, trace, scatter
+        DeviceArray<uint8_t> d_scratch;  // bytes: sort ping-pong (16 B a ray; the colours reuse 12 of them) + gathered rays and keys (36 B a ray)
+        DeviceArray<uint32_t> d_table;   // the sort's [digit][workgroup] table, then the stream box (REORDER_TABLE_WORDS, allocated once)
+        Event ev[6];                     // around keys + box, sort, gather, trace, scatter
         bool ran = false;                // the events have been recorded (by a reordered trace)
         uint64_t last_n = 0;
     } reorder;
-    rtc_camera camera;             // the camera of the resident scene as rtc_ctx_set_scene took it (has_scene)
-    uint32_t last_rows = 0;
-    uint32_t last_share_log2 = 0;  // lanes per pixel (log2) the last launch was planned with (rtc_diag_ctx_share_log2)
-    uint64_t last_pixels = 0;
 };
 
 // A new scene of the same frame size (an animation: the camera or an object has moved): what a tile cost in the frame before is
@@ -344,25 +362,6 @@ static void restart_block_lists(rtc_ctx* c) {
         ++it;
     }
 }
-// every block list of the context, with what its feedback holds (the caller knows that no launch is reading them)
-static void drop_scene_tile_lists(rtc_ctx* c) {
-    for (auto& tl : c->scene_tile_lists) {
-        if (tl.second.d) (void)hipFree(tl.second.d);
-        if (tl.second.d_fill) (void)hipFree(tl.second.d_fill);
-        if (tl.second.d_counts) (void)hipFree(tl.second.d_counts);
-    }
-    c->scene_tile_lists.clear();
-}
-static void drop_block_lists(rtc_ctx* c) {
-    for (auto& bl : c->block_lists) {
-        if (bl.second.d) (void)hipFree(bl.second.d);
-        if (bl.second.d_ticks) (void)hipFree(bl.second.d_ticks);
-        if (bl.second.ev0) (void)hipEventDestroy(bl.second.ev0);
-        if (bl.second.ev1) (void)hipEventDestroy(bl.second.ev1);
-    }
-    c->block_lists.clear();
-}
-
 // ============================================================================
 //  Scene-specialised kernels (hiprtc)
 //
@@ -527,21 +526,7 @@ static bool hit_planes_view(const rtc_hit_planes* p, HitPlanes* v) {
     return p->object || p->distance || p->point || p->eye || p->normal || p->reflectv || p->over_point || p->under_point || p->inside || p->n1n2 || p->light;
 }
 
-// a grow-only device buffer of at least `n` elements, *cap counting elements (nothing may be in flight that reads the old
-// one).  headroom: half as much again, for buffers that grow by steps.  The pointer is null and the capacity zero while
-// the allocation is attempted: a failed hipMalloc cannot leave a stale capacity beside a freed pointer.
-template <class T>
-static hipError_t grow(T** p, size_t* cap, size_t n, bool headroom = false) {
-    if (*p != nullptr && *cap >= n) return hipSuccess;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr, *cap = 0;
-    const size_t want = headroom ? std::max<size_t>(256 / sizeof(T), n + n / 2) : n;
-    hipError_t e = hipMalloc((void**)p, want * sizeof(T));
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-
-static KernelFamily aot_family(const rtc_ctx* c) { return aot_family(c->hdr.n_trav, c->n_objects, c->simple); }
+static KernelFamily aot_family(const rtc_ctx* c) { return aot_family(c->scene.hdr.n_trav, c->scene.hdr.n_objects, c->scene.plan.simple); }
 // f(NOBJ, SIMPLE) with the family as compile-time constants
 template <class F>
 static void dispatch_family(KernelFamily k, F&& f) {
@@ -552,7 +537,7 @@ static void dispatch_family(KernelFamily k, F&& f) {
     else if (k.nobj == 8) f(std::integral_constant<int, 8>(), std::false_type());
     else f(std::integral_constant<int, 0>(), std::false_type());
 }
-// One launch of a slot's kernel (rtc_ctx::SceneKernel): `fn`, the scene-compiled one, takes `args` as its one parameter; null: `aot`
+// One launch of a slot's kernel (SceneKernel): `fn`, the scene-compiled one, takes `args` as its one parameter; null: `aot`
 // dispatches to the ahead-of-time family.
 template <class Args, class Aot>
 static hipError_t launch_scene_kernel(hipFunction_t fn, dim3 grid, hipStream_t stream, Args& args, Aot&& aot) {
@@ -601,66 +586,23 @@ rtc_status rtc_ctx_create(int32_t device, rtc_ctx** out) {
     if (n <= 0) return fail(RTC_ERR_NO_DEVICE, "no HIP device visible; librtc_amd has no CPU fallback");
     if (device < 0 || device >= n) return fail(RTC_ERR_INVALID_ARG, "device %d out of range (have %d)", device, n);
     HIP_TRY(hipSetDevice(device));
-    rtc_ctx* c = new rtc_ctx();
+    std::unique_ptr<rtc_ctx> c(new rtc_ctx());  // (a failure below frees it, with its device current)
     c->device = device;
     c->policy = Policy::from_env();  // the one place a context looks at the environment
     if (const char* e = RTC_DEV_ENV("RTC_AMD_REORDER_DIR_MAJOR")) c->reorder.dir_major = *e && e[0] != '0';
-    HIP_TRY(hipMalloc(&c->d_total, 3 * CTX_TOTAL_SLOTS * sizeof(unsigned long long)));
+    HIP_TRY(c->d_total.grow(3 * CTX_TOTAL_SLOTS));
     HIP_TRY(hipMemset(c->d_total, 0, 3 * CTX_TOTAL_SLOTS * sizeof(unsigned long long)));
-    *out = c;
+    *out = c.release();
     return RTC_OK;
 }
 
 void rtc_ctx_destroy(rtc_ctx* c) {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->d_soa) (void)hipFree(c->d_soa);
-    if (c->d_open_trav) (void)hipFree(c->d_open_trav);
-    if (c->d_texels) (void)hipFree(c->d_texels);
-    if (c->d_block_counts) (void)hipFree(c->d_block_counts);
-    if (c->d_progress) (void)hipFree(c->d_progress);
-    for (WfRay* r : c->d_wf_rays)
-        if (r) (void)hipFree(r);
-    if (c->d_wf_nodes) (void)hipFree(c->d_wf_nodes);
-    if (c->d_wf_ctr) (void)hipFree(c->d_wf_ctr);
-    if (c->d_total) (void)hipFree(c->d_total);
-    if (c->d_ppm_rows) (void)hipFree(c->d_ppm_rows);
-    if (c->d_ppm_bits) (void)hipFree(c->d_ppm_bits);
-    drop_block_lists(c);
-    drop_scene_tile_lists(c);
-    if (c->fill_stream) (void)hipStreamDestroy(c->fill_stream);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->h_feedback) (void)hipHostFree(c->h_feedback);
-    for (auto& e : c->events) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
-    if (c->trace.d_counts) (void)hipFree(c->trace.d_counts);
-    if (c->trace.d_total) (void)hipFree(c->trace.d_total);
-    for (auto& e : c->trace.events) {
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
-    }
-    if (c->adaptive.d_list) (void)hipFree(c->adaptive.d_list);
-    if (c->adaptive.d_queue) (void)hipFree(c->adaptive.d_queue);
-    for (hipEvent_t e : c->adaptive.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->adaptive_seam.d_list) (void)hipFree(c->adaptive_seam.d_list);
-    if (c->adaptive_seam.d_halo) (void)hipFree(c->adaptive_seam.d_halo);
-    if (c->adaptive_seam.d_mask) (void)hipFree(c->adaptive_seam.d_mask);
-    if (c->adaptive_seam.d_queue) (void)hipFree(c->adaptive_seam.d_queue);
-    for (hipEvent_t e : c->adaptive_seam.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->reorder.d_scratch) (void)hipFree(c->reorder.d_scratch);
-    if (c->reorder.d_table) (void)hipFree(c->reorder.d_table);
-    for (hipEvent_t e : c->reorder.ev)
-        if (e) (void)hipEventDestroy(e);
+    (void)hipSetDevice(c->device);  // (rtc_owned.h: every release with the context's device current)
     delete c;
 }
 
 // ... and what the pairs in use measured, added up
-typedef std::vector<std::pair<hipEvent_t, hipEvent_t>> EventPairs;
 static hipError_t sum_event_ms(const EventPairs& events, size_t used, double* sum_ms) {
     for (size_t i = 0; i < used; i++) {
         float ms = 0.0f;
@@ -672,33 +614,26 @@ static hipError_t sum_event_ms(const EventPairs& events, size_t used, double* su
 }
 static hipError_t sum_event_ms(const rtc_ctx* c, double* sum_ms) { return sum_event_ms(c->events, c->events_used, sum_ms); }
 // the next HIP-event pair of the launches since the last rtc_ctx_stats (the renders' pairs, or the traces')
-static hipError_t next_event_pair(EventPairs& events, size_t& used, std::pair<hipEvent_t, hipEvent_t>** out) {
+static hipError_t next_event_pair(EventPairs& events, size_t& used, std::pair<Event, Event>** out) {
     if (used == events.size()) {
         if (events.size() >= 4096) {
             used = 0;  // nobody is reading the timings: recycle
         } else {
-            std::pair<hipEvent_t, hipEvent_t> e;
-            hipError_t err = hipEventCreate(&e.first);
-            if (err == hipSuccess) err = hipEventCreate(&e.second);
+            std::pair<Event, Event> e;
+            hipError_t err = e.first.create();
+            if (err == hipSuccess) err = e.second.create();
             if (err != hipSuccess) return err;
-            events.push_back(e);
+            events.push_back(std::move(e));
         }
     }
     *out = &events[used++];
     return hipSuccess;
 }
-static hipError_t next_event_pair(rtc_ctx* c, std::pair<hipEvent_t, hipEvent_t>** out) { return next_event_pair(c->events, c->events_used, out); }
+static hipError_t next_event_pair(rtc_ctx* c, std::pair<Event, Event>** out) { return next_event_pair(c->events, c->events_used, out); }
 static hipError_t feedback_staging(rtc_ctx* c, size_t bytes, void** p) {  // (the caller has synchronised the device: nothing is using the old one)
-    if (c->h_feedback == nullptr || c->h_feedback_cap < bytes) {
-        if (c->h_feedback) (void)hipHostFree(c->h_feedback);
-        c->h_feedback = nullptr, c->h_feedback_cap = 0;
-        const size_t want = std::max<size_t>(1u << 16, bytes + bytes / 2);
-        hipError_t e = hipHostMalloc(&c->h_feedback, want, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        c->h_feedback_cap = want;
-    }
-    *p = c->h_feedback;
-    return hipSuccess;
+    const hipError_t e = c->h_feedback.grow(bytes);
+    *p = c->h_feedback.get();
+    return e;
 }
 static int compute_units(rtc_ctx* c) {  // of the context's device (asked once: the query takes a fraction of a millisecond)
     if (c->n_cus == 0) {
@@ -720,8 +655,8 @@ static rtc_status recut_block_list(rtc_ctx* c, BlockList& bl, uint32_t rows) {
     HIP_TRY(feedback_staging(c, 4u * bl.n * sizeof(uint32_t), &staging));
     const uint32_t* ticks = (const uint32_t*)staging;
     HIP_TRY(hipMemcpy(staging, bl.d_ticks, 4u * bl.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    refine_block_list(bl.host, ticks, c->hdr.width, rows, 0.85 * 4.0 * compute_units(c) * c->tree_waves, 0.01 * P.feedback_pct, 0.01 * P.feedback_down_pct,
-                      &refined, P.feedback_max_s, &throughput_ticks, ss_max_share_log2(c->ss_k));
+    refine_block_list(bl.host, ticks, c->scene.hdr.width, rows, 0.85 * 4.0 * compute_units(c) * c->tree_waves, 0.01 * P.feedback_pct, 0.01 * P.feedback_down_pct,
+                      &refined, P.feedback_max_s, &throughput_ticks, ss_max_share_log2(c->scene.ss_k));
     if (P.jit_print) {
         size_t by_s[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};  // blocks by lanes per pixel (log2), before and after
         for (uint32_t t : bl.host.empty() ? refined : bl.host) by_s[0][tile_s(t)]++;
@@ -731,7 +666,7 @@ static rtc_status recut_block_list(rtc_ctx* c, BlockList& bl, uint32_t rows) {
                      by_s[0][3] * 32 / 1000, by_s[0][4] * 16 / 1000, by_s[1][0] * 256 / 1000, by_s[1][1] * 128 / 1000, by_s[1][2] * 64 / 1000, by_s[1][3] * 32 / 1000,
                      by_s[1][4] * 16 / 1000);
     }
-    HIP_TRY(grow(&bl.d, &bl.d_cap, refined.size(), true));  // (nothing is in flight: the synchronisation above)
+    HIP_TRY(bl.d.grow(refined.size(), true));  // (nothing is in flight: the synchronisation above)
     HIP_TRY(feedback_staging(c, refined.size() * sizeof(uint32_t), &staging));  // (the times have been used)
     std::memcpy(staging, refined.data(), refined.size() * sizeof(uint32_t));
     HIP_TRY(hipMemcpy(bl.d, staging, refined.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -793,9 +728,9 @@ static rtc_status order_grid(rtc_ctx* c, BlockList& bl, uint32_t gx, uint32_t gy
         if (P.jit_print) std::fprintf(stderr, "librtc_amd: grid of %zu blocks: modelled frame %.4g in image order, %.4g longest first\n", nt, in_order, longest_first);
         if (!pays) return RTC_OK;  // (the grid stays)
     }
-    refine_block_list(launched, ticks, c->hdr.width, rows, wave_slots, INFINITY, 0.0, &ordered);
+    refine_block_list(launched, ticks, c->scene.hdr.width, rows, wave_slots, INFINITY, 0.0, &ordered);
     if (ordered.empty() || ordered.size() > bl.n) return RTC_OK;
-    HIP_TRY(grow(&bl.d, &bl.d_cap, ordered.size(), true));  // (nothing is in flight: the synchronisation above)
+    HIP_TRY(bl.d.grow(ordered.size(), true));  // (nothing is in flight: the synchronisation above)
     std::memcpy(staging, ordered.data(), ordered.size() * sizeof(uint32_t));  // (the times have been used; ordered.size() <= nt)
     HIP_TRY(hipMemcpy(bl.d, staging, ordered.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     bl.n_listed = ordered.size();
@@ -805,22 +740,22 @@ static rtc_status order_grid(rtc_ctx* c, BlockList& bl, uint32_t gx, uint32_t gy
 
 // One launch of the scene's render kernel: the scene-compiled one, or the context's ahead-of-time family.
 static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hipStream_t stream, RenderArgs& a) {
-    if (c->ss_k != 1u) {  // a supersampled context: `a` is the fine frame's, a.out the output canvas (rtc_supersample.h)
+    if (c->scene.ss_k != 1u) {  // a supersampled context: `a` is the fine frame's, a.out the output canvas (rtc_supersample.h)
         SsRenderArgs sa;
         sa.fine = a;
-        sa.out_width = a.hdr.width / c->ss_k, sa.out_rows = a.rows / c->ss_k;
-        if (c->lens_mode) {  // ... whose rays leave from a lens (rtc_lens.h)
+        sa.out_width = a.hdr.width / c->scene.ss_k, sa.out_rows = a.rows / c->scene.ss_k;
+        if (c->scene.lens_mode) {  // ... whose rays leave from a lens (rtc_lens.h)
             LensRenderArgs la;
             la.ss = sa;
             // the scene-box early-out is argued for rays from the camera's origin (primary_ray): not for these
             la.ss.fine.hdr.has_scene_box = 0u;
-            la.aperture_radius = c->lens.aperture_radius, la.focal_distance = c->lens.focal_distance, la.seed = c->lens.seed;
+            la.aperture_radius = c->scene.lens.aperture_radius, la.focal_distance = c->scene.lens.focal_distance, la.seed = c->scene.lens.seed;
             return launch_scene_kernel(spec_fn, grid, stream, la, [&] {
                 dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
                     // (a context of the one-call seam launches the variant that stores bytes and reports its rows: rtc_lens_seam.h)
-                    if (c->seam_kernels && c->ss_k == 2u) hipLaunchKernelGGL((lens_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, la);
+                    if (c->seam_kernels && c->scene.ss_k == 2u) hipLaunchKernelGGL((lens_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, la);
                     else if (c->seam_kernels) hipLaunchKernelGGL((lens_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, la);
-                    else if (c->ss_k == 2u) hipLaunchKernelGGL((lens_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, la);
+                    else if (c->scene.ss_k == 2u) hipLaunchKernelGGL((lens_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, la);
                     else hipLaunchKernelGGL((lens_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, la);
                 });
             });
@@ -828,9 +763,9 @@ static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hi
         return launch_scene_kernel(spec_fn, grid, stream, sa, [&] {
             dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
                 // (a context of the one-call seam launches the variant that stores bytes and reports its rows: rtc_supersample.h SEAM)
-                if (c->seam_kernels && c->ss_k == 2u) hipLaunchKernelGGL((ss_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
+                if (c->seam_kernels && c->scene.ss_k == 2u) hipLaunchKernelGGL((ss_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
                 else if (c->seam_kernels) hipLaunchKernelGGL((ss_seam_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, sa);
-                else if (c->ss_k == 2u) hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
+                else if (c->scene.ss_k == 2u) hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 2>), grid, dim3(256), 0, stream, sa);
                 else hipLaunchKernelGGL((ss_render_kernel<decltype(nobj)::value, decltype(simple)::value, 4>), grid, dim3(256), 0, stream, sa);
             });
         });
@@ -844,7 +779,7 @@ static hipError_t launch_render(rtc_ctx* c, hipFunction_t spec_fn, dim3 grid, hi
 
 // A slot's kernel with a frame stack of at least `depth` levels (rtc_scene_prep.h deep_variant of the slot's own).  Always a
 // scene-compiled kernel, whatever RTC_AMD_SPECIALIZE says: the ahead-of-time kernels stop at RTC_STACK_DEPTH_BASE.
-static rtc_status deep_kernel(rtc_ctx* c, int32_t depth, rtc_ctx::SceneKernel& s, hipFunction_t* out, std::string* out_id = nullptr) {
+static rtc_status deep_kernel(rtc_ctx* c, int32_t depth, SceneKernel& s, hipFunction_t* out, std::string* out_id = nullptr) {
     auto it = s.deep.find(deep_stack_cap(depth));
     if (it == s.deep.end()) {
         KernelVariant deep;
@@ -865,7 +800,7 @@ static rtc_status deep_kernel(rtc_ctx* c, int32_t depth, rtc_ctx::SceneKernel& s
 // ahead-of-time kernel computes the same image -- several times slower on area-light scenes -- so say so: the note
 // (rtc_ctx_jit_status(), rtc_stats.flags) and one line on stderr per process and `doing` ("rendering with", "tracing with",
 // "refining with"; `named`: ... and the family's name).
-static rtc_status scene_kernel_for(rtc_ctx* c, rtc_ctx::SceneKernel& s, int32_t depth, bool want, bool lazy, bool& failed, std::string& note,
+static rtc_status scene_kernel_for(rtc_ctx* c, SceneKernel& s, int32_t depth, bool want, bool lazy, bool& failed, std::string& note,
                                    const char* doing, bool named, hipFunction_t* fn, std::string* id) {
     *fn = nullptr;
     if (depth > RTC_STACK_DEPTH_BASE) return deep_kernel(c, depth, s, fn, id);
@@ -893,19 +828,19 @@ static rtc_status scene_kernel_for(rtc_ctx* c, rtc_ctx::SceneKernel& s, int32_t 
 // (the one-call seam's variant of the supersampling kernels is a code object of its own: "aot_ss<k>_<hash>.seam"; its variant of the
 // lens kernels is a kind of its own, JitKind::LENS_SEAM, whose id says so itself: "aot_lens<k>_<hash of its own>.seam")
 static std::string ctx_aot_id(const rtc_ctx* c) {
-    return aot_kernel_id(c->render.variant.kind, c->render.variant.k) + (c->seam_kernels && c->render.variant.kind == JitKind::SS ? ".seam" : "");
+    return aot_kernel_id(c->scene.render.variant.kind, c->scene.render.variant.k) + (c->seam_kernels && c->scene.render.variant.kind == JitKind::SS ? ".seam" : "");
 }
 static rtc_status compile_render_kernel(rtc_ctx* c, bool lazy) {
-    rtc_ctx::SceneKernel& r = c->render;
+    SceneKernel& r = c->scene.render;
     hipFunction_t fn = nullptr;
     std::string id;
     const rtc_status jst = scene_kernel_for(c, r, 0, true, lazy, r.failed, r.note, "rendering with", true, &fn, &id);
-    c->kernel_name = fn ? r.variant.spec_name : r.variant.family_name;
-    c->kernel_id = fn ? id : ctx_aot_id(c);
-    c->jit_deferred = !fn && !r.failed;  // (lazy: this frame by the ahead-of-time kernel)
-    if (r.failed) c->spec_shares = false;
+    c->scene.kernel_name = fn ? r.variant.spec_name : r.variant.family_name;
+    c->scene.kernel_id = fn ? id : ctx_aot_id(c);
+    c->scene.jit_deferred = !fn && !r.failed;  // (lazy: this frame by the ahead-of-time kernel)
+    if (r.failed) c->scene.plan.spec_shares = false;
     if (jst != RTC_OK) {
-        c->has_scene = false;
+        c->scene.ready = false;
         c->soa_host.clear();
     }
     return jst;
@@ -913,19 +848,19 @@ static rtc_status compile_render_kernel(rtc_ctx* c, bool lazy) {
 
 // are these the records (and texels) that are resident on the device?
 static bool same_records(const rtc_ctx* c, const std::vector<float4>& soa, const std::vector<float>& texels) {
-    return c->has_scene && soa.size() == c->soa_host.size() && texels.size() == c->texels_host.size() &&
+    return c->scene.ready && soa.size() == c->soa_host.size() && texels.size() == c->texels_host.size() &&
            std::memcmp(soa.data(), c->soa_host.data(), soa.size() * sizeof(float4)) == 0 &&
            (texels.empty() || std::memcmp(texels.data(), c->texels_host.data(), texels.size() * sizeof(float)) == 0);
 }
 // The resident scene's kernel was left uncompiled the first time (jit_get, lazy): frames repeat, so now it pays.
 static rtc_status compile_deferred(rtc_ctx* c) {
-    c->jit_deferred = false;
+    c->scene.jit_deferred = false;
     HIP_TRY(hipDeviceSynchronize());  // (nothing of this context may be in flight while its kernel and lists change)
     RTC_TRY(compile_render_kernel(c, false));
-    if (!c->render.fn) return RTC_OK;
-    drop_block_lists(c);  // (lists of the ahead-of-time launches: the scene's kernel takes other ones)
-    drop_scene_tile_lists(c);
-    c->render.deep.clear();
+    if (!c->scene.render.fn) return RTC_OK;
+    c->block_lists.clear();  // (lists of the ahead-of-time launches: the scene's kernel takes other ones)
+    c->scene_tile_lists.clear();
+    c->scene.render.deep.clear();
     return RTC_OK;
 }
 
@@ -949,88 +884,66 @@ static rtc_status set_scene(rtc_ctx* c, const rtc_scene* scene, const rtc_camera
     const bool resident = same_records(c, soa, texels);
     // the very scene that is resident (records, camera, light; the switches are the context's for life): nothing to replace
     // (another lens on it -- a focus pull: three words of the next launch's arguments)
-    if (resident && c->ss_k == k && c->lens_mode == (lens != nullptr) && std::memcmp(&hdr, &c->hdr, sizeof(hdr)) == 0) {
-        if (lens) c->lens = *lens;
-        return c->jit_deferred ? compile_deferred(c) : RTC_OK;
+    if (resident && c->scene.ss_k == k && c->scene.lens_mode == (lens != nullptr) && std::memcmp(&hdr, &c->scene.hdr, sizeof(hdr)) == 0) {
+        if (lens) c->scene.lens = *lens;
+        return c->scene.jit_deferred ? compile_deferred(c) : RTC_OK;
     }
     // Renders are asynchronous on caller streams (torch's are non-blocking: the null-stream copies below do not order
     // against them), and a render still in flight reads the records and the counters this call replaces.  Wait for
     // everything the context has launched before touching them.  (rtc.h: one stream at a time per context.)
     HIP_TRY(hipDeviceSynchronize());
     // (block lists: below; another factor is another kernel and other lane caps -- its lists start afresh)
-    const bool same_frame = c->has_scene && c->hdr.width == hdr.width && c->hdr.height == hdr.height && c->ss_k == k && c->lens_mode == (lens != nullptr);
-    // until the new scene is fully resident the context has none: a failed allocation below must not leave a stale
-    // capacity beside a null pointer, nor a render path that believes the old scene is still there
+    const bool same_frame = c->scene.ready && c->scene.hdr.width == hdr.width && c->scene.hdr.height == hdr.height && c->scene.ss_k == k && c->scene.lens_mode == (lens != nullptr);
+    // until the new scene is fully resident the context has none (Scene::ready): nothing of the old one is left for a render path
+    // to believe in, whatever fails below
     // (only the camera has moved -- an animation's usual frame: the records and texels that are resident stay)
-    c->has_scene = false;
-    c->render.fn = nullptr;
-    c->render.note.clear();
+    c->scene = rtc_ctx::Scene();
+    rtc_ctx::Scene& s = c->scene;
     if (!resident) {
         c->soa_host.clear();
         c->texels_host.clear();
         if (!texels.empty()) {
-            HIP_TRY(grow(&c->d_texels, &c->texel_cap, texels.size()));
+            HIP_TRY(c->d_texels.grow(texels.size()));
             HIP_TRY(hipMemcpy(c->d_texels, texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
         }
-        if (!soa.empty()) HIP_TRY(grow(&c->d_soa, &c->soa_cap, soa.size()));
+        if (!soa.empty()) HIP_TRY(c->d_soa.grow(soa.size()));
         HIP_TRY(hipMemcpy(c->d_soa, soa.data(), soa.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
     // the stream kernels' guard (nothing is in flight: the synchronisation above)
-    c->stream_guard.open_trav = nullptr;
     if (hdr.internal_boxes && hdr.n_trav) {
         const std::vector<float4> open = open_flat_bvh(soa.data() + soa_index(SOA_COLUMNS, padded_count(hdr.n_objects), 0), hdr.n_trav);
-        HIP_TRY(grow(&c->d_open_trav, &c->open_trav_cap, open.size()));
+        HIP_TRY(c->d_open_trav.grow(open.size()));
         HIP_TRY(hipMemcpy(c->d_open_trav, open.data(), open.size() * sizeof(float4), hipMemcpyHostToDevice));
-        for (int a = 0; a < 3; a++) c->stream_guard.lo[a] = flat_hull.lo[a], c->stream_guard.hi[a] = flat_hull.hi[a];
-        c->stream_guard.r_min = flat_hull.r_min;
-        c->stream_guard.open_trav = c->d_open_trav;
+        for (int a = 0; a < 3; a++) s.stream_guard.lo[a] = flat_hull.lo[a], s.stream_guard.hi[a] = flat_hull.hi[a];
+        s.stream_guard.r_min = flat_hull.r_min;
+        s.stream_guard.open_trav = c->d_open_trav;
     }
-    ScenePlan plan = plan_scene(P, hdr, soa, scene, camera, heavy_boxes, region);  // which kernel will render this scene
+    s.plan = plan_scene(P, hdr, soa, scene, camera, heavy_boxes, region);  // which kernel will render this scene
     // Ray streams (rtc_ctx_trace) and the refinement of an adaptive frame: kernels of their own, none compiled yet -- the first call
     // that wants the scene's kernel compiles it
-    c->trace.kernel.reset(trace_variant(plan));
-    for (uint32_t i = 0; i < 2u; i++) c->adaptive.kernel[i].reset(refine_variant(plan, i ? 4u : 2u));
-    for (uint32_t i = 0; i < 3u; i++) c->adaptive_seam.kernel[i].reset(seam_refine_variant(plan, 1u << i));
-    if (k != 1u) plan_supersampled(&plan, k, c->seam_kernels && !lens);  // (the lens kernel's seam variant is derived from the non-seam plan)
-    if (lens) plan_lens(&plan, c->seam_kernels);
-    c->hdr = hdr;
-    c->camera = *camera;
-    c->ss_k = k;
-    c->lens_mode = lens != nullptr;
-    if (lens) c->lens = *lens;
-    c->n_objects = hdr.n_objects;
-    c->has_scene = true;
+    s.trace.kernel.variant = trace_variant(s.plan);
+    for (uint32_t i = 0; i < 2u; i++) s.adaptive.kernel[i].variant = refine_variant(s.plan, i ? 4u : 2u);
+    for (uint32_t i = 0; i < 3u; i++) s.adaptive_seam.kernel[i].variant = seam_refine_variant(s.plan, 1u << i);
+    if (k != 1u) plan_supersampled(&s.plan, k, c->seam_kernels && !lens);  // (the lens kernel's seam variant is derived from the non-seam plan)
+    if (lens) plan_lens(&s.plan, c->seam_kernels);
+    s.hdr = hdr;
+    s.camera = *camera;
+    s.ss_k = k;
+    s.lens_mode = lens != nullptr;
+    if (lens) s.lens = *lens;
+    s.ready = true;
     if (!resident) {
         c->soa_host.swap(soa);
         c->texels_host.swap(texels);
     }
     if (same_frame && P.block_feedback) restart_block_lists(c);
-    else drop_block_lists(c);  // (nothing is in flight any more: the synchronisation above)
-    drop_scene_tile_lists(c);
-    c->simple = plan.simple;
-    c->heavy_tiles.swap(plan.heavy_tiles), c->heavy_w = plan.heavy_w, c->heavy_h = plan.heavy_h;
-    c->scene_box_coverage = plan.scene_box_coverage;
-    std::memcpy(c->scene_rect, plan.scene_rect, sizeof(c->scene_rect));
-    c->scene_rect_coverage = plan.scene_rect_coverage;
-    c->scene_tile_mask.swap(plan.scene_tile_mask);
-    if (!c->scene_tile_mask.empty()) c->scene_tiles_w = plan.scene_tiles_w, c->scene_tiles_h = plan.scene_tiles_h;
-    c->scene_tiles_sparse = plan.scene_tiles_sparse;
-    c->spec_shares = plan.spec_shares, c->spec_blocks_y = plan.spec_blocks_y, c->spec_rect = plan.spec_rect;
-    if (plan.tree_waves) c->tree_waves = plan.tree_waves;
-    c->wf_pays = plan.wf_pays;
-    c->wf_disabled = false;
-    c->trace.compile_any_size = plan.compile_any_size, c->trace.compile_never = plan.compile_never;
-    c->trace.last = false;
-    c->trace.name.clear(), c->trace.id.clear();
-    c->adaptive.failed = false;
-    c->adaptive.note.clear(), c->adaptive.name.clear(), c->adaptive.id.clear();
-    c->adaptive_seam.failed = false;
-    c->adaptive_seam.note.clear(), c->adaptive_seam.name.clear(), c->adaptive_seam.id.clear(), c->adaptive_seam.halo_name.clear(), c->adaptive_seam.halo_id.clear();
-    c->render.reset(render_variant(plan));
-    c->kernel_name = plan.family_name;
-    c->kernel_id = ctx_aot_id(c);
-    c->jit_deferred = false;
-    if (plan.compile_now && !plan.spec_defs.empty()) return compile_render_kernel(c, c->lazy_jit && P.specialise == 2);
+    else c->block_lists.clear();  // (nothing is in flight any more: the synchronisation above)
+    c->scene_tile_lists.clear();
+    if (s.plan.tree_waves) c->tree_waves = s.plan.tree_waves;
+    s.render.variant = render_variant(s.plan);
+    s.kernel_name = s.plan.family_name;
+    s.kernel_id = ctx_aot_id(c);
+    if (s.plan.compile_now && !s.plan.spec_defs.empty()) return compile_render_kernel(c, c->lazy_jit && P.specialise == 2);
     return RTC_OK;
 }
 
@@ -1061,7 +974,7 @@ rtc_status rtc_ctx_set_scene_lens(rtc_ctx* c, const rtc_scene* scene, const rtc_
 // counter; 0: unknown (the level-by-level renderer's lanes draw rays from a queue), every shade point the word can count.
 // (Lights of up to 256 cells, the usual ones, fit whatever the launch is and are not looked at further.)
 static SceneHdr launch_hdr(const rtc_ctx* c, int32_t depth, uint32_t rays_per_lane) {
-    SceneHdr h = c->hdr;
+    SceneHdr h = c->scene.hdr;
     const int64_t cells = (int64_t)h.u_steps * (int64_t)h.v_steps;
     if (h.light_kind != RTC_LIGHT_RECT || depth > RTC_STACK_DEPTH_BASE || cells * (int64_t)SHADED_COUNT_MAX <= (int64_t)CULLED_COUNT_MAX) return h;
     bool any_refl = rays_per_lane == 0u, any_refr = rays_per_lane == 0u;
@@ -1080,57 +993,51 @@ static SceneHdr launch_hdr(const rtc_ctx* c, int32_t depth, uint32_t rays_per_la
 static rtc_status render_wavefront(rtc_ctx* c, int32_t depth, const Partition& q, uint32_t rows, void* d_out, bool out_u8, hipStream_t stream,
                                    uint32_t slot, bool* used) {
     *used = false;
-    const size_t pixels = (size_t)rows * c->hdr.width;
+    const size_t pixels = (size_t)rows * c->scene.hdr.width;
     // pools: a level's two ray lists hold up to two rays per pixel each, the node pool six suspended hits per pixel (a glass
     // mesh filling a quarter of the frame at depth 5 needs about one and three); a frame that needs more is rendered again
     const size_t cap_rays = std::max<size_t>(1024, 2 * pixels), cap_nodes = std::max<size_t>(1024, 6 * pixels);
     if (cap_nodes > 0x7fffffffull) return RTC_OK;
-    if (cap_rays > c->wf_cap_rays || cap_nodes > c->wf_cap_nodes || !c->d_wf_ctr) {
+    if (cap_rays > c->d_wf_rays[0].capacity() || cap_nodes > c->d_wf_nodes.capacity() || !c->d_wf_ctr) {
         HIP_TRY(hipDeviceSynchronize());  // (the pools may be in use by a frame in flight)
         auto free_pools = [c]() {
-            for (WfRay*& r : c->d_wf_rays) {
-                if (r) (void)hipFree(r);
-                r = nullptr;
-            }
-            if (c->d_wf_nodes) (void)hipFree(c->d_wf_nodes);
-            c->d_wf_nodes = nullptr;
-            c->wf_cap_rays = c->wf_cap_nodes = 0;
+            for (auto& r : c->d_wf_rays) r.release();
+            c->d_wf_nodes.release();
         };
         free_pools();
         bool ok = true;
-        for (WfRay*& r : c->d_wf_rays) ok = ok && hipMalloc((void**)&r, cap_rays * sizeof(WfRay)) == hipSuccess;
-        ok = ok && hipMalloc((void**)&c->d_wf_nodes, cap_nodes * sizeof(WfNode)) == hipSuccess;
-        if (ok && !c->d_wf_ctr) ok = hipMalloc((void**)&c->d_wf_ctr, WF_CTR_WORDS * sizeof(uint32_t)) == hipSuccess;
+        for (auto& r : c->d_wf_rays) ok = ok && r.grow(cap_rays) == hipSuccess;
+        ok = ok && c->d_wf_nodes.grow(cap_nodes) == hipSuccess;
+        if (ok && !c->d_wf_ctr) ok = c->d_wf_ctr.grow(WF_CTR_WORDS) == hipSuccess;
         if (!ok) {  // not enough memory for the pools: the per-pixel kernel needs none
             (void)hipGetLastError();
             free_pools();
             return RTC_OK;
         }
-        c->wf_cap_rays = cap_rays, c->wf_cap_nodes = cap_nodes;
     }
     WfArgs a;
     a.hdr = launch_hdr(c, depth, 0u);
-    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.soa = soa_view(c->d_soa, c->scene.hdr, c->d_texels);
     a.out = out_u8 ? nullptr : (float*)d_out;
     a.out_u8 = out_u8 ? (uint8_t*)d_out : nullptr;
     a.rows = rows, a.band_rows = q.band_rows, a.n_parts = q.n_parts, a.part = q.part;
     a.depth = depth;
     a.nodes = c->d_wf_nodes;
     a.ctr = c->d_wf_ctr;
-    a.cap_rays = (uint32_t)c->wf_cap_rays, a.cap_nodes = (uint32_t)c->wf_cap_nodes;
+    a.cap_rays = (uint32_t)c->d_wf_rays[0].capacity(), a.cap_nodes = (uint32_t)c->d_wf_nodes.capacity();
     // (levels after the first and the combining passes draw their work from counters: a launch that fills the chip once)
     const uint32_t ray_wgs = 256u * 6u, node_wgs = 256u * 4u;
-    const dim3 primary_grid((c->hdr.width + 15u) / 16u, (rows + 15u) / 16u);
+    const dim3 primary_grid((c->scene.hdr.width + 15u) / 16u, (rows + 15u) / 16u);
     const size_t n_counts = ((size_t)primary_grid.x * primary_grid.y + (size_t)depth * ray_wgs) * 4;  // one partial per wave of every tracing launch
-    if (n_counts > c->block_cap) {
+    if (n_counts > c->d_block_counts.capacity()) {
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(grow(&c->d_block_counts, &c->block_cap, n_counts));
+        HIP_TRY(c->d_block_counts.grow(n_counts));
     }
     a.wave_counts = c->d_block_counts;
     unsigned long long* total = c->d_total + 3 * (size_t)slot;
     HIP_TRY(hipMemsetAsync(c->d_wf_ctr, 0, WF_CTR_WORDS * sizeof(uint32_t), stream));
     HIP_TRY(hipMemsetAsync(total, 0, 3 * sizeof(unsigned long long), stream));
-    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    std::pair<Event, Event>* ev = nullptr;
     HIP_TRY(next_event_pair(c, &ev));
     HIP_TRY(hipEventRecord(ev->first, stream));
     for (int32_t level = 0; level <= depth; level++) {
@@ -1142,14 +1049,14 @@ static rtc_status render_wavefront(rtc_ctx* c, int32_t depth, const Partition& q
             hipLaunchKernelGGL(wf_trace_kernel<true>, primary_grid, dim3(256), 0, stream, a);
         else
             hipLaunchKernelGGL(wf_trace_kernel<false>, dim3(ray_wgs), dim3(256), 0, stream, a);
-        hipLaunchKernelGGL(wf_snapshot_kernel, dim3(1), dim3(1), 0, stream, c->d_wf_ctr, (uint32_t)level, a.cap_nodes);
+        hipLaunchKernelGGL(wf_snapshot_kernel, dim3(1), dim3(1), 0, stream, c->d_wf_ctr.get(), (uint32_t)level, a.cap_nodes);
     }
     for (int32_t level = depth; level >= 0; level--) {
         a.level = (uint32_t)level;
         hipLaunchKernelGGL(wf_combine_kernel, dim3(node_wgs), dim3(256), 0, stream, a);
     }
     HIP_TRY(hipEventRecord(ev->second, stream));
-    hipLaunchKernelGGL(sum_counts_kernel, dim3((uint32_t)((n_counts + SUM_COUNTS_SLICE - 1) / SUM_COUNTS_SLICE)), dim3(1024), 0, stream, c->d_block_counts,
+    hipLaunchKernelGGL(sum_counts_kernel, dim3((uint32_t)((n_counts + SUM_COUNTS_SLICE - 1) / SUM_COUNTS_SLICE)), dim3(1024), 0, stream, c->d_block_counts.get(),
                        (uint32_t)n_counts, total, 0ull);
     HIP_TRY(hipGetLastError());
     // did everything fit?  (One small read-back: the call returns when the frame is done -- these frames take milliseconds.)
@@ -1157,7 +1064,7 @@ static rtc_status render_wavefront(rtc_ctx* c, int32_t depth, const Partition& q
     HIP_TRY(hipMemcpyAsync(&overflow, c->d_wf_ctr + WF_CTR_OVERFLOW, sizeof(overflow), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (overflow) {
-        c->wf_disabled = true;  // this scene needs more than the pools hold: per-pixel kernels from now on
+        c->scene.wf_disabled = true;  // this scene needs more than the pools hold: per-pixel kernels from now on
         c->events_used--;
         return RTC_OK;
     }
@@ -1173,14 +1080,14 @@ struct LaunchLists {
     uint32_t* d_ticks = nullptr;        // RenderArgs::wave_ticks
     BlockList* timed_list = nullptr;    // a list whose own events bracket this launch
     void* copy_counts_to = nullptr;     // where the launch's wave counts go afterwards, on its stream
-    rtc_ctx::SceneTileList* scene_tiles = nullptr;
+    SceneTileList* scene_tiles = nullptr;
 };
 
 // (a world in which nothing reflects or transmits -- an empty world among them, which the reference renders black at any
 // depth -- never suspends a shade_hit: whatever the depth asked for, the base kernels trace it as they trace depth 8)
 static bool scene_recurses(const rtc_ctx* c) {
-    const uint32_t stride = padded_count(c->hdr.n_objects);
-    for (uint32_t i = 0; i < c->hdr.n_objects; i++) {
+    const uint32_t stride = padded_count(c->scene.hdr.n_objects);
+    for (uint32_t i = 0; i < c->scene.hdr.n_objects; i++) {
         const float4 mb = c->soa_host[soa_index(COL_MAT_B, stride, i)], mc = c->soa_host[soa_index(COL_MAT_C, stride, i)];
         if (!(mb.w == 0.0f) || !(mc.x == 0.0f)) return true;  // reflective, transparency (NaN: recurses)
     }
@@ -1191,7 +1098,7 @@ static bool scene_recurses(const rtc_ctx* c) {
 static rtc_status block_list_room(rtc_ctx* c) {
     if (c->block_lists.size() >= 256u) {
         HIP_TRY(hipDeviceSynchronize());
-        drop_block_lists(c);
+        c->block_lists.clear();
     }
     return RTC_OK;
 }
@@ -1212,35 +1119,30 @@ static rtc_status use_block_list(rtc_ctx* c, const Partition& q, uint32_t rows, 
     if (it == c->block_lists.end()) {
         RTC_TRY(block_list_room(c));
         std::vector<uint32_t> host;
-        if (mesh_list) build_block_list(P.block_order, P.block_s, P.block_s_top, TileMask{c->heavy_tiles.data(), c->heavy_w, c->heavy_h}, c->hdr.width, share_log2, rows, q, &host,
-                                        ss_max_share_log2(c->ss_k));
-        else uniform_block_list(share_log2, c->hdr.width, rows, &host);
+        if (mesh_list) build_block_list(P.block_order, P.block_s, P.block_s_top, TileMask{c->scene.plan.heavy_tiles.data(), c->scene.plan.heavy_w, c->scene.plan.heavy_h}, c->scene.hdr.width, share_log2, rows, q, &host,
+                                        ss_max_share_log2(c->scene.ss_k));
+        else uniform_block_list(share_log2, c->scene.hdr.width, rows, &host);
         BlockList bl;
         bl.n = host.size();
         if (P.block_feedback) bl.host = host;
-        HIP_TRY(grow(&bl.d, &bl.d_cap, host.size(), true));
+        HIP_TRY(bl.d.grow(host.size(), true));
         // (a new buffer: no launch in flight can be reading it; the copy is complete when the call returns)
         hipError_t ce = hipMemcpy(bl.d, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (ce != hipSuccess) {
-            (void)hipFree(bl.d);
-            return fail(RTC_ERR_DEVICE, "block list upload failed: %s", hipGetErrorString(ce));
-        }
-        it = c->block_lists.emplace(key, bl).first;
+        if (ce != hipSuccess) return fail(RTC_ERR_DEVICE, "block list upload failed: %s", hipGetErrorString(ce));
+        it = c->block_lists.emplace(key, std::move(bl)).first;
     }
     BlockList& bl = it->second;
     if (P.block_feedback && bl.state == BlockList::TIMED) RTC_TRY(recut_block_list(c, bl, rows));
     // (a refined list under scenes that change: every frame is timed -- restart_block_lists decides from them when to re-cut)
     if (P.block_feedback && (bl.state == BlockList::FRESH || (bl.state == BlockList::REFINED && bl.animated)) && bl.n != 0) {
-        HIP_TRY(grow(&bl.d_ticks, &bl.ticks_cap, 4u * bl.n, true));
+        HIP_TRY(bl.d_ticks.grow(4u * bl.n, true));
         HIP_TRY(hipMemsetAsync(bl.d_ticks, 0, 4u * bl.n * sizeof(uint32_t), stream));
         L->d_ticks = bl.d_ticks;
         if (bl.state == BlockList::FRESH) {
             bl.state = BlockList::TIMED;
         } else {
-            if (bl.ev0 == nullptr) {
-                HIP_TRY(hipEventCreate(&bl.ev0));
-                HIP_TRY(hipEventCreate(&bl.ev1));
-            }
+            HIP_TRY(bl.ev0.create());
+            HIP_TRY(bl.ev1.create());
             L->timed_list = &bl;
         }
     }
@@ -1251,9 +1153,9 @@ static rtc_status use_block_list(rtc_ctx* c, const Partition& q, uint32_t rows, 
 
 // A scene-tile list's second frame has left what its waves counted (SceneTileList::TIMED): as order_grid, for a list -- the same
 // cost of a wave, the same model of the dispatcher, the same 3 %.  The tiles stay whole and the fill runs as they are.
-static rtc_status order_scene_tiles(rtc_ctx* c, rtc_ctx::SceneTileList& tl, uint32_t rows) {
+static rtc_status order_scene_tiles(rtc_ctx* c, SceneTileList& tl, uint32_t rows) {
     HIP_TRY(hipDeviceSynchronize());  // (once per scene and partition)
-    tl.state = rtc_ctx::SceneTileList::SETTLED;
+    tl.state = SceneTileList::SETTLED;
     void* staging = nullptr;
     HIP_TRY(feedback_staging(c, 4u * tl.n * sizeof(uint4), &staging));
     HIP_TRY(hipMemcpy(staging, tl.d_counts, 4u * tl.n * sizeof(uint4), hipMemcpyDeviceToHost));
@@ -1269,7 +1171,7 @@ static rtc_status order_scene_tiles(rtc_ctx* c, rtc_ctx::SceneTileList& tl, uint
         std::fprintf(stderr, "librtc_amd: scene tiles: list of %zu: modelled frame %.4g in list order, %.4g longest first\n", tl.n, in_order, longest_first);
     if (!pays) return RTC_OK;  // (the list stays)
     std::vector<uint32_t> ordered;
-    order_tile_list(tl.host, ticks, c->hdr.width, rows, &ordered);
+    order_tile_list(tl.host, ticks, c->scene.hdr.width, rows, &ordered);
     if (ordered.size() != tl.n) return RTC_OK;
     HIP_TRY(hipMemcpy(tl.d, ordered.data(), tl.n * sizeof(uint32_t), hipMemcpyHostToDevice));  // (nothing is in flight: the synchronisation above)
     tl.host.swap(ordered);
@@ -1277,7 +1179,7 @@ static rtc_status order_scene_tiles(rtc_ctx* c, rtc_ctx::SceneTileList& tl, uint
     return RTC_OK;
 }
 
-// Scene tiles (rtc_ctx::scene_tile_mask): the canvas is zero-filled at memory speed (805 MB of an 8192^2 frame: 0.12 ms) and
+// Scene tiles (ScenePlan::scene_tile_mask): the canvas is zero-filled at memory speed (805 MB of an 8192^2 frame: 0.12 ms) and
 // only the tiles some entry of the world projects to get a workgroup -- C5: 18 k of 262 k, where the bounding rectangle of
 // them all has 60 k, and a frame of such short waves costs what starting them costs (0.78 waves per ns).  The partition's
 // list, built and uploaded on first use (an empty one: nothing of the scene in this partition's rows).
@@ -1292,47 +1194,47 @@ static rtc_status use_scene_tile_list(rtc_ctx* c, const Partition& q, uint32_t r
         // (a caller cycling through partitions without end: start over -- nothing may be in flight)
         if (c->scene_tile_lists.size() >= 256u) {
             HIP_TRY(hipDeviceSynchronize());
-            drop_scene_tile_lists(c);
+            c->scene_tile_lists.clear();
         }
         SceneTilePlan host;
-        plan_scene_tiles(TileMask{c->scene_tile_mask.data(), c->scene_tiles_w, c->scene_tiles_h}, c->hdr.width, c->hdr.height, q, &host);
+        plan_scene_tiles(TileMask{c->scene.plan.scene_tile_mask.data(), c->scene.plan.scene_tiles_w, c->scene.plan.scene_tiles_h}, c->scene.hdr.width, c->scene.hdr.height, q, &host);
         if (P.swizzle) {
             std::vector<uint32_t> permuted;
-            swizzle_tile_list(host.tiles, c->hdr.width, rows, &permuted);
+            swizzle_tile_list(host.tiles, c->scene.hdr.width, rows, &permuted);
             host.tiles.swap(permuted);
         }
         static_assert(sizeof(FillRun) == sizeof(uint2), "fill_tiles_kernel reads the runs as uint2");
-        rtc_ctx::SceneTileList tl;
+        SceneTileList tl;
         tl.n = host.tiles.size();
         tl.n_fill = host.fill.size();
         tl.traced_pixels = host.traced_pixels;
         if (tl.n) {
-            HIP_TRY(hipMalloc((void**)&tl.d, tl.n * sizeof(uint32_t)));
+            HIP_TRY(tl.d.grow(tl.n));
             HIP_TRY(hipMemcpyAsync(tl.d, host.tiles.data(), tl.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
             if (tl.n_fill) {
-                HIP_TRY(hipMalloc((void**)&tl.d_fill, tl.n_fill * sizeof(uint2)));
+                HIP_TRY(tl.d_fill.grow(tl.n_fill));
                 HIP_TRY(hipMemcpyAsync(tl.d_fill, host.fill.data(), tl.n_fill * sizeof(uint2), hipMemcpyHostToDevice, stream));
             }
             HIP_TRY(hipStreamSynchronize(stream));  // (the host vectors go out of scope)
         }
         tl.host.swap(host.tiles);
-        it = c->scene_tile_lists.emplace(key, tl).first;
+        it = c->scene_tile_lists.emplace(key, std::move(tl)).first;
     }
-    rtc_ctx::SceneTileList& tl = it->second;
+    SceneTileList& tl = it->second;
     if (tl.n && feedback) {
-        if (tl.state == rtc_ctx::SceneTileList::TIMED) RTC_TRY(order_scene_tiles(c, tl, rows));
-        if (tl.state == rtc_ctx::SceneTileList::IDLE) {
-            tl.state = rtc_ctx::SceneTileList::FRESH;
-        } else if (tl.state == rtc_ctx::SceneTileList::FRESH) {
-            if (!tl.d_counts) HIP_TRY(hipMalloc((void**)&tl.d_counts, 4u * tl.n * sizeof(uint4)));
+        if (tl.state == SceneTileList::TIMED) RTC_TRY(order_scene_tiles(c, tl, rows));
+        if (tl.state == SceneTileList::IDLE) {
+            tl.state = SceneTileList::FRESH;
+        } else if (tl.state == SceneTileList::FRESH) {
+            if (!tl.d_counts) HIP_TRY(tl.d_counts.grow(4u * tl.n));
             L->copy_counts_to = tl.d_counts;
-            tl.state = rtc_ctx::SceneTileList::TIMED;
+            tl.state = SceneTileList::TIMED;
         }
     }
     if (it->second.n && !c->fill_stream) {  // the zero-fill runs beside the render kernel (fork / join by events)
-        HIP_TRY(hipStreamCreateWithFlags(&c->fill_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+        HIP_TRY(c->fill_stream.create(hipStreamNonBlocking));
+        HIP_TRY(c->ev_fork.create(hipEventDisableTiming));
+        HIP_TRY(c->ev_join.create(hipEventDisableTiming));
     }
     L->scene_tiles = &it->second;
     return RTC_OK;
@@ -1352,7 +1254,7 @@ static rtc_status use_grid_feedback(rtc_ctx* c, const Partition& q, uint32_t row
         BlockList bl;
         bl.n = lp->n_workgroups();
         bl.state = BlockList::IDLE;
-        it = c->block_lists.emplace(key, bl).first;
+        it = c->block_lists.emplace(key, std::move(bl)).first;
     }
     BlockList& bl = it->second;
     if (bl.state == BlockList::TIMED) RTC_TRY(order_grid(c, bl, lp->grid_x, lp->grid_y, rows));
@@ -1361,7 +1263,7 @@ static rtc_status use_grid_feedback(rtc_ctx* c, const Partition& q, uint32_t row
     } else if (bl.state == BlockList::FRESH && bl.n == lp->n_workgroups()) {
         bl.counts = !timed_waves;
         bl.swizzled = lp->swizzle;
-        HIP_TRY(grow(&bl.d_ticks, &bl.ticks_cap, 4u * bl.n * (bl.counts ? sizeof(uint4) / sizeof(uint32_t) : 1u), true));
+        HIP_TRY(bl.d_ticks.grow(4u * bl.n * (bl.counts ? sizeof(uint4) / sizeof(uint32_t) : 1u), true));
         if (bl.counts) {
             L->copy_counts_to = bl.d_ticks;
         } else {
@@ -1384,22 +1286,22 @@ static rtc_status use_grid_feedback(rtc_ctx* c, const Partition& q, uint32_t row
 // (`kernel`: the slot's kernel this launch runs -- `fn`, or the ahead-of-time family's key; `launch_no_op`: one workgroup of it over the
 // caller's no-op variant of its arguments)
 template <class Launch>
-static rtc_status warm_up(rtc_ctx::SceneKernel& s, const void* kernel, hipStream_t stream, Launch&& launch_no_op) {
-    if (s.warmed.insert(std::make_pair(kernel, (const void*)stream)).second) HIP_TRY(launch_no_op());
+static rtc_status warm_up(Warmed& warmed, const void* kernel, hipStream_t stream, Launch&& launch_no_op) {
+    if (warmed.insert(std::make_pair(kernel, (const void*)stream)).second) HIP_TRY(launch_no_op());
     return RTC_OK;
 }
 
 // A scene-tile launch's zero-fill of the unlisted tiles runs beside the render kernel, on the context's fill stream: memory-bound
 // work under arithmetic.  (The caller joins: the frame's stream waits for ev_join after the render kernel.)
-static rtc_status fork_tile_fill(rtc_ctx* c, const rtc_ctx::SceneTileList& tl, void* d_out, uint32_t rows, bool out_u8, hipStream_t stream) {
+static rtc_status fork_tile_fill(rtc_ctx* c, const SceneTileList& tl, void* d_out, uint32_t rows, bool out_u8, hipStream_t stream) {
     HIP_TRY(hipEventRecord(c->ev_fork, stream));
     HIP_TRY(hipStreamWaitEvent(c->fill_stream, c->ev_fork, 0));
     // 96 workgroups share the jobs: enough to move 690 MB in the time C5's tiles take to render, few enough to leave the chip's wave
     // slots to the render kernel (C5 8192^2, whole frame: 0.84 / 0.46 / 0.33 / 0.294 / 0.30 / 0.36 / 0.38 ms with 16 / 32 / 64 / 96 /
     // 128 / 512 / 4096 of them; the bounding rectangle with its interleaved fill: 0.335; profiles/r04_c5_tile_fill.txt)
     const uint32_t fill_wgs = c->policy.tile_fill_wgs ? c->policy.tile_fill_wgs : 96u;
-    hipLaunchKernelGGL(fill_tiles_kernel, dim3((uint32_t)std::min<size_t>(tl.n_fill, fill_wgs)), dim3(256), 0, c->fill_stream, tl.d_fill,
-                       (uint32_t)tl.n_fill, (uint8_t*)d_out, c->hdr.width, rows, out_u8 ? 3u : 12u);
+    hipLaunchKernelGGL(fill_tiles_kernel, dim3((uint32_t)std::min<size_t>(tl.n_fill, fill_wgs)), dim3(256), 0, c->fill_stream.get(), tl.d_fill.get(),
+                       (uint32_t)tl.n_fill, (uint8_t*)d_out, c->scene.hdr.width, rows, out_u8 ? 3u : 12u);
     HIP_TRY(hipEventRecord(c->ev_join, c->fill_stream));
     return RTC_OK;
 }
@@ -1409,10 +1311,10 @@ static RenderArgs render_args(const rtc_ctx* c, const Partition& q, uint32_t row
                               unsigned long long* total, const ProgressPlan* progress, const LaunchPlan& lp, const LaunchLists& L) {
     RenderArgs a;
     a.hdr = launch_hdr(c, depth, lp.blocks_y);
-    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.soa = soa_view(c->d_soa, c->scene.hdr, c->d_texels);
     a.out = out_u8 ? nullptr : (float*)d_out_rgb;
     a.out_u8 = out_u8 ? (uint8_t*)d_out_rgb : nullptr;
-    a.progress = lp.n_chunks ? c->d_progress : nullptr;
+    a.progress = lp.n_chunks ? c->d_progress.get() : nullptr;
     a.done = lp.n_chunks ? progress->d_done : nullptr;
     a.chunk_block_rows = lp.chunk_block_rows;
     a.epoch = progress ? progress->epoch : 0u;
@@ -1439,8 +1341,8 @@ static RenderArgs render_args(const rtc_ctx* c, const Partition& q, uint32_t row
 // splitting leaf runs, no per-scene compile).  What the finding asks for is a single persistent launch with a queue of rays
 // and continuation frames, not level-synchronous passes.  Kept as a verified alternative, not a default.
 static bool wavefront_wanted(const rtc_ctx* c, uint32_t rows, int32_t depth) {
-    return c->hdr.n_trav != 0u && rows > 0u && depth >= 1 && depth <= RTC_STACK_DEPTH_BASE && (int)depth < (int)WF_MAX_LEVELS && !c->wf_disabled &&
-           (size_t)rows * c->hdr.width <= (16u << 20) && c->policy.wavefront == 1 && c->ss_k == 1u;
+    return c->scene.hdr.n_trav != 0u && rows > 0u && depth >= 1 && depth <= RTC_STACK_DEPTH_BASE && (int)depth < (int)WF_MAX_LEVELS && !c->scene.wf_disabled &&
+           (size_t)rows * c->scene.hdr.width <= (16u << 20) && c->policy.wavefront == 1 && c->scene.ss_k == 1u;
 }
 
 // What a partition with rows that is not run from a mesh / area-light block list is launched as: scene tiles, else the scene
@@ -1449,9 +1351,9 @@ static bool wavefront_wanted(const rtc_ctx* c, uint32_t rows, int32_t depth) {
 static rtc_status settle_shape(rtc_ctx* c, const Partition& q, uint32_t rows, int32_t depth, uint32_t share_log2, hipFunction_t spec_fn, void* d_out_rgb,
                                bool out_u8, const ProgressPlan* progress, hipStream_t stream, LaunchPlan* lp, LaunchLists* L) {
     const Policy& P = c->policy;
-    const bool list_words_fit = c->hdr.width <= 65532u && rows <= 131068u;  // (tile_word)
-    if (lp->shape == LaunchPlan::GRID && share_log2 == 0u && !c->scene_tile_mask.empty() && (q.band_rows & 15u) == 0u && list_words_fit &&
-        (progress == nullptr || c->scene_tiles_sparse)) {
+    const bool list_words_fit = c->scene.hdr.width <= 65532u && rows <= 131068u;  // (tile_word)
+    if (lp->shape == LaunchPlan::GRID && share_log2 == 0u && !c->scene.plan.scene_tile_mask.empty() && (q.band_rows & 15u) == 0u && list_words_fit &&
+        (progress == nullptr || c->scene.plan.scene_tiles_sparse)) {
         // (the feedback: as for the grid, not where rows are reported chunk by chunk -- the seam's frames pay no wait for it)
         RTC_TRY(use_scene_tile_list(c, q, rows, P.block_feedback && P.grid_feedback && progress == nullptr, stream, L));
         if (L->scene_tiles->n) {
@@ -1462,16 +1364,16 @@ static rtc_status settle_shape(rtc_ctx* c, const Partition& q, uint32_t rows, in
     // Scene rectangle: every primary ray outside the rectangle the scene's box projects to (project_heavy_boxes: exact
     // camera arithmetic in double, 8 pixels of padding, "everything" if the box reaches behind the camera) sees nothing --
     // black, one ray.  Where that rectangle is under half the frame: plan_rect_launch.  RTC_AMD_SCENE_RECT=0: the whole grid.
-    if (lp->shape == LaunchPlan::GRID && share_log2 == 0u && c->scene_rect[0] < c->scene_rect[1] && c->scene_rect_coverage < P.scene_rect_threshold() &&
-        (spec_fn == nullptr || c->spec_rect)) {
-        plan_rect_launch(lp, c->hdr.width, c->hdr.height, q, rows, c->last_pixels, c->scene_rect, P.blocks_y == 0 ? 1u : lp->blocks_y, out_u8, P.fill_wgs);
+    if (lp->shape == LaunchPlan::GRID && share_log2 == 0u && c->scene.plan.scene_rect[0] < c->scene.plan.scene_rect[1] && c->scene.plan.scene_rect_coverage < P.scene_rect_threshold() &&
+        (spec_fn == nullptr || c->scene.plan.spec_rect)) {
+        plan_rect_launch(lp, c->scene.hdr.width, c->scene.hdr.height, q, rows, c->last_pixels, c->scene.plan.scene_rect, P.blocks_y == 0 ? 1u : lp->blocks_y, out_u8, P.fill_wgs);
         // a frame of bytes: the zeros outside the rectangle are one asynchronous memset in front of the launch
-        if (out_u8) HIP_TRY(hipMemsetAsync(d_out_rgb, 0, (size_t)rows * c->hdr.width * 3u, stream));
+        if (out_u8) HIP_TRY(hipMemsetAsync(d_out_rgb, 0, (size_t)rows * c->scene.hdr.width * 3u, stream));
     }
     if (P.swizzle && lp->plain_grid()) lp->pad_for_swizzle();
     if (lp->plain_grid() && P.block_feedback && P.grid_feedback && progress == nullptr && share_log2 == 0u && list_words_fit &&
-        !(c->hdr.n_trav != 0u && P.wavefront))
-        RTC_TRY(use_grid_feedback(c, q, rows, depth, spec_fn && c->spec_shares, stream, lp, L));
+        !(c->scene.hdr.n_trav != 0u && P.wavefront))
+        RTC_TRY(use_grid_feedback(c, q, rows, depth, spec_fn && c->scene.plan.spec_shares, stream, lp, L));
     // progress reporting: a regular grid only (one workgroup per block, every block of the partition launched)
     if (progress && progress->d_done && lp->plain_grid()) plan_chunks(lp, progress->want_chunks, PROGRESS_MAX_CHUNKS);
     return RTC_OK;
@@ -1484,10 +1386,10 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     if (progress) progress->n_chunks = 0u, progress->chunk_rows = 0u;
     if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: null argument");
     if (slot >= CTX_TOTAL_SLOTS) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: counter slot %u", slot);
-    if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: no scene/camera set");
+    if (!c->scene.ready || c->scene.hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: no scene/camera set");
     // A supersampled context: the caller's partition counts OUTPUT rows -- bands of band_rows output rows are k * band_rows fine
-    // rows -- and from here on everything is the fine frame's: c->hdr, `rows`, the launch's shape, its lists and their feedback.
-    const uint32_t ss_k = c->ss_k;
+    // rows -- and from here on everything is the fine frame's: c->scene.hdr, `rows`, the launch's shape, its lists and their feedback.
+    const uint32_t ss_k = c->scene.ss_k;
     rtc_partition fine_part;
     if (ss_k != 1u) {
         // progress words and the u8 canvas (rtc_render_ss): the plain grid reports, a block-list launch is finished when its stream
@@ -1499,7 +1401,7 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
         fine_part.band_rows = o.band_rows * ss_k, fine_part.n_parts = o.n_parts, fine_part.part = o.part;
         part = &fine_part;
     }
-    const uint32_t rows = partition_rows(c->hdr.height, part);
+    const uint32_t rows = partition_rows(c->scene.hdr.height, part);
     // a partition that owns no band (height < band_rows * n_parts) has nothing to write and may pass a null buffer
     if (!d_out_rgb && rows != 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render: null output buffer");
     if (depth < 0 || depth > RTC_MAX_DEPTH)
@@ -1509,26 +1411,26 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     const Policy& P = c->policy;
-    const uint32_t width = c->hdr.width, height = c->hdr.height;
+    const uint32_t width = c->scene.hdr.width, height = c->scene.hdr.height;
     // ---- depth and kernel
     // camera.rs:76 takes any depth; the kernels' frame stack (one suspended shade_hit per level, world.rs:62-86) holds
     // RTC_STACK_DEPTH_BASE levels.  Deeper than that, the scene's kernel is compiled once more with a longer stack -- 16, 32,
     // ... RTC_MAX_DEPTH levels of per-lane scratch -- on first use, and kept with the context.
-    hipFunction_t spec_fn = c->render.fn;
+    hipFunction_t spec_fn = c->scene.render.fn;
     if (depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) depth = RTC_STACK_DEPTH_BASE;
-    if (depth > RTC_STACK_DEPTH_BASE && rows > 0u) RTC_TRY(deep_kernel(c, depth, c->render, &spec_fn));
-    const bool shares = spec_fn && c->spec_shares;  // only kernels compiled for it share lanes
+    if (depth > RTC_STACK_DEPTH_BASE && rows > 0u) RTC_TRY(deep_kernel(c, depth, c->scene.render, &spec_fn));
+    const bool shares = spec_fn && c->scene.plan.spec_shares;  // only kernels compiled for it share lanes
     // (supersampled: capped so that a k x k group lies in one wave's tile, rtc_launch_plan.h)
-    const uint32_t share_log2 = shares ? std::min(choose_share_log2(c->hdr, rows, P, progress == nullptr), ss_max_share_log2(ss_k)) : 0u;
+    const uint32_t share_log2 = shares ? std::min(choose_share_log2(c->scene.hdr, rows, P, progress == nullptr), ss_max_share_log2(ss_k)) : 0u;
     // ---- the launch's shape, and the cached list that goes with it
-    LaunchPlan lp = plan_grid(width, rows, share_log2, spec_fn && c->spec_blocks_y && ss_k == 1u, (uint32_t)P.blocks_y);
+    LaunchPlan lp = plan_grid(width, rows, share_log2, spec_fn && c->scene.plan.spec_blocks_y && ss_k == 1u, (uint32_t)P.blocks_y);
     LaunchLists L;
     // (block lists: not when RTC_AMD_SHARE_LOG2 pins one value for all; an area light's not for rtc_render_ex, whose rows leave in order)
-    const bool mesh_list = shares && !c->heavy_tiles.empty() && c->hdr.light_kind == RTC_LIGHT_POINT;
-    const bool area_list = shares && c->hdr.light_kind == RTC_LIGHT_RECT && share_log2 != 0u && P.block_feedback && progress == nullptr;
+    const bool mesh_list = shares && !c->scene.plan.heavy_tiles.empty() && c->scene.hdr.light_kind == RTC_LIGHT_POINT;
+    const bool area_list = shares && c->scene.hdr.light_kind == RTC_LIGHT_RECT && share_log2 != 0u && P.block_feedback && progress == nullptr;
     const bool list_words_fit = width <= 65532u && rows <= 131068u;  // (tile_word)
     if ((mesh_list || area_list) && P.share_log2 < 0 && list_words_fit && rows > 0u) RTC_TRY(use_block_list(c, q, rows, depth, share_log2, mesh_list, stream, &lp, &L));
-    c->trace.last = false;       // (rtc_ctx_stats reports renders again)
+    c->scene.trace.last = false;  // (rtc_ctx_stats reports renders again)
     c->last_rows = rows / ss_k;  // (rows written to the caller's buffer)
     c->last_share_log2 = share_log2;
     c->last_pixels = traced_pixels(width, height, q);
@@ -1547,10 +1449,10 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     RTC_TRY(settle_shape(c, q, rows, depth, share_log2, spec_fn, d_out_rgb, out_u8, progress, stream, &lp, &L));
     // ---- workspaces (grow-only: first call / larger image only)
     const size_t n_blocks = lp.n_workgroups() * 4;  // partial counts: one per wave
-    HIP_TRY(grow(&c->d_block_counts, &c->block_cap, n_blocks));
+    HIP_TRY(c->d_block_counts.grow(n_blocks));
     if (lp.n_chunks) {
         const size_t words = lp.progress_words(PROGRESS_STRIDE);
-        HIP_TRY(grow(&c->d_progress, &c->progress_cap, words));
+        HIP_TRY(c->d_progress.grow(words));
         HIP_TRY(hipMemsetAsync(c->d_progress, 0, words * sizeof(uint32_t), stream));
         // (the counters are the FINE grid's, one per block row of lp.grid_y; the caller's rows are output rows)
         uint32_t chunk_rows = 0u;
@@ -1561,9 +1463,9 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     }
     RenderArgs a = render_args(c, q, rows, depth, share_log2, d_out_rgb, out_u8, total, progress, lp, L);
     // ---- warm up, time, launch, sum
-    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    std::pair<Event, Event>* ev = nullptr;
     HIP_TRY(next_event_pair(c, &ev));
-    RTC_TRY(warm_up(c->render, spec_fn ? (const void*)spec_fn : aot_family(c).key(ss_k, ss_k != 1u && c->seam_kernels, c->lens_mode), stream, [&] {
+    RTC_TRY(warm_up(c->render_warmed, spec_fn ? (const void*)spec_fn : aot_family(c).key(ss_k, ss_k != 1u && c->seam_kernels, c->scene.lens_mode), stream, [&] {
         RenderArgs w = a;
         w.rows = 0u, w.tiles = nullptr, w.wave_ticks = nullptr, w.progress = nullptr, w.done = nullptr, w.fill_wg_rows = 0u, w.swizzle = 0u, w.blocks_y = 1u;
         return launch_render(c, spec_fn, dim3(1, 1), stream, w);
@@ -1581,7 +1483,7 @@ rtc_status rtc::ctx_render_slot(rtc_ctx* c, int32_t depth, const rtc_partition* 
     }
     if (L.copy_counts_to) HIP_TRY(hipMemcpyAsync(L.copy_counts_to, c->d_block_counts, n_blocks * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
     hipLaunchKernelGGL(sum_counts_kernel, dim3((uint32_t)((n_blocks + SUM_COUNTS_SLICE - 1) / SUM_COUNTS_SLICE)), dim3(1024), 0, stream,
-                       c->d_block_counts, (uint32_t)n_blocks, total, lp.extra_rays);
+                       c->d_block_counts.get(), (uint32_t)n_blocks, total, lp.extra_rays);
     HIP_TRY(hipGetLastError());
     c->rendered = true;
     return RTC_OK;
@@ -1608,7 +1510,7 @@ rtc_status rtc::ctx_collect(rtc_ctx* c, uint32_t n_slots, rtc_stats* out) {
     HIP_TRY(sum_event_ms(c, &sum_ms));
     out->kernel_ms = (float)sum_ms;
     out->launches = (uint32_t)c->events_used;
-    out->flags = c->render.note.empty() ? 0u : RTC_STATS_JIT_FALLBACK;
+    out->flags = c->scene.render.note.empty() ? 0u : RTC_STATS_JIT_FALLBACK;
     c->events_used = 0;
     return RTC_OK;
 }
@@ -1691,9 +1593,9 @@ void rtc_diag_ctx_scene_tiles(rtc_ctx* c, const rtc_partition* part, uint32_t ou
     const Partition q = resolve(part);
     auto it = c->scene_tile_lists.find({q.band_rows, q.n_parts, q.part});
     if (it == c->scene_tile_lists.end()) return;
-    const rtc_ctx::SceneTileList& tl = it->second;
+    const SceneTileList& tl = it->second;
     out[0] = (uint32_t)tl.n, out[1] = (uint32_t)tl.n_fill;
-    out[2] = tl.state <= rtc_ctx::SceneTileList::FRESH ? 0u : tl.state == rtc_ctx::SceneTileList::TIMED ? 1u : tl.ordered ? 3u : 2u;
+    out[2] = tl.state <= SceneTileList::FRESH ? 0u : tl.state == SceneTileList::TIMED ? 1u : tl.ordered ? 3u : 2u;
 }
 // A scene-rectangle launch of a partition: out = {grid_x, grid_y, blocks_y, block_x0, block_y0, fill_wg_rows, fill_rows, fill_period,
 // fill_rect[4]}; -> extra_rays.
@@ -1864,19 +1766,19 @@ rtc_status rtc_ctx_render_hits(rtc_ctx* c, const rtc_partition* part, const rtc_
     if (!c || !d_out) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: null argument");
     HitPlanes planes;
     if (!hit_planes_view(d_out, &planes)) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: no plane requested");
-    if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: no scene/camera set");
-    if (c->lens_mode) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_hits: the context renders through a lens (%u x %u rays per pixel): a first hit per output pixel is not defined", c->ss_k, c->ss_k);
-    if (c->ss_k != 1u) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_hits: the context is supersampled (%u x %u rays per pixel): a first hit per output pixel is not defined", c->ss_k, c->ss_k);
+    if (!c->scene.ready || c->scene.hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_hits: no scene/camera set");
+    if (c->scene.lens_mode) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_hits: the context renders through a lens (%u x %u rays per pixel): a first hit per output pixel is not defined", c->scene.ss_k, c->scene.ss_k);
+    if (c->scene.ss_k != 1u) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_hits: the context is supersampled (%u x %u rays per pixel): a first hit per output pixel is not defined", c->scene.ss_k, c->scene.ss_k);
     const Partition q = resolve(part);
     if (q.part >= q.n_parts) return fail(RTC_ERR_INVALID_ARG, "partition %u of %u", q.part, q.n_parts);
     // (rtc_ctx_set_scene refuses RTC_JITTER_SEQUENCE lights: no resident scene has one)
-    const uint32_t rows = partition_rows(c->hdr.height, part);
+    const uint32_t rows = partition_rows(c->scene.hdr.height, part);
     if (rows == 0) return RTC_OK;  // a partition that owns no band has nothing to write
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     HitsArgs a;
-    a.hdr = c->hdr;
-    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.hdr = c->scene.hdr;
+    a.soa = soa_view(c->d_soa, c->scene.hdr, c->d_texels);
     a.planes = planes;
     a.rows = rows;
     a.band_rows = q.band_rows, a.n_parts = q.n_parts, a.part = q.part;
@@ -1889,10 +1791,10 @@ rtc_status rtc_ctx_render_hits(rtc_ctx* c, const rtc_partition* part, const rtc_
     // 32 x 2 one where most of the frame is sky (the share below which the render puts several blocks into a workgroup).
     // With the light plane always the compact tile: intensity_at's wave votes (block cones, culls) decide more when a wave's
     // pixels are close together.  RTC_AMD_HITS_TILE (development) pins one.
-    a.tile_w_log2 = (!light && c->scene_box_coverage < 0.25f) ? 5u : 3u;
+    a.tile_w_log2 = (!light && c->scene.plan.scene_box_coverage < 0.25f) ? 5u : 3u;
     if (c->policy.hits_tile == 3 || c->policy.hits_tile == 5 || c->policy.hits_tile == 6) a.tile_w_log2 = (uint32_t)c->policy.hits_tile;
     const uint32_t bw = a.tile_w_log2 == 3u ? 16u : 1u << a.tile_w_log2, bh = 256u / bw;
-    const dim3 grid((c->hdr.width + bw - 1) / bw, (rows + bh - 1) / bh), block(256);
+    const dim3 grid((c->scene.hdr.width + bw - 1) / bw, (rows + bh - 1) / bh), block(256);
     // the families rtc_ctx_render's ahead-of-time branch chooses from (SIMPLE is a property of intensity_at alone: the
     // geometry-only kernels exist once per object-loop family)
     dispatch_family(aot_family(c), [&](auto nobj, auto simple) {
@@ -1925,7 +1827,7 @@ static rtc_status trace_args_ok(const char* who, const rtc_ctx* c, int32_t depth
     if (((uintptr_t)d_keys & 3u) || ((uintptr_t)d_out_rgb & 3u)) return fail(RTC_ERR_INVALID_ARG, "%s: keys and output must be 4-byte aligned", who);
     if (depth < 0 || depth > RTC_MAX_DEPTH) return fail(RTC_ERR_INVALID_ARG, "%s: depth %d outside [0, %d]", who, depth, RTC_MAX_DEPTH);
     if (!c) return fail(RTC_ERR_INVALID_ARG, "%s: ctx is NULL", who);
-    if (!c->has_scene) return fail(RTC_ERR_INVALID_ARG, "%s: no scene set", who);
+    if (!c->scene.ready) return fail(RTC_ERR_INVALID_ARG, "%s: no scene set", who);
     return RTC_OK;
 }
 
@@ -1935,24 +1837,25 @@ static rtc_status trace_launch(rtc_ctx* c, int32_t depth, const void* d_origins,
                                void* d_out_rgb, hipStream_t stream) {
     // (rtc_ctx_set_scene refuses RTC_JITTER_SEQUENCE lights: no resident scene has one)
     rtc_ctx::Trace& t = c->trace;
+    rtc_ctx::Scene::Trace& st = c->scene.trace;
     const Policy& P = c->policy;
     if (depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) depth = RTC_STACK_DEPTH_BASE;  // (as rtc_ctx_render)
     // (rtc_ctx_set_scene's policy with the number of rays in the place of the frame's pixels)
-    const bool want = !t.kernel.variant.defs.empty() && wants_scene_kernel(P, n, t.compile_any_size, t.compile_never);
+    const bool want = !st.kernel.variant.defs.empty() && wants_scene_kernel(P, n, c->scene.plan.compile_any_size, c->scene.plan.compile_never);
     hipFunction_t fn = nullptr;
     std::string id;
-    RTC_TRY(scene_kernel_for(c, t.kernel, depth, want, false, t.kernel.failed, t.kernel.note, "tracing with", true, &fn, &id));
-    t.name = fn ? t.kernel.variant.spec_name : t.kernel.variant.family_name;
-    t.id = fn ? id : aot_kernel_id(JitKind::TRACE);
+    RTC_TRY(scene_kernel_for(c, st.kernel, depth, want, false, st.kernel.failed, st.kernel.note, "tracing with", true, &fn, &id));
+    st.name = fn ? st.kernel.variant.spec_name : st.kernel.variant.family_name;
+    st.id = fn ? id : aot_kernel_id(JitKind::TRACE);
     // workspaces (grow-only; a trace in flight on this stream may still be writing the old partials: grow frees, which waits)
     const uint32_t n_workgroups = (uint32_t)(((uint64_t)n + 255u) / 256u);
     const size_t n_counts = (size_t)n_workgroups * 4u;
-    HIP_TRY(grow(&t.d_counts, &t.counts_cap, n_counts));
-    if (!t.d_total) HIP_TRY(hipMalloc((void**)&t.d_total, 3 * sizeof(unsigned long long)));
+    HIP_TRY(t.d_counts.grow(n_counts));
+    if (!t.d_total) HIP_TRY(t.d_total.grow(3));
     TraceArgs a;
     a.hdr = launch_hdr(c, depth, 1u);
-    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
-    a.guard = c->stream_guard;
+    a.soa = soa_view(c->d_soa, c->scene.hdr, c->d_texels);
+    a.guard = c->scene.stream_guard;
     a.origins = (const float4*)d_origins, a.directions = (const float4*)d_directions, a.keys = (const uint32_t*)d_keys;
     a.out = (float*)d_out_rgb;
     a.wave_counts = t.d_counts;
@@ -1960,21 +1863,21 @@ static rtc_status trace_launch(rtc_ctx* c, int32_t depth, const void* d_origins,
     a.n = n;
     a.depth = depth;
     // warm up (warm_up: a code object's first launch on a queue, in front of the events), time, launch, sum
-    RTC_TRY(warm_up(t.kernel, fn ? (const void*)fn : aot_family(c).key(), stream, [&] {
+    RTC_TRY(warm_up(t.warmed, fn ? (const void*)fn : aot_family(c).key(), stream, [&] {
         TraceArgs w = a;
         w.n = 0u;
         return launch_trace(c, fn, 1u, stream, w);
     }));
-    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    std::pair<Event, Event>* ev = nullptr;
     HIP_TRY(next_event_pair(t.events, t.events_used, &ev));
     HIP_TRY(hipEventRecord(ev->first, stream));
     HIP_TRY(launch_trace(c, fn, n_workgroups, stream, a));
     HIP_TRY(hipEventRecord(ev->second, stream));
-    hipLaunchKernelGGL(sum_counts_kernel, dim3((uint32_t)((n_counts + SUM_COUNTS_SLICE - 1) / SUM_COUNTS_SLICE)), dim3(1024), 0, stream, t.d_counts,
-                       (uint32_t)n_counts, t.d_total, 0ull);
+    hipLaunchKernelGGL(sum_counts_kernel, dim3((uint32_t)((n_counts + SUM_COUNTS_SLICE - 1) / SUM_COUNTS_SLICE)), dim3(1024), 0, stream, t.d_counts.get(),
+                       (uint32_t)n_counts, t.d_total.get(), 0ull);
     HIP_TRY(hipGetLastError());
     t.last_n = n;
-    t.last = true;
+    st.last = true;
     return RTC_OK;
 }
 
@@ -1998,8 +1901,8 @@ static ReorderBuffers reorder_buffers(uint8_t* base, uint32_t n) {
 // The scratch block (grow-only; a call in flight on this stream may still be using the old one: grow frees, which waits) and the table.
 static rtc_status reorder_room(rtc_ctx* c, uint32_t n, bool gathered) {
     rtc_ctx::Reorder& r = c->reorder;
-    if (!r.d_table) HIP_TRY(hipMalloc((void**)&r.d_table, REORDER_TABLE_WORDS * sizeof(uint32_t)));
-    const hipError_t e = grow(&r.d_scratch, &r.scratch_cap, (size_t)n * (REORDER_SORT_BYTES + (gathered ? REORDER_GATHER_BYTES : 0u)));
+    if (!r.d_table) HIP_TRY(r.d_table.grow(REORDER_TABLE_WORDS));
+    const hipError_t e = r.d_scratch.grow((size_t)n * (REORDER_SORT_BYTES + (gathered ? REORDER_GATHER_BYTES : 0u)));
     if (e != hipSuccess) {
         (void)hipGetLastError();  // (the context stays usable: the next call allocates again)
         return fail(RTC_ERR_DEVICE, "ray reordering: %zu bytes of scratch for %u rays: %s", (size_t)n * (REORDER_SORT_BYTES + REORDER_GATHER_BYTES), n,
@@ -2027,10 +1930,10 @@ static rtc_status reorder_sort(rtc_ctx* c, const void* d_origins, const void* d_
         const bool to_b = (pass & 1u) == 0u;
         uint32_t* const keys_out = to_b ? b.keys_b : b.keys_a;
         uint32_t* const idx_out = pass + 1u == REORDER_PASSES ? d_order : to_b ? b.idx_b : b.idx_a;
-        hipLaunchKernelGGL(reorder_count_kernel, dim3(plan.grid), dim3(256), 0, stream, keys_in, n, plan.segment, 8u * pass, r.d_table);
-        hipLaunchKernelGGL(reorder_scan_kernel, dim3(1), dim3(1024), 0, stream, r.d_table, REORDER_DIGITS * plan.grid);
+        hipLaunchKernelGGL(reorder_count_kernel, dim3(plan.grid), dim3(256), 0, stream, keys_in, n, plan.segment, 8u * pass, r.d_table.get());
+        hipLaunchKernelGGL(reorder_scan_kernel, dim3(1), dim3(1024), 0, stream, r.d_table.get(), REORDER_DIGITS * plan.grid);
         hipLaunchKernelGGL(reorder_scatter_kernel, dim3(plan.grid), dim3(256), 0, stream, keys_in, idx_in, n, plan.segment, 8u * pass,
-                           (const uint32_t*)r.d_table, keys_out, idx_out);
+                           (const uint32_t*)r.d_table.get(), keys_out, idx_out);
         keys_in = keys_out, idx_in = idx_out;
     }
     HIP_TRY(hipGetLastError());
@@ -2069,8 +1972,7 @@ rtc_status rtc_ctx_trace_reordered(rtc_ctx* c, int32_t depth, const void* d_orig
     HIP_TRY(hipSetDevice(c->device));
     rtc_ctx::Reorder& r = c->reorder;
     RTC_TRY(reorder_room(c, n, true));
-    for (hipEvent_t& e : r.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    for (Event& e : r.ev) HIP_TRY(e.create());
     const ReorderBuffers b = reorder_buffers(r.d_scratch, n);
     const dim3 grid((uint32_t)(((uint64_t)n + 255u) / 256u)), block(256);
     HIP_TRY(hipEventRecord(r.ev[0], stream));
@@ -2185,14 +2087,14 @@ rtc_status rtc_ctx_trace_hits(rtc_ctx* c, const void* d_origins, const void* d_d
         if ((uintptr_t)p & 3u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: keys and the scalar planes must be 4-byte aligned");
     if (n == 0u) return RTC_OK;  // nothing to trace, whatever the context
     if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: ctx is NULL");
-    if (!c->has_scene) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: no scene set");
+    if (!c->scene.ready) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_trace_hits: no scene set");
     // (rtc_ctx_set_scene refuses RTC_JITTER_SEQUENCE lights: no resident scene has one)
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     TraceHitsArgs a;
-    a.hdr = c->hdr;
-    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
-    a.guard = c->stream_guard;
+    a.hdr = c->scene.hdr;
+    a.soa = soa_view(c->d_soa, c->scene.hdr, c->d_texels);
+    a.guard = c->scene.stream_guard;
     a.origins = (const float4*)d_origins, a.directions = (const float4*)d_directions, a.keys = (const uint32_t*)d_keys;
     a.planes = planes;
     a.n = n;
@@ -2216,13 +2118,13 @@ rtc_status rtc_ctx_is_shadowed(rtc_ctx* c, const void* d_light_positions, const 
     if ((uintptr_t)d_out_i32 & 3u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: output must be 4-byte aligned");
     if (n == 0u) return RTC_OK;  // nothing to answer, whatever the context
     if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: ctx is NULL");
-    if (!c->has_scene) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: no scene set");
+    if (!c->scene.ready) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_is_shadowed: no scene set");
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     ShadowedArgs a;
-    a.hdr = c->hdr;
-    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
-    a.guard = c->stream_guard;
+    a.hdr = c->scene.hdr;
+    a.soa = soa_view(c->d_soa, c->scene.hdr, c->d_texels);
+    a.guard = c->scene.stream_guard;
     a.light_positions = (const float4*)d_light_positions, a.points = (const float4*)d_points;
     a.out = (int32_t*)d_out_i32;
     a.n = n;
@@ -2234,8 +2136,8 @@ rtc_status rtc_ctx_is_shadowed(rtc_ctx* c, const void* d_light_positions, const 
     return RTC_OK;
 }
 
-const char* rtc_ctx_trace_kernel_name(rtc_ctx* c) { return c ? c->trace.name.c_str() : ""; }
-const char* rtc_ctx_trace_kernel_id(rtc_ctx* c) { return c ? c->trace.id.c_str() : ""; }
+const char* rtc_ctx_trace_kernel_name(rtc_ctx* c) { return c ? c->scene.trace.name.c_str() : ""; }
+const char* rtc_ctx_trace_kernel_id(rtc_ctx* c) { return c ? c->scene.trace.id.c_str() : ""; }
 
 }  // extern "C"
 
@@ -2249,23 +2151,27 @@ static void dispatch_adaptive(rtc_ctx* c, uint32_t k, F&& f) {
         else f(adaptive_refine_kernel<decltype(nobj)::value, decltype(simple)::value, 2>);
     });
 }
-static hipError_t launch_adaptive(rtc_ctx* c, hipFunction_t fn, uint32_t k, uint32_t n_workgroups, hipStream_t stream, AdaptiveRefineArgs& a) {
+// One launch of a refinement kernel, of either path: `fn`, or the ahead-of-time one `aot` names -- aot(f) calls f(that kernel), as
+// [&](auto&& f) { dispatch_adaptive(c, k, f); } does
+template <class Args, class Aot>
+static hipError_t launch_refine(hipFunction_t fn, uint32_t n_workgroups, hipStream_t stream, Args& a, Aot&& aot) {
     return launch_scene_kernel(fn, dim3(n_workgroups), stream, a, [&] {
-        dispatch_adaptive(c, k, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_workgroups), dim3(256), 0, stream, a); });
+        aot([&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_workgroups), dim3(256), 0, stream, a); });
     });
 }
-// workgroups of the refinement kernel a compute unit holds at once (asked once per kernel; 0 from the runtime: one)
-static int adaptive_wgs_per_cu(rtc_ctx* c, hipFunction_t fn, uint32_t k, const void* key) {
-    auto it = c->adaptive.wgs_per_cu.find(key);
-    if (it != c->adaptive.wgs_per_cu.end()) return it->second;
+// workgroups of the refinement kernel a compute unit holds at once (asked once per kernel, `known` by `key`; 0 from the runtime: one)
+template <class Aot>
+static int wgs_per_cu(std::map<const void*, int>& known, hipFunction_t fn, const void* key, Aot&& aot) {
+    auto it = known.find(key);
+    if (it != known.end()) return it->second;
     int n = 0;
     hipError_t e = hipSuccess;
     if (fn) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, 0);
-    else dispatch_adaptive(c, k, [&](auto kernel) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0); });
+    else aot([&](auto kernel) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0); });
     if (e != hipSuccess) (void)hipGetLastError();
     if (e != hipSuccess || n < 1) n = 1;
     if (n > 8) n = 8;  // (a compute unit holds 32 waves)
-    c->adaptive.wgs_per_cu[key] = n;
+    known[key] = n;
     return n;
 }
 
@@ -2282,37 +2188,39 @@ rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float 
     if ((uintptr_t)d_out_rgb & 3u) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: the output must be 4-byte aligned");
     if (depth < 0 || depth > RTC_MAX_DEPTH) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: depth %d outside [0, %d]", depth, RTC_MAX_DEPTH);
     if (!c) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: ctx is NULL");
-    if (!c->has_scene || c->hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: no scene/camera set");
-    if (c->lens_mode) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_adaptive: a lens context renders every pixel with k x k lens rays already (adaptive lens frames are not defined)");
-    if (c->ss_k != 1u) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_adaptive: a supersampled context renders every pixel with k x k rays already");
+    if (!c->scene.ready || c->scene.hdr.width == 0) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_render_adaptive: no scene/camera set");
+    if (c->scene.lens_mode) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_adaptive: a lens context renders every pixel with k x k lens rays already (adaptive lens frames are not defined)");
+    if (c->scene.ss_k != 1u) return fail(RTC_ERR_UNSUPPORTED, "rtc_ctx_render_adaptive: a supersampled context renders every pixel with k x k rays already");
     rtc_camera fine;
-    RTC_TRY(rtc_camera_supersampled(&c->camera, k, &fine));  // (the fine frame's limits: 2^32 pixels, 2^17 rows)
+    RTC_TRY(rtc_camera_supersampled(&c->scene.camera, k, &fine));  // (the fine frame's limits: 2^32 pixels, 2^17 rows)
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     rtc_ctx::Adaptive& ad = c->adaptive;
+    rtc_ctx::Scene::Adaptive& sa = c->scene.adaptive;
     const Policy& P = c->policy;
-    const uint32_t width = c->hdr.width, height = c->hdr.height;
+    const uint32_t width = c->scene.hdr.width, height = c->scene.hdr.height;
     const size_t n_pixels = (size_t)width * height;
     // ---- the refinement kernel: the policy's question is asked with the frame's pixels, as the base pass asks it
     int32_t refine_depth = depth;
     if (refine_depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) refine_depth = RTC_STACK_DEPTH_BASE;  // (as rtc_ctx_render)
-    rtc_ctx::SceneKernel& slot = ad.kernel[k == 4u ? 1 : 0];
-    const bool want = !slot.variant.defs.empty() && wants_scene_kernel(P, n_pixels, c->trace.compile_any_size, c->trace.compile_never);
+    const int slot_i = k == 4u ? 1 : 0;
+    SceneKernel& slot = sa.kernel[slot_i];
+    const auto aot = [&](auto&& f) { dispatch_adaptive(c, k, f); };
+    const bool want = !slot.variant.defs.empty() && wants_scene_kernel(P, n_pixels, c->scene.plan.compile_any_size, c->scene.plan.compile_never);
     hipFunction_t fn = nullptr;
     std::string id;
-    RTC_TRY(scene_kernel_for(c, slot, refine_depth, want, false, ad.failed, ad.note, "refining with", false, &fn, &id));
+    RTC_TRY(scene_kernel_for(c, slot, refine_depth, want, false, sa.failed, sa.note, "refining with", false, &fn, &id));
     // ---- workspaces (the list: first use / a larger frame only)
-    HIP_TRY(grow(&ad.d_list, &ad.list_cap, n_pixels));
-    if (!ad.d_queue) HIP_TRY(hipMalloc((void**)&ad.d_queue, sizeof(AdaptiveQueue)));
-    for (hipEvent_t& e : ad.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(ad.d_list.grow(n_pixels));
+    if (!ad.d_queue) HIP_TRY(ad.d_queue.grow(1));
+    for (Event& e : ad.ev) HIP_TRY(e.create());
     const void* const kernel_key = fn ? (const void*)fn : aot_family(c).key(k);
-    const uint32_t n_workgroups = adaptive_grid((uint32_t)compute_units(c), (uint32_t)adaptive_wgs_per_cu(c, fn, k, kernel_key), width, height, k);
+    const uint32_t n_workgroups = adaptive_grid((uint32_t)compute_units(c), (uint32_t)wgs_per_cu(ad.wgs_per_cu, fn, kernel_key, aot), width, height, k);
     AdaptiveRefineArgs a;
     a.hdr = launch_hdr(c, refine_depth, 1u);  // (a step's counters are unpacked before the next: one ray per lane and counter)
     a.hdr.width = fine.width, a.hdr.height = fine.height, a.hdr.pixel_size = fine.pixel_size;  // (half extents and transform: the same, checked)
     a.hdr.has_scene_box = 0u;  // (rtc_adaptive.h)
-    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.soa = soa_view(c->d_soa, c->scene.hdr, c->d_texels);
     a.list = ad.d_list, a.queue = ad.d_queue;
     a.out = (float*)d_out_rgb;
     a.out_width = width;
@@ -2321,10 +2229,10 @@ rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float 
     // ---- the base frame B: the context's normal render, with its tiles, lists, feedback and stats
     RTC_TRY(rtc_ctx_render(c, depth, nullptr, d_out_rgb, stream_));
     // ---- warm up (in front of the events), mask, refinement, sum
-    RTC_TRY(warm_up(slot, kernel_key, stream, [&] {
+    RTC_TRY(warm_up(ad.warmed[slot_i], kernel_key, stream, [&] {
         AdaptiveRefineArgs w = a;
         w.warm = 1u;
-        return launch_adaptive(c, fn, k, 1u, stream, w);
+        return launch_refine(fn, 1u, stream, w, aot);
     }));
     HIP_TRY(hipMemsetAsync(ad.d_queue, 0, sizeof(AdaptiveQueue), stream));
     HIP_TRY(hipEventRecord(ad.ev[0], stream));
@@ -2335,11 +2243,11 @@ rtc_status rtc_ctx_render_adaptive(rtc_ctx* c, int32_t depth, uint32_t k, float 
     hipLaunchKernelGGL(adaptive_mask_kernel, dim3(adaptive_mask_grid((uint32_t)compute_units(c), m.n_blocks)), dim3(256), 0, stream, m);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ad.ev[1], stream));
-    HIP_TRY(launch_adaptive(c, fn, k, n_workgroups, stream, a));
+    HIP_TRY(launch_refine(fn, n_workgroups, stream, a, aot));
     HIP_TRY(hipEventRecord(ad.ev[2], stream));
     // (named once it has been launched: a call that failed on the way names no kernel it did not run)
-    ad.name = fn ? slot.variant.spec_name : slot.variant.family_name;
-    ad.id = fn ? id : aot_kernel_id(JitKind::ADAPTIVE, k);
+    sa.name = fn ? slot.variant.spec_name : slot.variant.family_name;
+    sa.id = fn ? id : aot_kernel_id(JitKind::ADAPTIVE, k);
     ad.ran = true;
     return RTC_OK;
 }
@@ -2361,8 +2269,8 @@ rtc_status rtc_ctx_adaptive_stats(rtc_ctx* c, rtc_adaptive_stats* out) {
     return RTC_OK;
 }
 
-const char* rtc_ctx_adaptive_kernel_name(rtc_ctx* c) { return c ? c->adaptive.name.c_str() : ""; }
-const char* rtc_ctx_adaptive_kernel_id(rtc_ctx* c) { return c ? c->adaptive.id.c_str() : ""; }
+const char* rtc_ctx_adaptive_kernel_name(rtc_ctx* c) { return c ? c->scene.adaptive.name.c_str() : ""; }
+const char* rtc_ctx_adaptive_kernel_id(rtc_ctx* c) { return c ? c->scene.adaptive.id.c_str() : ""; }
 
 // Diagnostic (not in rtc.h; tests/test_adaptive_boundary.py, no device needed): rtc_adaptive.h's adaptive_slot -- the function the
 // refinement kernel calls -- for slots [first_slot, first_slot + n), {entry, sx, sy, lane} per slot into `out`, and
@@ -2402,25 +2310,6 @@ static void dispatch_adaptive_seam(rtc_ctx* c, uint32_t k, F&& f) {
         else f(adaptive_seam_kernel<decltype(nobj)::value, decltype(simple)::value, 1>);
     });
 }
-static hipError_t launch_adaptive_seam(rtc_ctx* c, hipFunction_t fn, uint32_t k, uint32_t n_workgroups, hipStream_t stream, AdaptiveSeamArgs& a) {
-    return launch_scene_kernel(fn, dim3(n_workgroups), stream, a, [&] {
-        dispatch_adaptive_seam(c, k, [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_workgroups), dim3(256), 0, stream, a); });
-    });
-}
-static int adaptive_seam_wgs_per_cu(rtc_ctx* c, hipFunction_t fn, uint32_t k, const void* key) {
-    auto it = c->adaptive_seam.wgs_per_cu.find(key);
-    if (it != c->adaptive_seam.wgs_per_cu.end()) return it->second;
-    int n = 0;
-    hipError_t e = hipSuccess;
-    if (fn) e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, 0);
-    else dispatch_adaptive_seam(c, k, [&](auto kernel) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, 0); });
-    if (e != hipSuccess) (void)hipGetLastError();
-    if (e != hipSuccess || n < 1) n = 1;
-    if (n > 8) n = 8;
-    c->adaptive_seam.wgs_per_cu[key] = n;
-    return n;
-}
-
 static std::string adaptive_seam_aot_id(uint32_t k) { return aot_kernel_id(JitKind::ADAPTIVE_SEAM, k); }  // (rtc::ctx_adaptive_seam sees rtc::aot_kernel_id first)
 
 // Behind a base pass that ctx_render_slot has queued on `stream` for the same partition into d_share_f32: halo pass, banded mask,
@@ -2430,16 +2319,17 @@ static std::string adaptive_seam_aot_id(uint32_t k) { return aot_kernel_id(JitKi
 rtc_status rtc::ctx_adaptive_seam(rtc_ctx* c, int32_t depth, uint32_t k, float threshold, const rtc_partition* part, void* d_share_f32, void* d_out_u8,
                                   bool want_mask, void* stream_, void** d_mask) {
     if (d_mask) *d_mask = nullptr;
-    if (!c || !c->has_scene || c->ss_k != 1u || c->lens_mode) return fail(RTC_ERR_INVALID_ARG, "rtc_render_adaptive: the context holds no plain scene");
+    if (!c || !c->scene.ready || c->scene.ss_k != 1u || c->scene.lens_mode) return fail(RTC_ERR_INVALID_ARG, "rtc_render_adaptive: the context holds no plain scene");
     if (k != 2u && k != 4u) return fail(RTC_ERR_INVALID_ARG, "rtc_render_adaptive: supersampling factor %u: 2 or 4 rays per pixel side", k);
     rtc_camera fine;
-    RTC_TRY(rtc_camera_supersampled(&c->camera, k, &fine));
+    RTC_TRY(rtc_camera_supersampled(&c->scene.camera, k, &fine));
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     rtc_ctx::AdaptiveSeam& ad = c->adaptive_seam;
+    rtc_ctx::Scene::AdaptiveSeam& sa = c->scene.adaptive_seam;
     const Policy& P = c->policy;
     const Partition q = resolve(part);
-    const uint32_t width = c->hdr.width, height = c->hdr.height;
+    const uint32_t width = c->scene.hdr.width, height = c->scene.hdr.height;
     uint32_t n_halo = 0u;
     const AdaptiveShare share = adaptive_seam_share(width, height, q, &n_halo);
     ad.ran = false;
@@ -2451,28 +2341,30 @@ rtc_status rtc::ctx_adaptive_seam(rtc_ctx* c, int32_t depth, uint32_t k, float t
     // scene's first sighting (jit_get, lazy) as for its frame kernel
     int32_t refine_depth = depth;
     if (refine_depth > RTC_STACK_DEPTH_BASE && !scene_recurses(c)) refine_depth = RTC_STACK_DEPTH_BASE;
-    rtc_ctx::SceneKernel& slot = ad.kernel[k == 4u ? 2 : 1];
-    rtc_ctx::SceneKernel& halo_slot = ad.kernel[0];
-    const bool want = !slot.variant.defs.empty() && wants_scene_kernel(P, (uint64_t)width * height, c->trace.compile_any_size, c->trace.compile_never);
+    const int slot_i = k == 4u ? 2 : 1;
+    SceneKernel& slot = sa.kernel[slot_i];
+    SceneKernel& halo_slot = sa.kernel[0];
+    const auto aot = [&](auto&& f) { dispatch_adaptive_seam(c, k, f); };
+    const auto halo_aot = [&](auto&& f) { dispatch_adaptive_seam(c, 1u, f); };
+    const bool want = !slot.variant.defs.empty() && wants_scene_kernel(P, (uint64_t)width * height, c->scene.plan.compile_any_size, c->scene.plan.compile_never);
     const bool lazy = c->lazy_jit && P.specialise == 2;
     hipFunction_t fn = nullptr, halo_fn = nullptr;
     std::string id, halo_id;
-    RTC_TRY(scene_kernel_for(c, slot, refine_depth, want, lazy, ad.failed, ad.note, "refining with", false, &fn, &id));
-    if (n_halo) RTC_TRY(scene_kernel_for(c, halo_slot, refine_depth, want, lazy, ad.failed, ad.note, "refining with", false, &halo_fn, &halo_id));
+    RTC_TRY(scene_kernel_for(c, slot, refine_depth, want, lazy, sa.failed, sa.note, "refining with", false, &fn, &id));
+    if (n_halo) RTC_TRY(scene_kernel_for(c, halo_slot, refine_depth, want, lazy, sa.failed, sa.note, "refining with", false, &halo_fn, &halo_id));
     // ---- workspaces (grow-only; the caller's stream is the only one that has used them, and it is ordered)
-    HIP_TRY(grow(&ad.d_list, &ad.list_cap, n_share));
-    if (n_halo) HIP_TRY(grow(&ad.d_halo, &ad.halo_cap, n_halo_px * 3));
-    if (want_mask) HIP_TRY(grow(&ad.d_mask, &ad.mask_cap, n_share));
-    if (!ad.d_queue) HIP_TRY(hipMalloc((void**)&ad.d_queue, 2 * sizeof(AdaptiveQueue)));
-    for (hipEvent_t& e : ad.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(ad.d_list.grow(n_share));
+    if (n_halo) HIP_TRY(ad.d_halo.grow(n_halo_px * 3));
+    if (want_mask) HIP_TRY(ad.d_mask.grow(n_share));
+    if (!ad.d_queue) HIP_TRY(ad.d_queue.grow(2));
+    for (Event& e : ad.ev) HIP_TRY(e.create());
     const void* const kernel_key = fn ? (const void*)fn : aot_family(c).key(k);
     const void* const halo_key = halo_fn ? (const void*)halo_fn : aot_family(c).key(1u);
     const uint32_t n_cus = (uint32_t)compute_units(c);
     AdaptiveSeamArgs a;
     a.hdr = launch_hdr(c, refine_depth, 1u);
     a.hdr.has_scene_box = 0u;  // (rtc_adaptive.h)
-    a.soa = soa_view(c->d_soa, c->hdr, c->d_texels);
+    a.soa = soa_view(c->d_soa, c->scene.hdr, c->d_texels);
     a.share = share;
     a.depth = refine_depth;
     a.warm = 0u;
@@ -2481,34 +2373,34 @@ rtc_status rtc::ctx_adaptive_seam(rtc_ctx* c, int32_t depth, uint32_t k, float t
     a.hdr.width = fine.width, a.hdr.height = fine.height, a.hdr.pixel_size = fine.pixel_size;
     a.list = ad.d_list, a.queue = ad.d_queue, a.out = (float*)d_share_f32, a.out_u8 = (uint8_t*)d_out_u8, a.n_halo = 0u;
     // ---- warm up (in front of the events), halo, mask, refinement
-    RTC_TRY(warm_up(slot, kernel_key, stream, [&] {
+    RTC_TRY(warm_up(ad.warmed[slot_i], kernel_key, stream, [&] {
         AdaptiveSeamArgs w = a;
         w.warm = 1u;
-        return launch_adaptive_seam(c, fn, k, 1u, stream, w);
+        return launch_refine(fn, 1u, stream, w, aot);
     }));
     if (n_halo)
-        RTC_TRY(warm_up(halo_slot, halo_key, stream, [&] {
+        RTC_TRY(warm_up(ad.warmed[0], halo_key, stream, [&] {
             AdaptiveSeamArgs w = h;
             w.warm = 1u;
-            return launch_adaptive_seam(c, halo_fn, 1u, 1u, stream, w);
+            return launch_refine(halo_fn, 1u, stream, w, halo_aot);
         }));
     HIP_TRY(hipMemsetAsync(ad.d_queue, 0, 2 * sizeof(AdaptiveQueue), stream));
     HIP_TRY(hipEventRecord(ad.ev[0], stream));
     if (n_halo)
-        HIP_TRY(launch_adaptive_seam(c, halo_fn, 1u, adaptive_grid(n_cus, (uint32_t)adaptive_seam_wgs_per_cu(c, halo_fn, 1u, halo_key), width, n_halo, 1u), stream, h));
+        HIP_TRY(launch_refine(halo_fn, adaptive_grid(n_cus, (uint32_t)wgs_per_cu(ad.wgs_per_cu, halo_fn, halo_key, halo_aot), width, n_halo, 1u), stream, h, halo_aot));
     AdaptiveSeamMaskArgs m;
-    m.frame = (const float*)d_share_f32, m.halo = ad.d_halo, m.mask = want_mask ? ad.d_mask : nullptr, m.out_u8 = (uint8_t*)d_out_u8;
+    m.frame = (const float*)d_share_f32, m.halo = ad.d_halo, m.mask = want_mask ? ad.d_mask.get() : nullptr, m.out_u8 = (uint8_t*)d_out_u8;
     m.list = ad.d_list, m.queue = ad.d_queue, m.share = share, m.threshold = threshold;
     m.blocks_x = (width + 15u) / 16u, m.n_blocks = m.blocks_x * ((share.rows + 15u) / 16u);
     hipLaunchKernelGGL(adaptive_seam_mask_kernel, dim3(adaptive_mask_grid(n_cus, m.n_blocks)), dim3(256), 0, stream, m);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ad.ev[1], stream));
-    HIP_TRY(launch_adaptive_seam(c, fn, k, adaptive_grid(n_cus, (uint32_t)adaptive_seam_wgs_per_cu(c, fn, k, kernel_key), width, share.rows, k), stream, a));
+    HIP_TRY(launch_refine(fn, adaptive_grid(n_cus, (uint32_t)wgs_per_cu(ad.wgs_per_cu, fn, kernel_key, aot), width, share.rows, k), stream, a, aot));
     HIP_TRY(hipEventRecord(ad.ev[2], stream));
-    ad.name = fn ? slot.variant.spec_name : slot.variant.family_name;
-    ad.id = fn ? id : adaptive_seam_aot_id(k);
-    ad.halo_name = !n_halo ? std::string() : halo_fn ? halo_slot.variant.spec_name : halo_slot.variant.family_name;
-    ad.halo_id = !n_halo ? std::string() : halo_fn ? halo_id : adaptive_seam_aot_id(1u);
+    sa.name = fn ? slot.variant.spec_name : slot.variant.family_name;
+    sa.id = fn ? id : adaptive_seam_aot_id(k);
+    sa.halo_name = !n_halo ? std::string() : halo_fn ? halo_slot.variant.spec_name : halo_slot.variant.family_name;
+    sa.halo_id = !n_halo ? std::string() : halo_fn ? halo_id : adaptive_seam_aot_id(1u);
     ad.halo_pixels = n_halo_px;
     ad.ran = true;
     if (d_mask && want_mask) *d_mask = ad.d_mask;
@@ -2537,7 +2429,7 @@ extern "C" {
 // name and id; 2, 3: the halo pass's ("": no halo row) -- tests/test_gpu_seam_adaptive.py, through rtc_diag_seam_ctx.
 const char* rtc_diag_ctx_adaptive_seam_kernel(rtc_ctx* c, uint32_t what) {
     if (!c) return "";
-    const rtc_ctx::AdaptiveSeam& ad = c->adaptive_seam;
+    const rtc_ctx::Scene::AdaptiveSeam& ad = c->scene.adaptive_seam;
     return what == 0u ? ad.name.c_str() : what == 1u ? ad.id.c_str() : what == 2u ? ad.halo_name.c_str() : what == 3u ? ad.halo_id.c_str() : "";
 }
 // ... and the host-only plan of a part (tests/test_seam_adaptive_boundary.py, no device needed): the compact-row -> frame-row map
@@ -2582,27 +2474,27 @@ extern "C" {
 rtc_status rtc_ctx_stats(rtc_ctx* c, rtc_stats* out) {
     if (!c || !out) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_stats: null argument");
     std::memset(out, 0, sizeof(*out));
-    if (c->trace.last) {  // the last launch was rtc_ctx_trace: its counters, and the traces' own events
+    if (c->scene.trace.last) {  // the last launch was rtc_ctx_trace: its counters, and the traces' own events
         rtc_ctx::Trace& t = c->trace;
         out->pixels = t.last_n;
-        return read_launch_stats(c, t.d_total, t.events, t.events_used, t.kernel.note, out);
+        return read_launch_stats(c, t.d_total, t.events, t.events_used, c->scene.trace.kernel.note, out);
     }
     out->rows = c->last_rows;
     out->pixels = c->last_pixels;
     if (!c->rendered) return RTC_OK;
-    return read_launch_stats(c, c->d_total, c->events, c->events_used, c->render.note, out);
+    return read_launch_stats(c, c->d_total, c->events, c->events_used, c->scene.render.note, out);
 }
 
 const char* rtc_ctx_kernel_name(rtc_ctx* c) {
     if (!c) return "";
     if (c->wf_last) {  // the frame before this call was rendered by rtc_wavefront.h's kernels, not by the scene's per-pixel kernel
-        c->wf_name = "wavefront[tree walk of " + c->kernel_name + "]";
+        c->wf_name = "wavefront[tree walk of " + c->scene.kernel_name + "]";
         return c->wf_name.c_str();
     }
-    return c->kernel_name.c_str();
+    return c->scene.kernel_name.c_str();
 }
-const char* rtc_ctx_jit_status(rtc_ctx* c) { return c ? c->render.note.c_str() : ""; }
-const char* rtc_ctx_kernel_id(rtc_ctx* c) { return c ? c->kernel_id.c_str() : ""; }
+const char* rtc_ctx_jit_status(rtc_ctx* c) { return c ? c->scene.render.note.c_str() : ""; }
+const char* rtc_ctx_kernel_id(rtc_ctx* c) { return c ? c->scene.kernel_id.c_str() : ""; }
 
 rtc_status rtc_ctx_quantize(rtc_ctx* c, const void* d_rgb, uint64_t n, void* d_out_u8, void* stream_) {
     if (!c || !d_rgb || !d_out_u8) return fail(RTC_ERR_INVALID_ARG, "rtc_ctx_quantize: null argument");
@@ -2631,17 +2523,17 @@ rtc_status rtc_ctx_to_ppm(rtc_ctx* c, const void* d_rgb, uint32_t width, uint32_
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t words = (3u * width + 31u) / 32u;
-    HIP_TRY(grow(&c->d_ppm_rows, &c->ppm_rows_cap, (size_t)height + 1));
-    HIP_TRY(grow(&c->d_ppm_bits, &c->ppm_bits_cap, (size_t)height * words));
+    HIP_TRY(c->d_ppm_rows.grow((size_t)height + 1));
+    HIP_TRY(c->d_ppm_bits.grow((size_t)height * words));
     char head[40];
     const int head_len = snprintf(head, sizeof(head), "P3\n%u %u\n255\n", width, height);  // canvas.rs:60-63
     HIP_TRY(hipMemcpyAsync(d_text, head, (size_t)head_len, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(ppm_row_scan_kernel, dim3((height + 63) / 64), dim3(64), 0, stream, (const float*)d_rgb, width, height,
-                       c->d_ppm_rows, c->d_ppm_bits, words);
-    hipLaunchKernelGGL(ppm_row_offsets_kernel, dim3(1), dim3(1024), 0, stream, c->d_ppm_rows, height,
+                       c->d_ppm_rows.get(), c->d_ppm_bits.get(), words);
+    hipLaunchKernelGGL(ppm_row_offsets_kernel, dim3(1), dim3(1024), 0, stream, c->d_ppm_rows.get(), height,
                        (unsigned long long)head_len, c->d_ppm_rows + height);
     hipLaunchKernelGGL(ppm_emit_kernel, dim3((height + 3) / 4), dim3(256), 0, stream, (const float*)d_rgb, width, height,
-                       c->d_ppm_rows, c->d_ppm_bits, words, (char*)d_text);
+                       c->d_ppm_rows.get(), c->d_ppm_bits.get(), words, (char*)d_text);
     HIP_TRY(hipGetLastError());
     unsigned long long total = 0;
     HIP_TRY(hipMemcpyAsync(&total, c->d_ppm_rows + height, sizeof(total), hipMemcpyDeviceToHost, stream));
@@ -2652,12 +2544,8 @@ rtc_status rtc_ctx_to_ppm(rtc_ctx* c, const void* d_rgb, uint32_t width, uint32_
 
 // ---- batched test/utility entry points (host buffers) ---------------------------
 namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
+struct DevBuf : DeviceArray<uint8_t> {  // bytes, allocated once
+    hipError_t alloc(size_t n) { return grow(n ? n : 1); }
 };
 rtc_status begin_batch(const rtc_scene* scene, int32_t device, SceneHdr* hdr, DevBuf* soa_buf, DevBuf* tex_buf, bool allow_sequence = false) {
     int n = usable_devices();
@@ -2669,9 +2557,9 @@ rtc_status begin_batch(const rtc_scene* scene, int32_t device, SceneHdr* hdr, De
     if (st != RTC_OK) return st;
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(soa_buf->alloc(soa.size() * sizeof(float4)));
-    HIP_TRY(hipMemcpy(soa_buf->p, soa.data(), soa.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(soa_buf->get(), soa.data(), soa.size() * sizeof(float4), hipMemcpyHostToDevice));
     HIP_TRY(tex_buf->alloc(texels.size() * sizeof(float)));
-    if (!texels.empty()) HIP_TRY(hipMemcpy(tex_buf->p, texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!texels.empty()) HIP_TRY(hipMemcpy(tex_buf->get(), texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
     return RTC_OK;
 }
 }  // namespace
@@ -2692,13 +2580,13 @@ rtc_status rtc_color_at(const rtc_scene* scene, const float* origins, const floa
     HIP_TRY(d_o.alloc((size_t)n * 16));
     HIP_TRY(d_d.alloc((size_t)n * 16));
     HIP_TRY(d_out.alloc((size_t)n * 12));
-    HIP_TRY(hipMemcpy(d_o.p, origins, (size_t)n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d.p, directions, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_o.get(), origins, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d.get(), directions, (size_t)n * 16, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(color_at_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr,
-                       soa_view((const float4*)soa.p, hdr, (const float*)tex.p), (const float4*)d_o.p, (const float4*)d_d.p, n,
-                       depth, (float*)d_out.p);
+                       soa_view((const float4*)soa.get(), hdr, (const float*)tex.get()), (const float4*)d_o.get(), (const float4*)d_d.get(), n,
+                       depth, (float*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out_rgb, d_out.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_rgb, d_out.get(), (size_t)n * 12, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2720,8 +2608,8 @@ rtc_status rtc_hit_at(const rtc_scene* scene, const float* origins, const float*
     if (st != RTC_OK) return st;
     HIP_TRY(d_o.alloc((size_t)n * 16));
     HIP_TRY(d_d.alloc((size_t)n * 16));
-    HIP_TRY(hipMemcpy(d_o.p, origins, (size_t)n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d.p, directions, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_o.get(), origins, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d.get(), directions, (size_t)n * 16, hipMemcpyHostToDevice));
     // the planes in rtc_hit_planes' order: host pointer, bytes per element, where the device view keeps its pointer
     HitPlanes dev;
     std::memset(&dev, 0, sizeof(dev));
@@ -2738,13 +2626,13 @@ rtc_status rtc_hit_at(const rtc_scene* scene, const float* origins, const float*
     for (int k = 0; k < 11; k++) {
         if (!planes[k].host) continue;
         HIP_TRY(d_planes[k].alloc((size_t)n * planes[k].bytes));
-        *planes[k].dev = d_planes[k].p;
+        *planes[k].dev = d_planes[k].get();
     }
-    hipLaunchKernelGGL(hit_at_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr, soa_view((const float4*)soa.p, hdr, (const float*)tex.p),
-                       (const float4*)d_o.p, (const float4*)d_d.p, n, dev);
+    hipLaunchKernelGGL(hit_at_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr, soa_view((const float4*)soa.get(), hdr, (const float*)tex.get()),
+                       (const float4*)d_o.get(), (const float4*)d_d.get(), n, dev);
     HIP_TRY(hipGetLastError());
     for (int k = 0; k < 11; k++)
-        if (planes[k].host) HIP_TRY(hipMemcpy(planes[k].host, d_planes[k].p, (size_t)n * planes[k].bytes, hipMemcpyDeviceToHost));
+        if (planes[k].host) HIP_TRY(hipMemcpy(planes[k].host, d_planes[k].get(), (size_t)n * planes[k].bytes, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2757,14 +2645,14 @@ rtc_status rtc_intensity_at(const rtc_scene* scene, const float* points, uint32_
     if (st != RTC_OK) return st;
     HIP_TRY(d_p.alloc((size_t)n * 16));
     HIP_TRY(d_out.alloc((size_t)n * 4));
-    HIP_TRY(hipMemcpy(d_p.p, points, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_p.get(), points, (size_t)n * 16, hipMemcpyHostToDevice));
     bool simple = !hdr.has_patterns && hdr.n_objects <= 4 && !hdr.n_trav;  // (as rtc_ctx_set_scene decides it for the render kernels)
     for (uint32_t i = 0; simple && i < hdr.n_objects; i++) simple = simple_shape(shape_bits(scene->objects[i]));
     const auto kernel = simple ? intensity_at_kernel_simple : (hdr.n_objects <= 4 && !hdr.n_trav) ? intensity_at_kernel : intensity_at_kernel_generic;
-    hipLaunchKernelGGL(kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr, soa_view((const float4*)soa.p, hdr, (const float*)tex.p),
-                       (const float4*)d_p.p, n, (float*)d_out.p);
+    hipLaunchKernelGGL(kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr, soa_view((const float4*)soa.get(), hdr, (const float*)tex.get()),
+                       (const float4*)d_p.get(), n, (float*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2785,10 +2673,10 @@ rtc_status rtc_point_on_light(const rtc_light* light, const int32_t* cells_uv, u
     if (st != RTC_OK) return st;
     HIP_TRY(d_c.alloc((size_t)n * 8));
     HIP_TRY(d_out.alloc((size_t)n * 16));
-    HIP_TRY(hipMemcpy(d_c.p, cells_uv, (size_t)n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(point_on_light_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr, (const int2*)d_c.p, n, (float4*)d_out.p);
+    HIP_TRY(hipMemcpy(d_c.get(), cells_uv, (size_t)n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(point_on_light_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr, (const int2*)d_c.get(), n, (float4*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 16, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2803,13 +2691,13 @@ rtc_status rtc_is_shadowed(const rtc_scene* scene, const float* light_positions,
     HIP_TRY(d_l.alloc((size_t)n * 16));
     HIP_TRY(d_p.alloc((size_t)n * 16));
     HIP_TRY(d_out.alloc((size_t)n * 4));
-    HIP_TRY(hipMemcpy(d_l.p, light_positions, (size_t)n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_p.p, points, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_l.get(), light_positions, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_p.get(), points, (size_t)n * 16, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(is_shadowed_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, hdr,
-                       soa_view((const float4*)soa.p, hdr, (const float*)tex.p), (const float4*)d_l.p, (const float4*)d_p.p, n,
-                       (int32_t*)d_out.p);
+                       soa_view((const float4*)soa.get(), hdr, (const float*)tex.get()), (const float4*)d_l.get(), (const float4*)d_p.get(), n,
+                       (int32_t*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2824,12 +2712,12 @@ rtc_status rtc_powf(const float* x, const float* y, uint32_t n, int32_t device, 
     HIP_TRY(d_x.alloc((size_t)n * 4));
     HIP_TRY(d_y.alloc((size_t)n * 4));
     HIP_TRY(d_out.alloc((size_t)n * 4));
-    HIP_TRY(hipMemcpy(d_x.p, x, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_y.p, y, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(powf_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_x.p, (const float*)d_y.p, n,
-                       (float*)d_out.p);
+    HIP_TRY(hipMemcpy(d_x.get(), x, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_y.get(), y, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(powf_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_x.get(), (const float*)d_y.get(), n,
+                       (float*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2841,10 +2729,10 @@ rtc_status rtc_cosf(const float* x, uint32_t n, int32_t device, float* out) {
     DevBuf d_x, d_out;
     HIP_TRY(d_x.alloc((size_t)n * 4));
     HIP_TRY(d_out.alloc((size_t)n * 4));
-    HIP_TRY(hipMemcpy(d_x.p, x, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(cosf_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_x.p, n, (float*)d_out.p);
+    HIP_TRY(hipMemcpy(d_x.get(), x, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(cosf_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_x.get(), n, (float*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2857,12 +2745,12 @@ rtc_status rtc_atan2f(const float* y, const float* x, uint32_t n, int32_t device
     HIP_TRY(d_x.alloc((size_t)n * 4));
     HIP_TRY(d_y.alloc((size_t)n * 4));
     HIP_TRY(d_out.alloc((size_t)n * 4));
-    HIP_TRY(hipMemcpy(d_x.p, x, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_y.p, y, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(atan2f_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_y.p, (const float*)d_x.p, n,
-                       (float*)d_out.p);
+    HIP_TRY(hipMemcpy(d_x.get(), x, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_y.get(), y, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(atan2f_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_y.get(), (const float*)d_x.get(), n,
+                       (float*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 rtc_status rtc_acosf(const float* x, uint32_t n, int32_t device, float* out) {
@@ -2873,10 +2761,10 @@ rtc_status rtc_acosf(const float* x, uint32_t n, int32_t device, float* out) {
     DevBuf d_x, d_out;
     HIP_TRY(d_x.alloc((size_t)n * 4));
     HIP_TRY(d_out.alloc((size_t)n * 4));
-    HIP_TRY(hipMemcpy(d_x.p, x, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(acosf_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_x.p, n, (float*)d_out.p);
+    HIP_TRY(hipMemcpy(d_x.get(), x, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(acosf_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_x.get(), n, (float*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2906,7 +2794,7 @@ static rtc_status object_arg(const rtc_object* object, const char* who, Obj* ob,
     float4 tri[3] = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
     if (object->kind == RTC_TRIANGLE) pack_triangle(*object, tri);
     HIP_TRY(d_tri->alloc(sizeof(tri)));
-    HIP_TRY(hipMemcpy(d_tri->p, tri, sizeof(tri), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_tri->get(), tri, sizeof(tri), hipMemcpyHostToDevice));
     return RTC_OK;
 }
 
@@ -2925,13 +2813,13 @@ rtc_status rtc_local_intersect(const rtc_object* object, const float* origins, c
     HIP_TRY(d_d.alloc((size_t)n * 16));
     HIP_TRY(d_t.alloc((size_t)n * 16));
     HIP_TRY(d_c.alloc((size_t)n * 4));
-    HIP_TRY(hipMemcpy(d_o.p, origins, (size_t)n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d.p, directions, (size_t)n * 16, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(local_intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, ob, (const float4*)d_tri.p, (const float4*)d_o.p,
-                       (const float4*)d_d.p, n, (float4*)d_t.p, (int32_t*)d_c.p);
+    HIP_TRY(hipMemcpy(d_o.get(), origins, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d.get(), directions, (size_t)n * 16, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(local_intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, ob, (const float4*)d_tri.get(), (const float4*)d_o.get(),
+                       (const float4*)d_d.get(), n, (float4*)d_t.get(), (int32_t*)d_c.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out_t, d_t.p, (size_t)n * 16, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_count, d_c.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_t, d_t.get(), (size_t)n * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_count, d_c.get(), (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2946,11 +2834,11 @@ rtc_status rtc_normal_at(const rtc_object* object, const float* world_points, ui
     DevBuf d_p, d_out;
     HIP_TRY(d_p.alloc((size_t)n * 16));
     HIP_TRY(d_out.alloc((size_t)n * 16));
-    HIP_TRY(hipMemcpy(d_p.p, world_points, (size_t)n * 16, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(normal_at_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, ob, (const float4*)d_tri.p, (const float4*)d_p.p, n,
-                       (float4*)d_out.p);
+    HIP_TRY(hipMemcpy(d_p.get(), world_points, (size_t)n * 16, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(normal_at_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, ob, (const float4*)d_tri.get(), (const float4*)d_p.get(), n,
+                       (float4*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out.get(), (size_t)n * 16, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -2975,17 +2863,17 @@ rtc_status rtc_pattern_color_at(const rtc_pattern* pattern, const rtc_object* ob
     DevBuf d_pat, d_p, d_out, d_uv, d_tex;
     HIP_TRY(d_uv.alloc(uvrec.size() * sizeof(float4)));
     HIP_TRY(d_tex.alloc(texels.size() * sizeof(float)));
-    if (!uvrec.empty()) HIP_TRY(hipMemcpy(d_uv.p, uvrec.data(), uvrec.size() * sizeof(float4), hipMemcpyHostToDevice));
-    if (!texels.empty()) HIP_TRY(hipMemcpy(d_tex.p, texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!uvrec.empty()) HIP_TRY(hipMemcpy(d_uv.get(), uvrec.data(), uvrec.size() * sizeof(float4), hipMemcpyHostToDevice));
+    if (!texels.empty()) HIP_TRY(hipMemcpy(d_tex.get(), texels.data(), texels.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(d_pat.alloc(sizeof(rec)));
     HIP_TRY(d_p.alloc((size_t)n * 16));
     HIP_TRY(d_out.alloc((size_t)n * 12));
-    HIP_TRY(hipMemcpy(d_pat.p, rec, sizeof(rec), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_p.p, world_points, (size_t)n * 16, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(pattern_color_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, ob, (const float4*)d_pat.p,
-                       (const float4*)d_uv.p, (const float*)d_tex.p, (const float4*)d_p.p, n, (float*)d_out.p);
+    HIP_TRY(hipMemcpy(d_pat.get(), rec, sizeof(rec), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_p.get(), world_points, (size_t)n * 16, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(pattern_color_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, ob, (const float4*)d_pat.get(),
+                       (const float4*)d_uv.get(), (const float*)d_tex.get(), (const float4*)d_p.get(), n, (float*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out_rgb, d_out.p, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_rgb, d_out.get(), (size_t)n * 12, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
@@ -3020,13 +2908,13 @@ rtc_status rtc_selftest_fastmath(const float* vectors, uint32_t n, int32_t devic
     DevBuf d_v, d_out;
     HIP_TRY(d_v.alloc((size_t)n * 12));
     HIP_TRY(d_out.alloc(8));
-    HIP_TRY(hipMemcpy(d_v.p, vectors, (size_t)n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_out.p, 0, 8));
+    HIP_TRY(hipMemcpy(d_v.get(), vectors, (size_t)n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_out.get(), 0, 8));
     if (n)
-        hipLaunchKernelGGL(fastmath_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_v.p, n,
-                           (uint32_t*)d_out.p);
+        hipLaunchKernelGGL(fastmath_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, (const float*)d_v.get(), n,
+                           (uint32_t*)d_out.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(counts, d_out.p, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts, d_out.get(), 8, hipMemcpyDeviceToHost));
     return RTC_OK;
 }
 
